@@ -18,12 +18,20 @@ A "step" renders one frame:
 Inputs (scene tables, BVH, camera) are resident in HBM before timing; the
 frame stays on the device (host gather is not in `value`).  Timing: W untimed
 warm-up steps, then K steps bracketed by barrier + synchronize, max over
-ranks; kernel durations from HIP events on the launch stream.  After the
-timed region rank 0 also times the product's own entry point, rt_render
-(scene cache, N-device fan-out over per-device host threads, D2H into pinned
-memory and the host gather) as `end_to_end`.
+ranks; kernel durations from HIP events on the launch stream.
 
-Run:  python bench.py [--gpus N --steps K --warmup W] [--workload c1|c2|c3|c4]
+A plain run does only that: set-up, the W warm-up and K timed steps, the
+outputs if --dump-outputs DIR is given (the last timed step's frame and the
+counters, as DIR/*.npy), and the result line (`value`, `ms_per_step`, ...).
+--full adds every other leg, each with its own switch: the kernel launched
+alone under HIP events, a new shape's first launch, the other frames-in-flight
+basis, the sustained load, the statistics build's counted flops (roofline),
+the product's own entry point rt_render end to end on rank 0 (scene cache,
+N-device fan-out over per-device host threads, D2H into pinned memory and the
+host gather) as `end_to_end`, a fresh rt_main process, and the CPU baseline
+with the parity of the GPU frame against the oracle.
+
+Run:  python bench.py [--gpus N --steps K --warmup W] [--workload c1|c2|c3|c4] [--full] [--dump-outputs DIR]
       python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...   (N > 1)
 Prints ONE JSON line on rank 0.
 """
@@ -83,6 +91,16 @@ def parse():
     ap.add_argument("--steps", type=int, default=None,
                     help="timed frames (default: 100 for c1, a ~0.6 s GPU region; 5 for the larger workloads)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed frames (default: 5 for c1, 1 otherwise)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure (--pipelined, --sustained, --stats, "
+                         "--first-launch, --e2e, --cpu-baseline and the kernel launched alone under HIP events); "
+                         "without it a run sets up, warms up, times the steps and prints the line, and those "
+                         "switches have nothing to switch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/*.npy: frame.npy (this "
+                         "rank's rows x width x 3 fp32 frame; above the size limit frame_sample.npy, the pixels at "
+                         "frame_sample_index.npy's seeded flat indices) and counters.npy (path segments and "
+                         "samples per step, float64); _rank<r> is appended to the names when N > 1")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c1")
     ap.add_argument("--spp", type=int, default=None, help="override the workload's spp (not a bench line)")
@@ -122,7 +140,40 @@ def parse():
         a.warmup = 5 if a.workload == "c1" else 1
     if a.sustained is None:
         a.sustained = 5.0 if a.workload == "c1" else 0.0
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     return a
+
+
+# --dump-outputs: bytes over all ranks' files
+DUMP_LIMIT = 64 * 1000 * 1000
+
+
+def dump_outputs(directory, frame, rows, width, segments, samples, steps, rank, world):
+    """What the last timed step's rt_launch handed its caller, as float .npy
+    files: the frame (rows x width x 3 fp32, this rank's rows) and the two
+    counters, per step (the timed steps' totals / steps; every step renders
+    the same frame).  A frame above this rank's share of DUMP_LIMIT is
+    sampled: the pixels at fixed flat indices (generator seed 0, ascending),
+    the indices beside them.  Returns the names written."""
+    import numpy as np
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    px = frame.view(rows * width, 3)
+    share = DUMP_LIMIT // world - 4096   # (the counters and the .npy headers)
+    files = {}
+    if px.numel() * 4 <= share:
+        files[f"frame{tag}"] = px.cpu().numpy().reshape(rows, width, 3)
+    else:
+        k = share // (3 * 4 + 8)   # an fp32 pixel and its float64 index
+        idx = np.sort(np.random.default_rng(0).choice(rows * width, size=k, replace=False))
+        files[f"frame_sample{tag}"] = px[torch.from_numpy(idx).to(px.device)].cpu().numpy()
+        files[f"frame_sample_index{tag}"] = idx.astype(np.float64)
+    files[f"counters{tag}"] = np.array([segments / steps, samples / steps], dtype=np.float64)
+    for name, arr in files.items():
+        np.save(d / f"{name}.npy", arr)
+    return sorted(f"{name}.npy" for name in files)
 
 
 def host_cpus():
@@ -621,7 +672,7 @@ def main():
     # throughput); the other basis (2 if --inflight is 1) is timed the same
     # way after it and reported beside it (single_frame / pipelined)
     inflight = max(1, a.inflight)
-    other_nf = (2 if inflight == 1 else 1) if a.pipelined == "auto" else None
+    other_nf = (2 if inflight == 1 else 1) if a.full and a.pipelined == "auto" else None
     n_streams = max(inflight, other_nf or 1)
     streams = [torch.cuda.Stream(dev) for _ in range(n_streams)]
     outs = [torch.empty(rows * W * 3, dtype=torch.float32, device=dev) for _ in range(n_streams)]
@@ -649,7 +700,7 @@ def main():
     # one frame at a time on one stream (no RT_FLAG_STREAMED): the kernel's
     # own duration, which the roofline and the rocprof average use
     single_ms = None
-    if a.warmup > 0:
+    if a.full and a.warmup > 0:
         for _ in range(2):
             step(0, p)
         n1 = max(3, min(20, a.steps))
@@ -669,7 +720,7 @@ def main():
     # launches move by +-0.1 ms)
     first_ms = plain_ms = None
     first_all, plain_all = [], []
-    if a.warmup > 0 and a.schedule == 0 and p.row_end - p.row_begin > 16 and a.first_launch == "auto":
+    if a.full and a.warmup > 0 and a.schedule == 0 and p.row_end - p.row_begin > 16 and a.first_launch == "auto":
         other = type(p).from_buffer_copy(p)
         other.row_end = p.row_end - 8
 
@@ -723,6 +774,11 @@ def main():
                 "segments": cnt[0], "samples": cnt[1]}
 
     main_t = timed(inflight)
+    dumped = None
+    if a.dump_outputs:
+        # the last timed step's frame, before any other leg writes its buffer
+        dumped = dump_outputs(a.dump_outputs, outs[(a.steps - 1) % inflight], rows, W, main_t["segments"],
+                              main_t["samples"], a.steps, rank, world)
     other_t = timed(other_nf) if other_nf else None
     kern_ms = main_t["spans"]
     props = torch.cuda.get_device_properties(dev)
@@ -750,7 +806,7 @@ def main():
     # sustained load: as many single-stream frames as fit the requested seconds
     # at the slowest rank's rate, every rank at once
     sustained = None
-    if a.sustained > 0:
+    if a.full and a.sustained > 0:
         frames = max(1, int(a.sustained * 1e3 / max(r["ms_per_frame"] for r in per_rank)))
         barrier()
         torch.cuda.synchronize()
@@ -773,7 +829,7 @@ def main():
     res = None
     if rank == 0:
         occ = occupancy(ds, p)
-        stats = stats_leg(scene, cam, p, device, rows * W * 3) if a.stats == "auto" else None
+        stats = stats_leg(scene, cam, p, device, rows * W * 3) if a.full and a.stats == "auto" else None
         value = samples_total / elapsed / 1e6
         seg_per_sample = segs_total / max(samples_total, 1)
         # the dominant (only) kernel, per launch on rank 0
@@ -816,7 +872,8 @@ def main():
         res = {
             "metric": METRIC if (a.workload == "c1" and not a.spp) else metric_for(W, H, spp, depth), "value": value, "unit": "Mray-samples/s", "n_gpus": world, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True,
-            "scaling": a.scaling, "vs_baseline": None, "dtype": "fp32",
+            "scaling": a.scaling, "vs_baseline": None, "dtype": "fp32", "full": a.full,
+            "outputs": {"dir": str(a.dump_outputs), "files": dumped} if dumped else None,
             "data": f"synthetic: RTIOW cover scene ({len(scene)} bodies, generator seed 42), render seed {a.seed}",
             "config": {"workload": wl["name"] if not a.spp else f"{wl['name']} (spp override {spp})",
                        "width": W, "height": H, "spp": spp, "max_depth": depth, "bodies": len(scene),
@@ -863,7 +920,7 @@ def main():
                       "sample pool per 256-thread workgroup, fixed-point colour sums in LDS)",
             "sustained": sustained, "end_to_end": None, "cpu_baseline": None, "parity": None,
         }
-    if a.e2e == "auto":
+    if a.full and a.e2e == "auto":
         # the product fan-out over world devices, timed on rank 0 while the
         # other ranks wait at the barrier
         barrier()
@@ -873,7 +930,7 @@ def main():
                 res["end_to_end"]["first_process"] = first_process(wl, spp, depth, a.seed, world)
         barrier()
     if rank == 0:
-        if a.cpu_baseline == "auto" and world == 1:
+        if a.full and a.cpu_baseline == "auto" and world == 1:
             import numpy as np
             gpu_rows = segs_rows = None
             if a.scaling == "strong":

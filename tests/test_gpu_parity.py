@@ -297,16 +297,17 @@ def test_gpu_matches_committed_mirror_fixture(gpu_lib, samplers):
 
 
 @pytest.mark.parametrize("seed,samplers", [(1, "direct"), (2, "direct"), (1, "rejection")])
-def test_gpu_reproduces_reference_scene_ppm(gpu_lib, seed, samplers):
+def test_gpu_reproduces_reference_scene_ppm(gpu_lib, tmp_path, seed, samplers):
     """Full reference config (400x225, 100 spp, depth 50) vs the reference's
     own scene.ppm, within SURVEY.md §8c's statistical tolerance: the default
     loop-free samplers (two seeds) and the rejection samplers."""
     from rtclj import raytracing as R
     from test_oracle_pinning import within_tolerance
-    rgb = R.main(100, 50, out_path="/tmp/rtclj_scene_gpu.ppm", seed=seed, flags=_flags(samplers))
+    ppm = str(tmp_path / "scene_gpu.ppm")
+    rgb = R.main(100, 50, out_path=ppm, seed=seed, flags=_flags(samplers))
     ok, info = within_tolerance(rgb)
     assert all(ok.values()), (ok, info)
-    assert np.array_equal(R.read_ppm("/tmp/rtclj_scene_gpu.ppm"), rgb)
+    assert np.array_equal(R.read_ppm(ppm), rgb)
 
 
 def test_c1_frame_properties(gpu_lib):

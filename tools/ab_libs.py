@@ -41,7 +41,7 @@ def main():
     for r in range(a.rounds):
         for lib, v, name in runs:
             env = dict(os.environ, RTCLJ_LIBRARY=str(Path(lib).resolve()))
-            cmd = [sys.executable, str(ROOT / "bench.py"), "--cpu-baseline", "off", "--steps", str(a.steps),
+            cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--cpu-baseline", "off", "--steps", str(a.steps),
                    "--warmup", "2", "--variant", str(v)] + extra
             p = subprocess.run(["timeout", "-k", "10", "240"] + cmd, env=env, capture_output=True, text=True)
             if p.returncode != 0:

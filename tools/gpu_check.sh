@@ -20,7 +20,7 @@ for s in $STAGES; do
   case $s in
     tests) run pytest 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread ;;
     smoke) run smoke 180 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py --steps 20 --warmup 5
+    bench) run bench 600 python bench.py --full --steps 20 --warmup 5
            tail -1 "$OUT/bench.log" > "$OUT/bench.json" ;;
     prof)  run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o prof -- \
                python3 bench.py --steps 20 --warmup 5 --cpu-baseline off --e2e off --stats off --pipelined off --sustained 0 ;;
@@ -28,7 +28,7 @@ for s in $STAGES; do
     shard) run shard 300 python tools/shard_time.py --workload c1 --reps 5 --inflight 2 --frames 80
            grep "N=" "$OUT/shard.log" > "$OUT/shard.txt" ;;
     dist2) run dist2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-               --master-port 29511 bench.py --gpus 2 --steps 10 --warmup 3
+               --master-port 29511 bench.py --full --gpus 2 --steps 10 --warmup 3
            tail -1 "$OUT/dist2.log" > "$OUT/dist2.json" ;;
   esac
 done

@@ -3,7 +3,7 @@
 set -u
 OUT=${1:?outdir}; mkdir -p $OUT; export TMPDIR=/tmp
 step() { local n=$1 t=$2; shift 2; echo "== $n"; timeout -k 10 $t "$@" > $OUT/$n.log 2>&1; local rc=$?; echo "   rc=$rc"; if [ $rc -ne 0 ]; then tail -40 $OUT/$n.log; exit $rc; fi; }
-B="python bench.py --cpu-baseline off --e2e off"
+B="python bench.py --full --cpu-baseline off --e2e off"
 step c2 600 $B --workload c2
 step c3 600 $B --workload c3
 step c4 900 $B --workload c4 --steps 2 --warmup 1 --pipelined off

@@ -17,15 +17,15 @@ for s in $STEPS; do
             mkdir -p profiles/r05/pmc_c1 && cp $OUT/pmc_c1/*.csv profiles/r05/pmc_c1/ ;;
     pmc_c4) step pmc_c4 1000 bash profiles/pmc.sh $OUT/pmc_c4 --workload c4 --steps 2 --warmup 0
             mkdir -p profiles/r05/pmc_c4 && cp $OUT/pmc_c4/*.csv profiles/r05/pmc_c4/ ;;
-    bench) step bench 600 python bench.py; tail -1 $OUT/bench.log > $OUT/bench.json ;;
+    bench) step bench 600 python bench.py --full; tail -1 $OUT/bench.log > $OUT/bench.json ;;
     prof) step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o prof -- python3 bench.py --cpu-baseline off --e2e off --stats off --pipelined off --sustained 0 ;;
-    dist2) step dist2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 10 --warmup 3 --cpu-baseline off
+    dist2) step dist2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --steps 10 --warmup 3 --cpu-baseline off
            tail -1 $OUT/dist2.log > $OUT/dist2.json ;;
-    dist8) step dist8 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 8 --steps 10 --warmup 3 --cpu-baseline off
+    dist8) step dist8 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 8 --steps 10 --warmup 3 --cpu-baseline off
            tail -1 $OUT/dist8.log > $OUT/dist8.json ;;
     configs) for c in c2 c3 c4; do
                extra=""; [ "$c" = "c4" ] && extra="--steps 2 --warmup 1 --pipelined off"
-               step $c 500 python bench.py --cpu-baseline off --e2e off --workload $c $extra
+               step $c 500 python bench.py --full --cpu-baseline off --e2e off --workload $c $extra
                tail -1 $OUT/$c.log > $OUT/$c.json
              done ;;
     shard) step shard 400 python tools/shard_time.py --workload c1 --reps 9 --inflight 2 --frames 80

@@ -11,7 +11,7 @@ done
 for r in 1 2; do
   for L in "$A" "$B"; do
     n=$(basename "$L" .so)
-    RTCLJ_LIBRARY=$PWD/$L timeout -k 10 300 python bench.py --cpu-baseline off --e2e off --stats off --workload c4 --steps 2 --warmup 1 --pipelined off --sustained 0 > "$OUT/c4_${n}_$r.log" 2>&1 || exit 1
+    RTCLJ_LIBRARY=$PWD/$L timeout -k 10 300 python bench.py --full --cpu-baseline off --e2e off --stats off --workload c4 --steps 2 --warmup 1 --pipelined off --sustained 0 > "$OUT/c4_${n}_$r.log" 2>&1 || exit 1
     python3 -c "import json,sys; d=json.loads(open('$OUT/c4_${n}_$r.log').read().strip().splitlines()[-1]); print('$n', $r, round(d['value']), round(d['kernel_ms_avg'],1))"
   done
 done

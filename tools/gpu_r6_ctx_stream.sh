@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 for r in $(seq 1 "$R"); do
   for K in 0 1 2; do
-    RTCLJ_CTX_STREAM=$K timeout -k 10 300 python bench.py --cpu-baseline off --stats off --first-launch off --sustained 0 --steps 50 > "$OUT/r${r}_k$K.log" 2>&1 || exit $?
+    RTCLJ_CTX_STREAM=$K timeout -k 10 300 python bench.py --full --cpu-baseline off --stats off --first-launch off --sustained 0 --steps 50 > "$OUT/r${r}_k$K.log" 2>&1 || exit $?
     tail -1 "$OUT/r${r}_k$K.log" > "$OUT/r${r}_k$K.json"
     python -c "
 import json; l=json.load(open('$OUT/r${r}_k$K.json')); e=l['end_to_end']; f=e['frames_in_flight']

@@ -12,7 +12,7 @@ step cold 300 python -u tools/first_frame.py --workload c1 --rounds 9 --cold --j
 step prof_cold 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_cold" -o prof -- python3 tools/first_frame.py --child 0 0
 step prof_alt 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_alt" -o prof -- python3 tools/first_frame.py --rounds 5
 for v in 22 28 22 28; do
-  step bench_v$v 300 python bench.py --variant $v --cpu-baseline off --e2e off --sustained 0 --pipelined off --stats off --steps 20 --warmup 3
+  step bench_v$v 300 python bench.py --full --variant $v --cpu-baseline off --e2e off --sustained 0 --pipelined off --stats off --steps 20 --warmup 3
   tail -1 "$OUT/bench_v$v.log" >> "$OUT/bench_v$v.jsonl"
 done
 echo done

@@ -13,9 +13,9 @@ for s in $STEPS; do
   case $s in
     tests) step pytest 1500 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ;;
     smoke) step smoke 180 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 400 python bench.py; tail -1 "$OUT/bench.log" > "$OUT/c1_bench.json" ;;
+    bench) step bench 400 python bench.py --full; tail -1 "$OUT/bench.log" > "$OUT/c1_bench.json" ;;
     prof)  step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o prof -- python3 bench.py --cpu-baseline off --e2e off --stats off --pipelined off --sustained 0 --first-launch off ;;
-    dist2) step dist2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 20 --warmup 3
+    dist2) step dist2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 2 --steps 20 --warmup 3
            tail -1 "$OUT/dist2.log" > "$OUT/dist2_rehearsal_one_gpu.json" ;;
   esac
 done

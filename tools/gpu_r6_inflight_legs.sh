@@ -10,7 +10,7 @@ i=0
 for r in 1 2; do
   for LEGS in "" "--first-launch off" "--pipelined off" "--first-launch off --pipelined off" "--first-launch off --pipelined off --stats off"; do
     i=$((i+1))
-    timeout -k 10 300 python bench.py --cpu-baseline off --sustained 0 --steps 50 $LEGS > "$OUT/run$i.log" 2>&1 || exit $?
+    timeout -k 10 300 python bench.py --full --cpu-baseline off --sustained 0 --steps 50 $LEGS > "$OUT/run$i.log" 2>&1 || exit $?
     tail -1 "$OUT/run$i.log" > "$OUT/run$i.json"
     python -c "
 import json; l=json.load(open('$OUT/run$i.json')); e=l['end_to_end']; f=e['frames_in_flight']

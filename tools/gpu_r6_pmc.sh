@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 step() { local name=$1 lim=$2; shift 2; timeout -k 10 "$lim" "$@" > "$OUT/$name.log" 2>&1; local rc=$?;
   echo "$name rc=$rc"; grep -v amdgpu.ids "$OUT/$name.log" | grep -v '^{' | tail -4; [ $rc -ne 0 ] && exit $rc; return 0; }
-B="python bench.py --cpu-baseline off --e2e off"
+B="python bench.py --full --cpu-baseline off --e2e off"
 for s in $STEPS; do
   case $s in
     pmc1)    step pmc_c1 900 bash profiles/pmc.sh "$OUT/pmc_c1" ;;

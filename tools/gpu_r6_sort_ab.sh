@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 for r in $(seq 1 "$R"); do
   for S in lazy eager; do
     if [ $S = eager ]; then export RTCLJ_SORT_EAGER=1; else unset RTCLJ_SORT_EAGER; fi
-    timeout -k 10 300 python bench.py --cpu-baseline off --stats off --sustained 0 --steps 50 > "$OUT/r${r}_$S.log" 2>&1 || exit $?
+    timeout -k 10 300 python bench.py --full --cpu-baseline off --stats off --sustained 0 --steps 50 > "$OUT/r${r}_$S.log" 2>&1 || exit $?
     tail -1 "$OUT/r${r}_$S.log" > "$OUT/r${r}_$S.json"
     python -c "
 import json; l=json.load(open('$OUT/r${r}_$S.json')); e=l['end_to_end']

@@ -13,7 +13,7 @@ for s in $STEPS; do
   case $s in
     tests)   step pytest 1500 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ;;
     smoke)   step smoke 180 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)   step bench 400 python bench.py; tail -1 "$OUT/bench.log" > "$OUT/bench.json" ;;
+    bench)   step bench 400 python bench.py --full; tail -1 "$OUT/bench.log" > "$OUT/bench.json" ;;
     shard1)  step shard_c1 400 python -u tools/shard_time.py --workload c1 --worlds 1 2 4 8 --reps 9 --inflight 2 --frames 40 ;;
     shard34) step shard_c3 600 python -u tools/shard_time.py --workload c3 --worlds 1 8 --reps 3
              step shard_c4 900 python -u tools/shard_time.py --workload c4 --worlds 1 8 --reps 2 ;;

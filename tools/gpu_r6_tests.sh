@@ -14,6 +14,6 @@ rc=$?; echo "pytest rc=$rc"; tail -3 "$OUT/pytest.log"; [ $rc -ne 0 ] && exit $r
 timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; rc=$?; echo "smoke rc=$rc"; tail -1 "$OUT/smoke.log"; [ $rc -ne 0 ] && exit $rc
 timeout -k 10 400 python -u tools/shard_time.py --workload c1 --worlds 1 2 4 8 --reps 9 --configs "" "RTCLJ_TH4=0" > "$OUT/shard_c1.txt" 2>&1
 rc=$?; echo "shard rc=$rc"; tail -12 "$OUT/shard_c1.txt"; [ $rc -ne 0 ] && exit $rc
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > "$OUT/bench.log" 2>&1; rc=$?; echo "bench rc=$rc"; [ $rc -ne 0 ] && exit $rc
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench.log" 2>&1; rc=$?; echo "bench rc=$rc"; [ $rc -ne 0 ] && exit $rc
 tail -1 "$OUT/bench.log" > "$OUT/bench.json"
 echo done

@@ -2,7 +2,7 @@
 """Per-block VALU counts of a trace kernel from the marked ISA listing
 (make -C raytracing-clj_amd isa-marks: RT_MARK in trace_kernel.h), priced by
 tools/isa_cost.py's issue classes, and -- with the statistics build's events
-per wave iteration (a bench.py line's stats_build.per_wave_iter) -- the
+per wave iteration (a bench.py --full line's stats_build.per_wave_iter) -- the
 estimated VALU instructions and busy quad-cycles per wave iteration by block
 (DESIGN.md §9).  An instruction belongs to the last marker above it in the
 listing (layout order), so a block's count is its static code: a loop inside a
@@ -94,7 +94,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--isa", default=str(ROOT / "raytracing-clj_amd" / "lib" / "isa" / "trace_marks.s"))
     ap.add_argument("--kernel", default=DEFAULT_KERNEL)
-    ap.add_argument("--bench", default=None, help="a bench.py JSON line with stats_build (events per wave iteration)")
+    ap.add_argument("--bench", default=None, help="a bench.py --full JSON line with stats_build (events per wave iteration)")
     ap.add_argument("--pmc-valu-per-iter", type=float, default=None,
                     help="measured VALU instructions per wave iteration (PMC SQ_INSTS_VALU / wave iterations)")
     ap.add_argument("--iters-per-wave", type=float, default=69.0,
