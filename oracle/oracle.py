@@ -1,7 +1,7 @@
 """ctypes wrapper of oracle/_build/liboracle.so — TEST INFRASTRUCTURE ONLY.
 
 Parity status: pinned statistically against the reference's own render
-(/root/reference/scene.ppm -> tests/golden/scene_ppm.npz, scene_ppm_stats.json)
+(its scene.ppm -> tests/golden/scene_ppm.npz, scene_ppm_stats.json)
 and by hand-derived known answers (tests/golden/kats.json).  The reference's
 RNG is unseeded java.util.Random, so no bitwise reference image can exist.
 """
@@ -16,8 +16,14 @@ import numpy as np
 HERE = Path(__file__).resolve().parent
 LIB = HERE / "_build" / "liboracle.so"
 MODE_REF64, MODE_MIRROR32, MODE_BOOK64, MODE_REALM64, MODE_REALM32 = 0, 1, 2, 3, 4
+# MODE_REF64 / MODE_REALM64 with the two samplers drawn loop-free in plain
+# double from the same uniforms as the kernel's: the same-draw fp64 partners
+# of MODE_MIRROR32 | DIRECT / MODE_REALM32 | DIRECT.  They take no DIRECT bits.
+MODE_REF64D, MODE_REALM64D = 5, 6
+MODES64 = (MODE_REF64, MODE_BOOK64, MODE_REALM64, MODE_REF64D, MODE_REALM64D)
 # ored into MODE_MIRROR32 / MODE_REALM32: the kernel's loop-free samplers
-# (RT_FLAG_DIRECT_SAMPLERS): the unit-sphere draw, the defocus disk, both
+# (its default, i.e. without RT_FLAG_REJECTION_SAMPLERS): the unit-sphere
+# draw, the defocus disk, both
 DIRECT_SPHERE, DIRECT_DISK = 0x10, 0x20
 DIRECT = DIRECT_SPHERE | DIRECT_DISK
 
@@ -61,6 +67,14 @@ def _lib():
         d.oracle_sampler_draws.restype = C.c_int
         d.oracle_sampler_draws.argtypes = [C.c_int, C.c_uint64, C.c_int, fp]
         d.oracle_turn24.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.c_float, fp]
+        d.oracle_sampler_draws64.restype = C.c_int
+        d.oracle_sampler_draws64.argtypes = [C.c_int, C.c_uint64, C.c_int, dp]
+        d.oracle_direct_from_uniforms.restype = C.c_int
+        d.oracle_direct_from_uniforms.argtypes = [C.c_int, C.c_int, fp, C.POINTER(C.c_uint32), fp, dp]
+        d.oracle_set_sampler_bias.restype = None
+        d.oracle_set_sampler_bias.argtypes = [C.c_double]
+        d.oracle_get_sampler_bias.restype = C.c_double
+        d.oracle_get_sampler_bias.argtypes = []
         _dll = d
     return _dll
 
@@ -178,6 +192,41 @@ def sampler_draws(which, seed, n):
     if _lib().oracle_sampler_draws(SAMPLERS[which], seed, n, out.ctypes.data_as(C.POINTER(C.c_float))) != 0:
         raise ValueError(which)
     return out
+
+
+def sampler_draws64(which, seed, n):
+    """sampler_draws' stream through the fp64 loop-free samplers
+    ("sphere_direct" / "disk_direct" in plain double): (n, 3) float64."""
+    out = np.zeros((n, 3), np.float64)
+    if _lib().oracle_sampler_draws64(SAMPLERS[which], seed, n, out.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+        raise ValueError(which)
+    return out
+
+
+def direct_from_uniforms(which, xi1, u):
+    """One loop-free sampler in both precisions for given uniforms: xi1 (draws,
+    k / 2^24, float32) and the next step's 24-bit integers u ->
+    ((n, 3) float32 as the kernel computes it, (n, 3) float64 by definition)."""
+    xi1 = np.ascontiguousarray(xi1, np.float32).reshape(-1)
+    u = np.ascontiguousarray(u, np.uint32).reshape(-1)
+    assert len(xi1) == len(u)
+    o32, o64 = np.zeros((len(u), 3), np.float32), np.zeros((len(u), 3), np.float64)
+    if _lib().oracle_direct_from_uniforms(SAMPLERS[which], len(u), xi1.ctypes.data_as(C.POINTER(C.c_float)),
+                                          u.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                          o32.ctypes.data_as(C.POINTER(C.c_float)),
+                                          o64.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+        raise ValueError(which)
+    return o32, o64
+
+
+def sampler_bias(zscale=1.0):
+    """TEST-ONLY negative control: multiply the fp64 loop-free sphere draw's z
+    (MODE_REF64D / MODE_REALM64D, sampler_draws64) by zscale before r is
+    formed.  Process-wide, read at the start of a render; 1 is unbiased.
+    Callers reset it in a `finally`.  Returns the previous value."""
+    old = _lib().oracle_get_sampler_bias()
+    _lib().oracle_set_sampler_bias(float(zscale))
+    return old
 
 
 def turn24(u, r=1.0):

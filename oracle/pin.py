@@ -8,6 +8,14 @@ stream: the paths agree except where an fp32 decision flips, so the images
 agree far inside the reference fixture's statistical noise.  The bounds
 (`within`) are written in tests/test_oracle_cover_pin.py's docstring with
 the values they were measured at.
+
+Which bounds hold depends on whether the two images share their draws:
+BOUNDS for the rejection-sampler contract (RT_FLAG_REJECTION_SAMPLERS /
+MODE_MIRROR32) against MODE_REF64, and equally for the kernel's default path
+(loop-free samplers; MODE_MIRROR32 | DIRECT, MODE_REALM32 | DIRECT) against
+MODE_REF64D / MODE_REALM64D, the fp64 path with those samplers in plain
+double from the same uniforms; BOUNDS_INDEPENDENT for the default path
+against MODE_REF64 itself.
 """
 from __future__ import annotations
 
@@ -40,13 +48,14 @@ def compare(a64, seg_per_sample64, a32, seg_per_sample32, by):
 
 
 # same draws (the fp32 contract with the reference's rejection samplers,
-# RT_FLAG_REJECTION_SAMPLERS / MODE_MIRROR32): the paths agree except where an
-# fp32 decision flips, so per-pixel bounds hold
+# RT_FLAG_REJECTION_SAMPLERS / MODE_MIRROR32, against MODE_REF64; the default
+# path, MODE_MIRROR32 | DIRECT, against MODE_REF64D): the paths agree except
+# where an fp32 decision flips, so per-pixel bounds hold
 BOUNDS = {"seg_rel": 2e-3, "lin_mean": 5e-4, "px8_mean": 0.25, "px8_off_gt1": 0.02, "block_mean": 0.25,
           "block_max": 2.5}
-# independent draws (the kernel's default loop-free samplers draw the same
-# distributions from a different number of uniforms, so every path after the
-# first scatter differs): the bounds SURVEY.md §8c sets for a render against
+# independent draws (the kernel's default loop-free samplers against
+# MODE_REF64's rejection loops: the same distributions from a different number
+# of uniforms, so every path after the first scatter differs): the bounds SURVEY.md §8c sets for a render against
 # the reference's own unseeded one -- block means (8-bit) mean |d| <= 0.25,
 # max <= 2.5, per-pixel mean |d| <= 3.5 -- and segments/sample within 2e-3
 BOUNDS_INDEPENDENT = {"seg_rel": 2e-3, "px8_mean": 3.5, "block_mean": 0.25, "block_max": 2.5}

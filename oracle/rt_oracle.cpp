@@ -35,9 +35,18 @@
 //   MODE_REALM32 (4) — MODE_MIRROR32 with the kernel's RT_FLAG_REALM: the
 //     same three semantic changes, the pixel as total * RN(1/spp).
 //   mode | 0x10, | 0x20 (MODE_MIRROR32 / MODE_REALM32 only) — the kernel's
-//     loop-free samplers (RT_FLAG_DIRECT_SAMPLERS: 0x10 the unit-sphere draw
-//     of lambertian and metal, 0x20 the defocus disk): the same
-//     distributions as vec3a.clj:74-86, a fixed number of draws.
+//     loop-free samplers (its default; RT_FLAG_REJECTION_SAMPLERS switches
+//     them off: 0x10 the unit-sphere draw of lambertian and metal, 0x20 the
+//     defocus disk): the same distributions as vec3a.clj:74-86, a fixed
+//     number of draws.
+//   MODE_REF64D (5), MODE_REALM64D (6) — MODE_REF64 / MODE_REALM64 with the
+//     two samplers drawn loop-free in plain double (sphere_direct64 /
+//     disk_direct64: z = 2 xi1 - 1 or r = sqrt(xi1), the angle 2 pi u / 2^24,
+//     libm cos and sin), consuming the same two xorshift steps per call as
+//     the kernel's samplers.  Everything else is the fp64 path unchanged, so
+//     these are the same-draw fp64 partners of the kernel's default path
+//     (MODE_MIRROR32 | 0x30, MODE_REALM32 | 0x30): the paths coincide except
+//     where an fp32 decision flips.  They take no 0x10 / 0x20 bits.
 //
 // The reference's RNG is clojure.core/rand (unseeded java.util.Random,
 // vec3a.clj:71-72), so no bitwise reference image exists.  Both modes draw
@@ -60,11 +69,21 @@
 
 namespace {
 
-enum { MODE_REF64 = 0, MODE_MIRROR32 = 1, MODE_BOOK64 = 2, MODE_REALM64 = 3, MODE_REALM32 = 4 };
+enum {
+  MODE_REF64 = 0, MODE_MIRROR32 = 1, MODE_BOOK64 = 2, MODE_REALM64 = 3, MODE_REALM32 = 4,
+  MODE_REF64D = 5, MODE_REALM64D = 6
+};
 
 // MODE_BOOK64: MODE_REF64 but metal reflects unit(d) as the RTIOW book does
 // (negative control: scene.ppm must reject it).
 thread_local bool t_book_metal = false;
+// MODE_REF64D / MODE_REALM64D: the fp64 path draws its two samplers loop-free
+thread_local bool t_direct64 = false;
+// Test-only negative control (oracle_set_sampler_bias): the fp64 loop-free
+// sphere draw's z is multiplied by this before r is formed.  1 = unbiased.
+// A render reads g_zscale once, at its start.
+double g_zscale = 1.0;
+thread_local double t_zscale = 1.0;
 enum { LAMB = 0, METAL = 1, DIEL = 2, NONE = 3 };
 
 // ------------------------------------------------------------ RNG (contract)
@@ -93,6 +112,12 @@ struct Rng {
     return static_cast<float>(s >> 8) * 0x1p-24f;
   }
   double ud() { return static_cast<double>(uf()); }  // clojure (rand) stand-in
+  uint32_t u24() {  // the next step's 24-bit integer itself
+    s ^= s << 13;
+    s ^= s >> 17;
+    s ^= s << 5;
+    return s >> 8;
+  }
 };
 
 // ----------------------------------------------------------- fp64 reference
@@ -127,6 +152,37 @@ V random_in_unit_disk64(Rng& r) {  // vec3a.clj:81-86
     if (x * x + y * y < 1.0) return V{x, y, 0.0};
   }
 }
+// The loop-free samplers as their mathematical definition, in plain double
+// with libm (no polynomial, no quarter-turn trick, no fp32): uniform on the
+// unit sphere by Archimedes (z uniform, the angle uniform) and in the unit disk
+// (r^2 uniform), from one uniform xi1 and the 24-bit integer u of the next
+// xorshift step -- the draws and their order of the kernel's sphere_direct /
+// disk_direct, which approximate exactly this.
+inline V sphere_from64(double xi1, uint32_t u, double zscale) {
+  const double z = (2.0 * xi1 - 1.0) * zscale;
+  const double r = std::sqrt(1.0 - z * z);
+  const double phi = 2.0 * 3.141592653589793 * static_cast<double>(u) / 16777216.0;
+  return V{r * std::cos(phi), r * std::sin(phi), z};
+}
+inline V disk_from64(double xi1, uint32_t u) {
+  const double r = std::sqrt(xi1);
+  const double phi = 2.0 * 3.141592653589793 * static_cast<double>(u) / 16777216.0;
+  return V{r * std::cos(phi), r * std::sin(phi), 0.0};
+}
+inline V sphere_direct64(Rng& r, double zscale) {
+  const double xi1 = r.ud();
+  const uint32_t u = r.u24();
+  return sphere_from64(xi1, u, zscale);
+}
+inline V disk_direct64(Rng& r) {
+  const double xi1 = r.ud();
+  const uint32_t u = r.u24();
+  return disk_from64(xi1, u);
+}
+// the fp64 path's two draws: the reference's rejection loops, or (MODE_*64D)
+// the loop-free ones
+inline V unit_vec64(Rng& r) { return t_direct64 ? sphere_direct64(r, t_zscale) : random_unit64(r); }
+inline V in_unit_disk64(Rng& r) { return t_direct64 ? disk_direct64(r) : random_in_unit_disk64(r); }
 inline bool near_zero64(V v) {  // vec3a.clj:88-92
   return std::fabs(v.x) < 1e-8 && std::fabs(v.y) < 1e-8 && std::fabs(v.z) < 1e-8;
 }
@@ -209,14 +265,14 @@ V ray_color64(const Scene64& sc, V o, V d, int depth, Rng& rng, uint64_t* segs) 
     V att;
     switch (sc.kind[h.what]) {
       case LAMB: {  // material.clj:13-19
-        V s = vadd(random_unit64(rng), h.n);
+        V s = vadd(unit_vec64(rng), h.n);
         sd = near_zero64(s) ? h.n : s;
         att = alb;
         break;
       }
       case METAL: {  // material.clj:21-28
         const V refl = reflect64(t_book_metal ? vunit(d) : d, h.n);
-        const V r2 = vadd(vmul(random_unit64(rng), m[3]), refl);
+        const V r2 = vadd(vmul(unit_vec64(rng), m[3]), refl);
         if (!(vdot(r2, h.n) > 0)) return V{0, 0, 0};
         sd = r2;
         att = alb;
@@ -263,12 +319,12 @@ V ray_color_realm64(const Scene64& sc, V o, V d, int depth, Rng& rng, uint64_t* 
     V sd, att;
     switch (sc.kind[h.what]) {
       case LAMB:  // :137-143, no near-zero fallback
-        sd = vadd(random_unit64(rng), h.n);
+        sd = vadd(unit_vec64(rng), h.n);
         att = alb;
         break;
       case METAL: {  // :145-156
         const V refl = reflect64(d, h.n);
-        const V r2 = vadd(refl, vmul(random_unit64(rng), m[3]));
+        const V r2 = vadd(refl, vmul(unit_vec64(rng), m[3]));
         if (!(vdot(r2, h.n) > 0)) return V{0, 0, 0};
         sd = r2;
         att = alb;
@@ -326,19 +382,13 @@ void random_unit32(Rng& s, float& x, float& y, float& z) {
   z = z * il;
 }
 
-// The kernel's loop-free samplers (RT_FLAG_DIRECT_SAMPLERS;
-// raytracing-clj_amd/csrc/trace_kernel.h turn24 / sphere_direct /
-// disk_direct), op for op: the same distributions as vec3a.clj:74-86's
+// The kernel's loop-free samplers (its default, without
+// RT_FLAG_REJECTION_SAMPLERS; raytracing-clj_amd/csrc/trace_kernel.h turn24 /
+// sphere_direct / disk_direct), op for op: the same distributions as vec3a.clj:74-86's
 // rejection loops -- uniform on the unit sphere (z = 2 xi1 - 1, r = sqrt(1 -
 // z^2)) and in the unit disk (r = sqrt(xi1)) -- at the angle 2 pi xi2, whose
 // (cos, sin) come from the 24-bit integer of xi2: the nearest quarter turn q
 // and Taylor polynomials of the rest (|theta| <= pi/4), rotated by q.
-inline uint32_t u24(Rng& r) {
-  r.s ^= r.s << 13;
-  r.s ^= r.s >> 17;
-  r.s ^= r.s << 5;
-  return r.s >> 8;
-}
 void turn24(uint32_t u, float r, float& x, float& y) {
   const int32_t f = static_cast<int32_t>(u << 10) >> 10;       // low 22 bits, signed
   const uint32_t q = (u + 0x200000u) >> 22;                    // nearest quarter turn (mod 4)
@@ -359,14 +409,25 @@ void turn24(uint32_t u, float r, float& x, float& y) {
   x = rx * a;
   y = ry * b;
 }
-void sphere_direct32(Rng& s, float& x, float& y, float& z) {
-  z = 2.0f * s.uf() - 1.0f;
+// from the uniform xi1 and the next step's 24-bit integer u
+void sphere_from32(float xi1, uint32_t u, float& x, float& y, float& z) {
+  z = 2.0f * xi1 - 1.0f;
   const float r = std::sqrt(std::fmaf(-z, z, 1.0f));
-  turn24(u24(s), r, x, y);
+  turn24(u, r, x, y);
+}
+void disk_from32(float xi1, uint32_t u, float& x, float& y) {
+  const float r = std::sqrt(xi1);
+  turn24(u, r, x, y);
+}
+void sphere_direct32(Rng& s, float& x, float& y, float& z) {
+  const float xi1 = s.uf();
+  const uint32_t u = s.u24();
+  sphere_from32(xi1, u, x, y, z);
 }
 void disk_direct32(Rng& s, float& x, float& y) {
-  const float r = std::sqrt(s.uf());
-  turn24(u24(s), r, x, y);
+  const float xi1 = s.uf();
+  const uint32_t u = s.u24();
+  disk_from32(xi1, u, x, y);
 }
 enum { DIRECT_SPHERE = 1, DIRECT_DISK = 2 };   // the kernel's RT_SAMPLER_* bits (mode >> 4)
 
@@ -528,6 +589,7 @@ void sample32(const Scene32& sc, const float* cam, bool defocus, bool realm, int
 struct Job {
   int mode;
   int direct;   // the fp32 modes' loop-free samplers (DIRECT_* bits)
+  double zscale;  // g_zscale at the start of the render
   Scene64 s64;
   Scene32 s32;
   double cam64[18];
@@ -542,11 +604,13 @@ struct Job {
 void render_row(const Job& J, int ro, int x0, int x1, uint64_t* segs) {
   const int gy = J.row_begin + ro * J.row_step;
   t_book_metal = J.mode == MODE_BOOK64;
-  const bool realm = J.mode == MODE_REALM64 || J.mode == MODE_REALM32;
+  t_direct64 = J.mode == MODE_REF64D || J.mode == MODE_REALM64D;
+  t_zscale = J.zscale;
+  const bool realm = J.mode == MODE_REALM64 || J.mode == MODE_REALM32 || J.mode == MODE_REALM64D;
   for (int px = x0; px < x1; ++px) {
     const uint32_t pixel = static_cast<uint32_t>(gy) * static_cast<uint32_t>(J.width) + static_cast<uint32_t>(px);
     const size_t o = (static_cast<size_t>(ro) * J.width + px) * 3;
-    if (J.mode == MODE_REF64 || J.mode == MODE_BOOK64 || J.mode == MODE_REALM64) {
+    if (J.mode != MODE_MIRROR32 && J.mode != MODE_REALM32) {
       // compute-pixel (raytracing.clj:141-155)
       const double* c = J.cam64;
       const V center{c[0], c[1], c[2]}, p00{c[3], c[4], c[5]}, du{c[6], c[7], c[8]}, dv{c[9], c[10], c[11]};
@@ -560,7 +624,7 @@ void render_row(const Job& J, int ro, int x0, int x1, uint64_t* segs) {
         const V ps = vadd(ps0, vmul(dv, gy + (xi2 - 0.5)));
         V org = center;
         if (J.defocus) {  // defocus-disk-sample (raytracing.clj:89-93)
-          const V p = random_in_unit_disk64(rng);
+          const V p = in_unit_disk64(rng);
           org = vadd(vadd(center, vmul(disk_u, p.x)), vmul(disk_v, p.y));
         }
         const V dir = vsub(ps, org);
@@ -618,7 +682,7 @@ extern "C" {
 
 // Render rows row_begin, row_begin+row_step, ... < row_end into out
 // (compacted: rows x width x 3 fp32, and
-// optionally out64 in double for MODE_REF64).  sphere/mat: n x 4 doubles,
+// optionally out64 in double for the fp64 modes).  sphere/mat: n x 4 doubles,
 // cam: 18 doubles (center, p00, du, dv, disk_u, disk_v).  nthreads <= 0 ->
 // hardware concurrency.  counters (nullable): [segments, samples].
 // oracle_render_cols: only columns [col_begin, col_end) of those rows (the
@@ -634,11 +698,12 @@ int oracle_render_cols(int mode, int n, const double* sphere, const int* kind, c
   // mode | (DIRECT_* << 4): the fp32 mirrors with the kernel's loop-free samplers
   const int direct = (mode >> 4) & (DIRECT_SPHERE | DIRECT_DISK);
   mode &= 0xf;
-  if (mode < MODE_REF64 || mode > MODE_REALM32 || (direct && mode != MODE_MIRROR32 && mode != MODE_REALM32))
+  if (mode < MODE_REF64 || mode > MODE_REALM64D || (direct && mode != MODE_MIRROR32 && mode != MODE_REALM32))
     return -1;
   Job J{};
   J.mode = mode;
   J.direct = direct;
+  J.zscale = g_zscale;
   J.s64 = Scene64{n, sphere, kind, mat};
   J.s32.n = n;
   J.s32.kind = kind;
@@ -853,6 +918,53 @@ int oracle_sampler_draws(int which, uint64_t seed, int n, float* out) {
   }
   return 0;
 }
+
+// The fp64 loop-free samplers from the same keyed stream as
+// oracle_sampler_draws: which 1 sphere_direct64, 3 disk_direct64 (the numbers
+// of their fp32 counterparts).  out: n x 3 doubles.
+int oracle_sampler_draws64(int which, uint64_t seed, int n, double* out) {
+  if ((which != 1 && which != 3) || n < 0 || (n > 0 && !out)) return -1;
+  Rng r{sample_state(seed_key(seed), 0, 0)};
+  for (int i = 0; i < n; ++i) {
+    const V v = which == 1 ? sphere_direct64(r, g_zscale) : disk_direct64(r);
+    out[3 * i] = v.x;
+    out[3 * i + 1] = v.y;
+    out[3 * i + 2] = v.z;
+  }
+  return 0;
+}
+
+// Both precisions of one loop-free sampler for given uniforms: xi1[i] (a
+// draw: k / 2^24) and the 24-bit integer u[i].  which as above.  out32: n x 3
+// floats, out64: n x 3 doubles.
+int oracle_direct_from_uniforms(int which, int n, const float* xi1, const uint32_t* u, float* out32,
+                                double* out64) {
+  if ((which != 1 && which != 3) || n < 0 || (n > 0 && (!xi1 || !u || !out32 || !out64))) return -1;
+  for (int i = 0; i < n; ++i) {
+    const uint32_t uu = u[i] & 0xffffffu;
+    float x = 0, y = 0, z = 0;
+    V v;
+    if (which == 1) {
+      sphere_from32(xi1[i], uu, x, y, z);
+      v = sphere_from64(static_cast<double>(xi1[i]), uu, g_zscale);
+    } else {
+      disk_from32(xi1[i], uu, x, y);
+      v = disk_from64(static_cast<double>(xi1[i]), uu);
+    }
+    out32[3 * i] = x;
+    out32[3 * i + 1] = y;
+    out32[3 * i + 2] = z;
+    out64[3 * i] = v.x;
+    out64[3 * i + 1] = v.y;
+    out64[3 * i + 2] = v.z;
+  }
+  return 0;
+}
+
+// Test-only negative control: scale the fp64 loop-free sphere draw's z (1 =
+// unbiased).  Process-wide; a render reads it once, at its start.
+void oracle_set_sampler_bias(double zscale) { g_zscale = zscale; }
+double oracle_get_sampler_bias() { return g_zscale; }
 
 // turn24 for given 24-bit integers: out[2i], out[2i+1] = r (cos, sin) of 2 pi u / 2^24
 void oracle_turn24(int n, const uint32_t* u, float r, float* out) {

@@ -9,7 +9,11 @@ against REF64 the default is held to oracle/pin.py's BOUNDS_INDEPENDENT (SURVEY.
 bounds for a render against the reference's own unseeded one), and the
 kernel with RT_FLAG_REJECTION_SAMPLERS -- the same draws as REF64 -- to the
 same-draw BOUNDS.  Bit-exact checks compare each with its own fp32 mirror
-(MODE_MIRROR32 | DIRECT, MODE_MIRROR32).
+(MODE_MIRROR32 | DIRECT, MODE_MIRROR32).  The default kernel's own same-draw
+fp64 pin -- against MODE_REF64D, the fp64 path with the loop-free samplers in
+plain double -- is tests/test_gpu_ref64_direct.py (C0, C1 rows, C4's kernel,
+the reference scene, realm, variants 16 and 18, all under BOUNDS); the
+comparisons with MODE_REF64 here stay as the check of the distributions.
 
   C1 cover 1200x675, 100 spp, depth 50: the kernel's frame against the
      oracle's MODE_REF64 (the Clojure path in double) on every 8th row at

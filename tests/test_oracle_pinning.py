@@ -9,6 +9,14 @@ measured noise floor in brackets):
   neighbour-difference std: within 0.15 of scene.ppm's (pins spp)
   per-pixel mean |d| <= 3.5 [3.23]
 The book's normalised-metal variant must FAIL these (fixture discriminates).
+
+The same frame also pins the kernel's default contract (MODE_MIRROR32 |
+DIRECT) against its same-draw fp64 reference MODE_REF64D (the Clojure path in
+double with the two samplers loop-free in plain double, from the same
+uniforms), with oracle/pin.py's same-draw BOUNDS: measured linear mean |d|
+2.5e-6 (<= 5e-4), 8-bit per-pixel 7e-4 (<= 0.25), off by > 1 0.008 % (<= 2 %),
+block means 5e-4 / 0.013, segments/sample 1.6e-6.  With the fp64 sphere
+draw's z scaled by 0.99 the linear mean is 7.5e-4 and off by > 1 2.02 %: fails.
 """
 import json
 from pathlib import Path
@@ -50,11 +58,15 @@ def test_fixture_matches_its_stats():
     assert np.allclose(mean, STATS["mean"]) and np.allclose(blocks, STATS["blocks"]) and np.allclose(nbr, STATS["nbr_std"])
 
 
-def _render(mode, seed=1, spp=100):
+def _render(mode, seed=1, spp=100, zscale=1.0):
     from rtclj import raytracing as R
     sph, kind, mat = R.flatten64(R.hittables)
     cam = oracle.camera(400, 225, **R.REFERENCE_CAMERA)
-    out, _, segs, smp = oracle.render(mode, sph, kind, mat, cam, 1, 400, 225, spp, 50, seed=seed)
+    oracle.sampler_bias(zscale)   # test-only negative control; 1 = unbiased
+    try:
+        out, _, segs, smp = oracle.render(mode, sph, kind, mat, cam, 1, 400, 225, spp, 50, seed=seed)
+    finally:
+        oracle.sampler_bias(1.0)
     return out, segs / smp
 
 
@@ -107,6 +119,26 @@ def test_direct_sampler_mirror_reproduces_scene_ppm(seed):
     ok, info = within_tolerance(_vq(lin))
     assert all(ok.values()), (ok, info)
     assert seg == pytest.approx(3.675, abs=0.02)
+
+
+def test_direct_sampler_mirror_tracks_ref64d():
+    """The default contract against its same-draw fp64 reference (module
+    docstring), and the negative control: a 1 % bias of the fp64 unit-sphere
+    draw fails the same bounds."""
+    from oracle.pin import compare, within
+    lin32, seg32 = _render(oracle.MODE_MIRROR32 | oracle.DIRECT)
+    lin64, seg64 = _render(oracle.MODE_REF64D)
+    st = compare(lin64, seg64, lin32, seg32, by=9)
+    print("reference scene MIRROR32|DIRECT vs REF64D:", st)
+    ok = within(st)
+    assert all(ok.values()), (ok, st)
+    assert seg64 == pytest.approx(3.675, abs=0.02)
+    bias, segb = _render(oracle.MODE_REF64D, zscale=0.99)
+    assert oracle.sampler_bias() == 1.0
+    st = compare(bias, segb, lin32, seg32, by=9)
+    print("the same, z * 0.99:", st)
+    ok = within(st)
+    assert not all(ok.values()) and not ok["lin_mean"], (ok, st)
 
 
 def test_book_metal_variant_is_rejected():

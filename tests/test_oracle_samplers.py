@@ -23,6 +23,10 @@ pin the distributions directly and then the renders they make:
     4.5e-3 / 1.1e-4 (the direct mirror: 6.1e-4 / 4.9e-3 / 2.3e-4); the book's
     normalised-metal control (MODE_BOOK64) is far outside (1.0e-2 / 0.18 /
     1.6e-2).
+  * turn24 over all 2^24 inputs, and the fp32 samplers draw by draw against
+    their definition in plain double (oracle MODE_REF64D's samplers: z = 2
+    xi1 - 1 or r = sqrt(xi1), the angle 2 pi u / 2^24, libm) from the same
+    uniforms, every component within 3.5e-7 (derived in the test).
 tests/test_oracle_pinning.py holds the direct mirror to the reference's own
 scene.ppm with SURVEY.md §8c's tolerances as well.
 """
@@ -48,6 +52,103 @@ def test_turn24_quarter_turns_and_sweep():
     # exact at the quarter turns (the signs ride on r: x = -0 at a quarter turn)
     q = oracle.turn24(np.array([0, 1 << 22, 1 << 23, 3 << 22], np.uint32), r=0.5)
     assert np.array_equal(q, np.array([[0.5, 0], [0, 0.5], [-0.5, 0], [0, -0.5]], np.float32))
+
+
+def test_turn24_every_input():
+    """All 2^24 angles against double cos / sin with the sweep's bound 2e-7
+    (measured maximum 7.51e-8), and |cos^2 + sin^2 - 1| <= 6e-7: two
+    components each within e = 2e-7 of a unit vector give at most
+    2 e (|cos| + |sin|) + 2 e^2 <= 2 sqrt(2) e + 2 e^2 = 5.7e-7 (measured
+    1.45e-7)."""
+    emax = nmax = 0.0
+    for c in range(16):
+        u = np.arange(c << 20, (c + 1) << 20, dtype=np.uint32)
+        got = oracle.turn24(u).astype(np.float64)
+        phi = 2 * np.pi * u.astype(np.float64) / (1 << 24)
+        emax = max(emax, np.abs(got - np.stack([np.cos(phi), np.sin(phi)], 1)).max())
+        nmax = max(nmax, np.abs((got ** 2).sum(1) - 1).max())
+    print("turn24, all 2^24 inputs: max |error|", emax, "max |cos^2 + sin^2 - 1|", nmax)
+    assert emax <= 2e-7, emax
+    assert nmax <= 6e-7, nmax
+
+
+# The fp32 samplers against their definition in double, per component:
+#   turn24's (cos, sin) within 2e-7 of the exact ones (above), scaled by r <= 1;
+#   r: 2 xi1 - 1 is exact in fp32 (xi1 = k / 2^24), fma(-z, z, 1) rounds once
+#   (relative 2^-24 of 1 - z^2, i.e. 2^-25 of r) and the square root once more
+#   (2^-24), the disk's sqrt(xi1) once: |dr| <= 1.5 * 2^-24 = 8.9e-8;
+#   the product r * cos rounds once: 2^-24 = 6.0e-8.
+# 2e-7 + 8.9e-8 + 6.0e-8 = 3.5e-7.  z itself is exact.
+PER_DRAW = 3.5e-7
+
+
+def test_direct_samplers_agree_with_their_fp64_definition_draw_by_draw(draws):
+    """2^20 draws from the same keyed stream (measured maxima: sphere 1.13e-7,
+    disk 1.09e-7)."""
+    for k in ("sphere_direct", "disk_direct"):
+        d64 = oracle.sampler_draws64(k, 12345, N)
+        err = np.abs(draws[k] - d64)
+        print(k, "fp32 vs fp64 definition, 2^20 draws: max |d| per component", err.max(0))
+        assert err.max() <= PER_DRAW, (k, err.max(), np.argmax(err.max(1)))
+        assert (d64[:, 2] == draws[k][:, 2]).all()          # z: exact in fp32 (0 for the disk)
+    s64 = oracle.sampler_draws64("sphere_direct", 12345, 4096)
+    assert np.abs(np.linalg.norm(s64, axis=1) - 1).max() <= 1e-15
+    with pytest.raises(ValueError):
+        oracle.sampler_draws64("sphere_rejection", 1, 4)
+
+
+def test_direct_samplers_at_the_edge_uniforms():
+    """The uniforms a random stream hardly visits: xi1 at both ends of its
+    range and its middle (the poles and the equator; the disk's centre and
+    rim), u at every quarter turn, either side of the first octant boundary
+    (where turn24 switches polynomials) and the last angle."""
+    xi = np.array([0, 2.0 ** -24, 0.5, 1 - 2.0 ** -24], np.float32)
+    u = np.array([0, (1 << 21) - 1, 1 << 21, 1 << 22, 1 << 23, 3 << 22, (1 << 24) - 1], np.uint32)
+    X, U = (a.ravel() for a in np.meshgrid(xi, u, indexing="ij"))
+    phi = 2 * np.pi * U.astype(np.float64) / (1 << 24)
+    for k in ("sphere_direct", "disk_direct"):
+        a32, a64 = oracle.direct_from_uniforms(k, X, U)
+        err = np.abs(a32.astype(np.float64) - a64)
+        print(k, "edge uniforms: max |d|", err.max())
+        assert err.max() <= PER_DRAW, (k, err.max(), X[np.argmax(err.max(1))], U[np.argmax(err.max(1))])
+        # the fp64 entry point is the definition itself
+        x1 = X.astype(np.float64)
+        z = 2 * x1 - 1
+        r = np.sqrt(1 - z * z) if k == "sphere_direct" else np.sqrt(x1)
+        want = np.stack([r * np.cos(phi), r * np.sin(phi), z if k == "sphere_direct" else 0 * z], 1)
+        assert np.abs(a64 - want).max() <= 1e-15, k
+    # the pole: xi1 = 0 is z = -1, r = 0 in both precisions
+    a32, a64 = oracle.direct_from_uniforms("sphere_direct", X[:len(u)], U[:len(u)])
+    assert (a32[:, 2] == -1).all() and (a32[:, :2] == 0).all() and (a64[:, 2] == -1).all() and (a64[:, :2] == 0).all()
+
+
+def test_entry_points_and_the_stream_are_the_same_samplers():
+    """direct_from_uniforms fed the keyed stream's own draws gives
+    sampler_draws / sampler_draws64 bit for bit (two xorshift steps a call)."""
+    n = 4096
+    st = oracle.rng_stream(12345, 0, 0, 2 * n)
+    xi, u = st[0::2], (st[1::2].astype(np.float64) * (1 << 24)).astype(np.uint32)
+    for k in ("sphere_direct", "disk_direct"):
+        a32, a64 = oracle.direct_from_uniforms(k, xi, u)
+        assert np.array_equal(a32, oracle.sampler_draws(k, 12345, n)), k
+        assert np.array_equal(a64, oracle.sampler_draws64(k, 12345, n)), k
+
+
+def test_sampler_bias_scales_z_of_the_fp64_sphere_draw_only():
+    base = oracle.sampler_draws64("sphere_direct", 7, 1024)
+    disk = oracle.sampler_draws64("disk_direct", 7, 1024)
+    m32 = oracle.sampler_draws("sphere_direct", 7, 1024)
+    assert oracle.sampler_bias(0.97) == 1.0
+    try:
+        b = oracle.sampler_draws64("sphere_direct", 7, 1024)
+        assert np.allclose(b[:, 2], 0.97 * base[:, 2], rtol=0, atol=1e-15)
+        r = np.sqrt(1 - b[:, 2] ** 2)                          # r formed from the scaled z: still unit length
+        assert np.abs(np.hypot(b[:, 0], b[:, 1]) - r).max() <= 1e-15
+        assert np.array_equal(oracle.sampler_draws64("disk_direct", 7, 1024), disk)
+        assert np.array_equal(oracle.sampler_draws("sphere_direct", 7, 1024), m32)
+    finally:
+        assert oracle.sampler_bias(1.0) == 0.97
+    assert np.array_equal(oracle.sampler_draws64("sphere_direct", 7, 1024), base)
 
 
 def _chi2_uniform(x, lo, hi, bins=64):
@@ -125,3 +226,26 @@ def test_direct_flag_needs_an_fp32_mode():
             oracle.render(bad, sph, kind, mat, cam, 1, 8, 8, 1, 5)
     a = oracle.render(oracle.MODE_REALM32 | oracle.DIRECT, sph, kind, mat, cam, 1, 8, 8, 2, 5)[0]
     assert np.isfinite(a).all()
+
+
+def test_fp64_direct_modes_take_no_direct_bits():
+    """MODE_REF64D / MODE_REALM64D are modes of their own (the fp64 path with
+    the loop-free samplers in double): they reject the fp32 mirrors' 0x10 /
+    0x20 bits as every fp64 mode does, give the double image, and draw a fixed
+    two uniforms a sampler call, unlike the rejection loops."""
+    from rtclj import raytracing as R
+    sph, kind, mat = R.flatten64(R.hittables)
+    cam = oracle.camera(8, 8, **R.REFERENCE_CAMERA)
+    assert (oracle.MODE_REF64D, oracle.MODE_REALM64D) == (5, 6)
+    for mode in (oracle.MODE_REF64D, oracle.MODE_REALM64D):
+        for bits in (oracle.DIRECT_SPHERE, oracle.DIRECT_DISK, oracle.DIRECT, 0x40):
+            with pytest.raises(ValueError):
+                oracle.render(mode | bits, sph, kind, mat, cam, 1, 8, 8, 1, 5)
+        out, out64, segs, smp = oracle.render(mode, sph, kind, mat, cam, 1, 8, 8, 2, 5, want64=True)
+        assert out64 is not None and np.isfinite(out64).all() and smp == 128 and segs >= smp
+        assert np.array_equal(out, out64.astype(np.float32))
+    with pytest.raises(ValueError):
+        oracle.render(7, sph, kind, mat, cam, 1, 8, 8, 1, 5)
+    a = oracle.render(oracle.MODE_REF64, sph, kind, mat, cam, 1, 8, 8, 2, 5)[0]
+    b = oracle.render(oracle.MODE_REF64D, sph, kind, mat, cam, 1, 8, 8, 2, 5)[0]
+    assert not np.array_equal(a, b)

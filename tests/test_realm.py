@@ -7,6 +7,15 @@ and max |d| <= 2.5, image mean within 0.15, neighbour-difference std within
 0.15, per-pixel mean |d| <= 3.5.  Measured: block mean 0.105 / max 0.83,
 per-pixel 2.24.  -main's semantics on the same scene and camera must fail
 (block max ~97: Schlick reflectance on the glass).
+
+The kernel's default realm contract (MODE_REALM32 | DIRECT) also has a
+same-draw fp64 reference, MODE_REALM64D (MODE_REALM64 with the two samplers
+loop-free in plain double from the same uniforms).  On the reference scene and
+camera (400x225, 100 spp, depth 50: defocus, so both samplers draw) it is held
+to oracle/pin.py's same-draw BOUNDS: measured linear mean |d| 2.3e-6 (<= 5e-4),
+8-bit per-pixel 7e-4 (<= 0.25), off by > 1 0.009 % (<= 2 %), block means
+5e-4 / 0.029, segments/sample 2.7e-6; with the fp64 sphere draw's z scaled by
+0.99 the linear mean is 7.2e-4: fails.
 """
 import json
 from pathlib import Path
@@ -52,7 +61,7 @@ def _render(mode, spp=100, seed=1, w=400, h=None, depth=50, bodies=None):
     cam = realm.camera(w, h)
     out, out64, segs, smp = oracle.render(mode, sc.sphere.astype(np.float64), sc.kind, sc.mat.astype(np.float64),
                                           cam.as_list(), cam.defocus, w, h, spp, depth, seed=seed,
-                                          want64=mode in (oracle.MODE_REF64, oracle.MODE_REALM64))
+                                          want64=mode in oracle.MODES64)
     return (out64 if out64 is not None else out), segs, smp
 
 
@@ -72,6 +81,43 @@ def test_realm_modes_reproduce_scene_realm_ppm(mode):
     assert smp == 400 * 224 * 100
     checks = _checks(_quantize(lin))
     assert all(checks.values()), checks
+
+
+def test_realm64d_reproduces_scene_realm_ppm():
+    """The loop-free fp64 mode draws the same distributions: realm's own frame
+    (no defocus: the unit-sphere draw only) passes the fixture as REALM64 does."""
+    lin, segs, smp = _render(oracle.MODE_REALM64D)
+    assert lin.dtype == np.float64 and smp == 400 * 224 * 100
+    checks = _checks(_quantize(lin))
+    assert all(checks.values()), checks
+
+
+def test_direct_realm_mirror_tracks_realm64d():
+    from oracle.pin import compare, within
+    from rtclj import raytracing as R
+    sph, kind, mat = R.flatten64(R.hittables)
+    cam = oracle.camera(400, 225, **R.REFERENCE_CAMERA)
+
+    def render(mode, zscale=1.0):
+        oracle.sampler_bias(zscale)   # test-only negative control; 1 = unbiased
+        try:
+            out, _, segs, smp = oracle.render(mode, sph, kind, mat, cam, 1, 400, 225, 100, 50, seed=1)
+        finally:
+            oracle.sampler_bias(1.0)
+        return out, segs / smp
+
+    a32, s32 = render(oracle.MODE_REALM32 | oracle.DIRECT)
+    a64, s64 = render(oracle.MODE_REALM64D)
+    st = compare(a64, s64, a32, s32, by=9)
+    print("reference scene REALM32|DIRECT vs REALM64D:", st)
+    ok = within(st)
+    assert all(ok.values()), (ok, st)
+    b64, sb = render(oracle.MODE_REALM64D, zscale=0.99)
+    assert oracle.sampler_bias() == 1.0
+    st = compare(b64, sb, a32, s32, by=9)
+    print("the same, z * 0.99:", st)
+    ok = within(st)
+    assert not all(ok.values()) and not ok["lin_mean"], (ok, st)
 
 
 def test_main_semantics_fail_the_realm_fixture():
