@@ -243,17 +243,19 @@ int bvh_build(const float* sph, int n, BvhHost* out, int leaf_size, bool sah) {
   // farthest surface): D = |O - centre| + radius bounds |oc| + r per ray
   Box all;
   for (int i : b.prim) all.add(body_box(sph + 4 * i));
-  double bc[3] = {0, 0, 0}, br = 0;
+  double bc[3] = {0, 0, 0}, br = 0, rmax = 0;
   if (!b.prim.empty()) {
     for (int k = 0; k < 3; ++k) bc[k] = 0.5 * (double(all.lo[k]) + all.hi[k]);
     for (int i : b.prim) {
       const float* s = sph + 4 * i;
       const double dx = s[0] - bc[0], dy = s[1] - bc[1], dz = s[2] - bc[2];
       br = std::max(br, std::sqrt(dx * dx + dy * dy + dz * dz) + std::fabs(s[3]));
+      rmax = std::max(rmax, double(std::fabs(s[3])));
     }
   }
   for (int k = 0; k < 3; ++k) out->center[k] = static_cast<float>(bc[k]);
   out->radius = static_cast<float>(br * (1.0 + 1e-6)) + 1e-6f;
+  out->r_max = static_cast<float>(rmax * (1.0 + 1e-6));
   // root is always node 0 with two children (a leaf-only tree gets a root)
   out->nodes.emplace_back();
   const int cnt = static_cast<int>(b.prim.size());

@@ -24,6 +24,7 @@ struct BvhHost {
   int n_big_leaves = 0;
   float center[3] = {0, 0, 0};
   float radius = 0.0f;        // bounding sphere of the tree's bodies
+  float r_max = 0.0f;         // largest |radius| among the tree's bodies (the big ones excluded; bvh_pad.h)
   int depth = 0;              // levels of nodes on the longest root-leaf path
   int leaf_size = 2;          // bodies per leaf (2, 4 or 8: 1, 2 or 4 pairs)
 };

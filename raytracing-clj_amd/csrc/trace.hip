@@ -315,6 +315,7 @@ struct DTree {
   float4* blob;
   int blob_f4, off_pairs, off_pidx, big_pair0, n_big_leaves, depth, n_nodes;
   float c[3], r;
+  float c0;   // kPadRmax x the tree bodies' largest radius (bvh_pad.h)
 };
 
 // Adaptive tile schedule (rt_launch): per stream, the per-tile durations of
@@ -589,6 +590,7 @@ extern "C" int rt_scene_upload(int device, const rt_scene* s, rt_dscene** out) {
     t.n_nodes = static_cast<int>(bvh.nodes.size());
     for (int j = 0; j < 3; ++j) t.c[j] = bvh.center[j];
     t.r = bvh.radius;
+    t.c0 = kPadRmax * bvh.r_max;
     e = hipMalloc(&t.blob, blob.size());
     if (e == hipSuccess) e = hipMemcpy(t.blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
   }
@@ -954,6 +956,7 @@ extern "C" int rt_launch(const rt_dscene* ds, const rt_camera* c, const rt_param
   a.bvh_stack = compact_variant(vsel) ? stack_entries_compact(tr) : stack_entries(tr, variant_tree(vsel));
   for (int k = 0; k < 3; ++k) a.bvh_c[k] = tr.c[k];
   a.bvh_r = tr.r;
+  a.bvh_c0 = tr.c0;
   // drain compaction: a post holds as many paths as a wave's stack slice has
   // room for (RTCLJ_COMPACT: post at or below that many paths; 0 off)
   {

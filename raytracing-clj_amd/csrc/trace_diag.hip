@@ -333,19 +333,13 @@ __global__ __launch_bounds__(kSortThreads, 6) void sorted_kernel(const KArgs a) 
         best = acc ? s : best;
       };
       const float ecx = ox - a.bvh_c[0], ecy = oy - a.bvh_c[1], ecz = oz - a.bvh_c[2];
-      const float D = __builtin_amdgcn_sqrtf(fmaf(ecz, ecz, fmaf(ecy, ecy, ecx * ecx))) + a.bvh_r;
-      const float P = fmaf(2e-3f, D, 1e-6f);
-      const float rux = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(ux), -1e24f, 1e24f);
-      const float ruy = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(uy), -1e24f, 1e24f);
-      const float ruz = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(uz), -1e24f, 1e24f);
-      f2 r_xy = {rux, ruy}, r_z = {ruz, ruz};
-      const float nlx = -(ecx + P) * rux, nly = -(ecy + P) * ruy, nlz = -(ecz + P) * ruz;
-      const float nhx = -(ecx - P) * rux, nhy = -(ecy - P) * ruy, nhz = -(ecz - P) * ruz;
-      const bool sx = rux < 0.0f, sy = ruy < 0.0f, sz = ruz < 0.0f;
-      f2 nf_x = {sx ? nhx : nlx, sx ? nlx : nhx};
-      f2 nf_y = {sy ? nhy : nly, sy ? nly : nhy};
-      f2 nf_z = {sz ? nhz : nlz, sz ? nlz : nhz};
-      const int offx = sx ? 8 : 0, offy = 24 + (sy ? 8 : 0), offz = 48 + (sz ? 8 : 0);
+      // the padding of trace_kernel.h's walk (bvh_pad.h), in step with it
+      const PadRay pr = pad_ray(ecx, ecy, ecz, ux, uy, uz, a.bvh_r, a.bvh_c0);
+      const PadAxis pax = pad_axis(ux, ecx, tmin, pr), pay = pad_axis(uy, ecy, tmin, pr), paz = pad_axis(uz, ecz, tmin, pr);
+      f2 r_x = {pax.mn, pax.mf}, r_y = {pay.mn, pay.mf}, r_z = {paz.mn, paz.mf};
+      f2 nf_x = {pax.on, pax.of}, nf_y = {pay.on, pay.of}, nf_z = {paz.on, paz.of};
+      const int offx = static_cast<int>(pax.sign >> 28), offy = 24 + static_cast<int>(pay.sign >> 28),
+                offz = 48 + static_cast<int>(paz.sign >> 28);
       f2 o_xy = {ox, oy}, o_zux = {oz, ux}, u_yz = {uy, uz};
       auto leaf = [&](int p) {
         float hh[4], dd[4];
@@ -395,10 +389,10 @@ __global__ __launch_bounds__(kSortThreads, 6) void sorted_kernel(const KArgs a) 
         const f2* ay = reinterpret_cast<const f2*>(nb + offy);
         const f2* az = reinterpret_cast<const f2*>(nb + offz);
         const int2 ch = *reinterpret_cast<const int2*>(nb + 72);
-        asm volatile("" : "+v"(r_xy), "+v"(r_z), "+v"(nf_x), "+v"(nf_y), "+v"(nf_z));
-        const f2 tnx = fma2(ax[0], bc_lo(r_xy), bc_lo(nf_x)), tfx = fma2(ax[1], bc_lo(r_xy), bc_hi(nf_x));
-        const f2 tny = fma2(ay[0], bc_hi(r_xy), bc_lo(nf_y)), tfy = fma2(ay[1], bc_hi(r_xy), bc_hi(nf_y));
-        const f2 tnz = fma2(az[0], bc_lo(r_z), bc_lo(nf_z)), tfz = fma2(az[1], bc_lo(r_z), bc_hi(nf_z));
+        asm volatile("" : "+v"(r_x), "+v"(r_y), "+v"(r_z), "+v"(nf_x), "+v"(nf_y), "+v"(nf_z));
+        const f2 tnx = fma2(ax[0], bc_lo(r_x), bc_lo(nf_x)), tfx = fma2(ax[1], bc_hi(r_x), bc_hi(nf_x));
+        const f2 tny = fma2(ay[0], bc_lo(r_y), bc_lo(nf_y)), tfy = fma2(ay[1], bc_hi(r_y), bc_hi(nf_y));
+        const f2 tnz = fma2(az[0], bc_lo(r_z), bc_lo(nf_z)), tfz = fma2(az[1], bc_hi(r_z), bc_hi(nf_z));
         tn0 = fmaxf(fmaxf(tnx.x, tny.x), tnz.x);
         tn1 = fmaxf(fmaxf(tnx.y, tny.y), tnz.y);
         const float tf0 = fminf(fminf(tfx.x, tfy.x), tfz.x);

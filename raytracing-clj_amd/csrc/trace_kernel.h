@@ -57,6 +57,7 @@
 #include <vector>
 
 #include "bvh.h"
+#include "bvh_pad.h"
 #include "fp_rn.h"
 #include "rt_internal.h"
 
@@ -88,6 +89,7 @@ struct alignas(16) KArgs {
   int n_big_leaves;
   int bvh_stack;         // stack entries per lane (stack_entries: tree depth, or + 2 for tree 0)
   float bvh_c[3], bvh_r; // bounding sphere of the tree's bodies
+  float bvh_c0;          // kPadRmax x the largest radius of the tree's bodies (bvh_pad.h)
   const int* tile_order;   // nullable: tile order (longest first) -> tile
   unsigned* tile_cost;     // nullable: per tile, its workgroups' durations added (s_memrealtime ticks) to half the history
   // Work units: the first n_whole tiles of the order are one
@@ -1116,9 +1118,12 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
       // Closest hit through the BVH (bvh.cpp), bit-identical to the scan:
       //  * each body is tested by the scan's fp32 op sequence and accepted if
       //    t is smaller, or equal with a lower index (= the scan's first-wins);
-      //  * boxes are padded per ray by P = 2e-3 * D, D = |O - c| + R bounding
-      //    |oc| + r of every tree body: the fp32 test never reports a point
-      //    farther than 6e-4 * (|oc| + r) outside a body's box (measured,
+      //  * boxes are padded per ray and axis by 2e-3 * (t + c0) at distance t
+      //    (c0 = 3 r_max of the tree's bodies plus a rounding term), or by
+      //    P = 2e-3 * D, D = |O - c| + R bounding |oc| + r of every tree body,
+      //    where the ray cannot take that form (bvh_pad.h): the
+      //    fp32 test never reports a point farther than 6e-4 * (|oc| + r), or
+      //    6e-4 * (t + 3 r), outside a body's box (measured,
       //    tools/pad_bound.cpp, 3x margin), so a body the scan would accept
       //    always lies in every box on its path; a box is skipped only if its
       //    padded interval misses (tmin, best_t].
@@ -1150,34 +1155,25 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
       const PidxT* pidx = reinterpret_cast<const PidxT*>(base + a.bvh_off_pidx);
       // box tests only cull (conservatively): hardware sqrt / rcp (1 ulp) are
       // far inside the padding.  Node boxes are stored relative to the tree
-      // centre c (bvh.cpp), so every slab bound is one fma:
-      // (b - (o' + P)) / u = b * (1/u) - (o' + P) / u with o' = o - c; its
-      // rounding (~1e-7 * D) is far inside the padding too.
+      // centre c (bvh.cpp), so every slab bound is one fma, b * m + o with a
+      // multiplier and an offset per ray, axis and plane (near, far).  The
+      // padding, its two forms (per hit distance where the ray allows it,
+      // ray-wide elsewhere) and their bounds: bvh_pad.h, shared with the CPU
+      // property test.
+      // (every BVH variant takes the per-distance form: each keeps its VGPR
+      // count and stays free of scratch with the two more live registers)
+      constexpr bool kPadPerT = true;
       const float ecx = ox - a.bvh_c[0], ecy = oy - a.bvh_c[1], ecz = oz - a.bvh_c[2];
-      const float D = __builtin_amdgcn_sqrtf(fmaf(ecz, ecz, fmaf(ecy, ecy, ecx * ecx))) + a.bvh_r;
-      const float P = fmaf(2e-3f, D, 1e-6f);
-      if constexpr (STATS) st_fl += 27;   // o - c, D, P, 3 rcp, 6 slab offsets
-      // 1/u clamped to +-1e24 (one v_med3): with u = 0 an infinite 1/u makes
-      // the fma bounds NaN and -inf, which would collapse the slab (a false
-      // miss); finite, the slab of an origin inside the padded box spans
-      // ~+-1e24 and one outside it lies ~1e24 away (culled) -- the u = 0
-      // answers.  (u = -0 gives -inf -> -1e24: the sign still orders the planes.)
-      const float rux = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(ux), -1e24f, 1e24f);
-      const float ruy = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(uy), -1e24f, 1e24f);
-      const float ruz = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(uz), -1e24f, 1e24f);
-      // broadcast operands as halves of packed pairs (bc_lo / bc_hi: one
-      // register read through op_sel for both halves, not a duplicated pair)
-      f2 r_xy = {rux, ruy}, r_z = {ruz, ruz};
-      // the min plane's bound b*(1/u) - (o' + P)/u, the max plane's
-      // b*(1/u) - (o' - P)/u; by the sign of 1/u one is the near plane
-      const float nlx = -(ecx + P) * rux, nly = -(ecy + P) * ruy, nlz = -(ecz + P) * ruz;
-      const float nhx = -(ecx - P) * rux, nhy = -(ecy - P) * ruy, nhz = -(ecz - P) * ruz;
-      const bool sx = rux < 0.0f, sy = ruy < 0.0f, sz = ruz < 0.0f;
-      f2 nf_x = {sx ? nhx : nlx, sx ? nlx : nhx};   // (near, far) plane offsets
-      f2 nf_y = {sy ? nhy : nly, sy ? nly : nhy};
-      f2 nf_z = {sz ? nhz : nlz, sz ? nlz : nhz};
-      // byte offsets of the (near, far) pairs of each axis inside a node
-      const int offx = sx ? 8 : 0, offy = 24 + (sy ? 8 : 0), offz = 48 + (sz ? 8 : 0);
+      const PadRay pr = pad_ray(ecx, ecy, ecz, ux, uy, uz, a.bvh_r, a.bvh_c0, kPadPerT);
+      if constexpr (STATS) st_fl += 36;   // o - c, D, P, pc, 6 u +- k, 6 rcp, 6 slab offsets
+      const PadAxis pax = pad_axis(ux, ecx, tmin, pr), pay = pad_axis(uy, ecy, tmin, pr), paz = pad_axis(uz, ecz, tmin, pr);
+      // (near, far) multipliers and plane offsets per axis as packed pairs
+      f2 r_x = {pax.mn, pax.mf}, r_y = {pay.mn, pay.mf}, r_z = {paz.mn, paz.mf};
+      f2 nf_x = {pax.on, pax.of}, nf_y = {pay.on, pay.of}, nf_z = {paz.on, paz.of};
+      // byte offsets of the (near, far) pairs of each axis inside a node: + 8
+      // for u < 0 (the sign bit shifted down: no compare, no select)
+      const int offx = static_cast<int>(pax.sign >> 28), offy = 24 + static_cast<int>(pay.sign >> 28),
+                offz = 48 + static_cast<int>(paz.sign >> 28);
       // the ray's (near, far) plane pairs of node 0; opaque, so that a node's
       // three axis addresses are one add each from them (not the blob's base
       // added to the node first)
@@ -1355,22 +1351,12 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
           x0 = ax[0], x1 = ax[1], y0 = ay[0], y1 = ay[1], z0 = az[0], z1 = az[1];
           ch = *reinterpret_cast<const int2*>(nb + 72);
         }
-        asm volatile("" : "+v"(r_xy), "+v"(r_z), "+v"(nf_x), "+v"(nf_y), "+v"(nf_z));
+        asm volatile("" : "+v"(r_x), "+v"(r_y), "+v"(r_z), "+v"(nf_x), "+v"(nf_y), "+v"(nf_z));
         // (per child scalar v_fma_f32: dual-issued, unlike v_pk_fma_f32)
-        f2 tnx, tfx, tny, tfy, tnz, tfz;
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          tnx[e] = fma3(x0[e], r_xy.x, nf_x.x);
-          tfx[e] = fma3(x1[e], r_xy.x, nf_x.y);
-          tny[e] = fma3(y0[e], r_xy.y, nf_y.x);
-          tfy[e] = fma3(y1[e], r_xy.y, nf_y.y);
-          tnz[e] = fma3(z0[e], r_z.x, nf_z.x);
-          tfz[e] = fma3(z1[e], r_z.x, nf_z.y);
-        }
-        tn0 = fmaxf(fmaxf(tnx.x, tny.x), tnz.x);
-        tn1 = fmaxf(fmaxf(tnx.y, tny.y), tnz.y);
-        tf0 = fminf(fminf(tfx.x, tfy.x), tfz.x);
-        tf1 = fminf(fminf(tfx.y, tfy.y), tfz.y);
+        const PadAxis px = {r_x.x, r_x.y, nf_x.x, nf_x.y, 0}, py = {r_y.x, r_y.y, nf_y.x, nf_y.y, 0},
+                      pz = {r_z.x, r_z.y, nf_z.x, nf_z.y, 0};
+        pad_interval(px, py, pz, x0.x, x1.x, y0.x, y1.x, z0.x, z1.x, tn0, tf0);
+        pad_interval(px, py, pz, x0.y, x1.y, y0.y, y1.y, z0.y, z1.y, tn1, tf1);
         c0 = ch.x;
         c1 = ch.y;
       };
@@ -1379,15 +1365,9 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
         node_planes(node, tn0, tn1, tf0, tf1, c0, c1);
         // "[tn, tf] meets (tmin, best_t]" as max(tn, tmin) <= min(tf, best_t),
         // spelled tn <= min(tf, best_t) and tmin <= tf (tmin < best_t always):
-        // a compare instead of a max per child.  Each is "not greater", so a
-        // NaN bound passes (conservative).
-        // (min(tf, best_t) as a bare v_min_f32: fminf would re-canonicalise
-        // best_t every step; a NaN tf gives best_t, conservative)
-        float tb0, tb1;
-        asm("v_min_f32 %0, %1, %2" : "=v"(tb0) : "v"(tf0), "v"(best_t));
-        asm("v_min_f32 %0, %1, %2" : "=v"(tb1) : "v"(tf1), "v"(best_t));
-        hit0 = !(tn0 > tb0) & !(tmin > tf0);
-        hit1 = !(tn1 > tb1) & !(tmin > tf1);
+        // a compare instead of a max per child (pad_meets, bvh_pad.h)
+        hit0 = pad_meets(tn0, tf0, tmin, best_t);
+        hit1 = pad_meets(tn1, tf1, tmin, best_t);
       };
       // the big bodies' leaves first: every lane, so a wave-uniform loop (their
       // hits, e.g. the ground, then cull the tree)
@@ -1403,8 +1383,12 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
       int node = SRC == SRC_LDS && SCAN == SCAN_BVHQ ? static_cast<int>(lds_addr(nodes)) : 0;   // (BVHQ7: index 0)
       // the stack top as a pointer into the [entry][lane] stack: one add per
       // push / pop instead of index arithmetic
-      StackT* const stk0 = s_stack + threadIdx.x;
-      StackT* top = stk0;
+      // (the lane's first entry made here, per segment, from a thread index
+      // the compiler cannot see through: hoisted out of the kernel's loop it
+      // would hold a register through the whole walk, which has none to spare)
+      unsigned tix = threadIdx.x;
+      asm volatile("" : "+v"(tix));
+      StackT* top = s_stack + tix;
       // a row of the stack in bytes, held in a register the compiler cannot
       // rematerialise (a literal would be moved into a VGPR on every push)
       int row_b = NT * static_cast<int>(sizeof(StackT));
@@ -1443,8 +1427,12 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
           // pop, unconditionally: with an empty stack the top moves one row
           // below the first entry, into the blob's last bytes (a harmless
           // read), and the lane leaves -- one add and one compare, no select
+          // (compared with the stack's base, the same for every lane: a lane's
+          // first entry lies less than a row above it, so one row below that
+          // is below the base -- and no per-lane bound is held in a register
+          // through the walk)
           top -= NT;
-          go = top >= stk0;
+          go = top >= s_stack;
           nxt = *top;
         }
         node = nxt;

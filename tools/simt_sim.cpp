@@ -35,11 +35,13 @@
 
 #include "../include/rt.h"
 #include "../raytracing-clj_amd/csrc/bvh.h"
+#include "../raytracing-clj_amd/csrc/bvh_pad.h"
 
 using namespace rtclj;
 namespace rtclj { extern float g_bvh_big_ratio; }
 static double g_cand = 0, g_rej = 0, g_segs = 0, g_visits = 0, g_leafs = 0;
 static float g_pad = 1.0f;
+static int g_padt = 0;   // PADT=1: the padding of bvh_pad.h (per hit distance)
 static int g_big_leaves = 0;
 static int g_tile_h = 8;      // workgroup pool: 8 x g_tile_h pixels (TILEH)
 static int g_nw = 4;          // waves per workgroup (NW; 8 with TILEH=16: 512 threads)
@@ -136,6 +138,10 @@ static Hit trace(const Scene& S, float ox, float oy, float oz, float ux, float u
   const float ex = ox - S.t.center[0], ey = oy - S.t.center[1], ez = oz - S.t.center[2];
   const float D = std::sqrt(ex * ex + ey * ey + ez * ez) + S.t.radius;
   const float P = g_pad * 2e-3f * D;
+  // PADT=1: the kernel's padding as it is (bvh_pad.h: per hit distance where
+  // the ray allows it, ray-wide elsewhere) instead of the ray-wide P alone
+  const PadRay pray = pad_ray(ex, ey, ez, ux, uy, uz, S.t.radius, kPadRmax * S.t.r_max);
+  const PadAxis pax[3] = {pad_axis(ux, ex, tmin, pray), pad_axis(uy, ey, tmin, pray), pad_axis(uz, ez, tmin, pray)};
   const float rx = 1.0f / (std::fabs(ux) < 1e-24f ? std::copysign(1e-24f, ux) : ux);
   const float ry = 1.0f / (std::fabs(uy) < 1e-24f ? std::copysign(1e-24f, uy) : uy);
   const float rz = 1.0f / (std::fabs(uz) < 1e-24f ? std::copysign(1e-24f, uz) : uz);
@@ -211,6 +217,16 @@ static Hit trace(const Scene& S, float ox, float oy, float oz, float ux, float u
       tn[c] = std::max({std::min(x0, x1), std::min(y0, y1), std::min(z0, z1)});
       tf[c] = std::min({std::max(x0, x1), std::max(y0, y1), std::max(z0, z1)});
       hit[c] = std::max(tn[c], tmin) <= std::min(tf[c], best.t);
+      if (g_padt) {
+        const float* ax[3] = {nd.x, nd.y, nd.z};
+        float pn[3], pf[3];
+        for (int k = 0; k < 3; ++k) {
+          pn[k] = ax[k][pax[k].sign ? 2 + c : c];
+          pf[k] = ax[k][pax[k].sign ? c : 2 + c];
+        }
+        pad_interval(pax[0], pax[1], pax[2], pn[0], pf[0], pn[1], pf[1], pn[2], pf[2], tn[c], tf[c]);
+        hit[c] = pad_meets(tn[c], tf[c], tmin, best.t);
+      }
     }
     const int c0 = nd.child[0], c1 = nd.child[1];
     const bool l0 = hit[0] && c0 < 0, l1 = hit[1] && c1 < 0;
@@ -674,6 +690,7 @@ int main(int argc, char** argv) {
   rt_scene_cover(11, 42, S.sph.data(), S.kind.data(), S.mat.data(), S.n);
   if (std::getenv("BIG")) g_bvh_big_ratio = std::atof(std::getenv("BIG"));
   if (std::getenv("PAD")) g_pad = std::atof(std::getenv("PAD"));
+  if (std::getenv("PADT")) g_padt = std::atoi(std::getenv("PADT"));
   if (std::getenv("EXACT")) g_exact_mode = std::atoi(std::getenv("EXACT"));
 
   const int ls = std::getenv("LS") ? std::atoi(std::getenv("LS")) : 4;
