@@ -64,13 +64,43 @@ enum { RT_LAMBERTIAN = 0, RT_METAL = 1, RT_DIELECTRIC = 2, RT_NONE = 3 };
 
 /* Maximum samples per pixel of one call (the pixel's fixed-point colour sums,
  * 2^-24 units per sample, stay below 2^64; larger counts: several calls with
- * sample_begin). */
+ * sample_begin).  A sample's colour channel enters that sum clamped to
+ * [0, 256): a negative or NaN channel counts as 0 (the Clojure code would sum
+ * it), one of 256 or more as 256 - 2^-24. */
 #define RT_MAX_SPP (1 << 24)
 
 /* ---- scene: the reference's `hittables` vector (raytracing.clj:63-78) -----
  * Bodies are tested in array order; on equal t the earlier body wins, exactly
  * as hit-anything's strict `root < closest-so-far` (raytracing.clj:35-42,
- * hittable.clj:17-23). */
+ * hittable.clj:17-23); identical spheres are such ties, in every kernel
+ * variant.
+ *
+ * What the arrays may hold beyond the reference's own scenes
+ * (tests/test_gpu_input_edges.py pins each against the fp32 mirror, and
+ * against the fp64 reference semantics where the two mean the same):
+ *  - Albedos above 1 are accepted; a scene with one runs the kernel with
+ *    64-bit pixel sums (rt_set_variant: 16 instead of 22).  Albedos below 0
+ *    and sample colours of 256 or more meet the clamp described at
+ *    RT_MAX_SPP.
+ *  - Fuzz and refraction index are used as given, whatever their value
+ *    (fuzz above 1 or below 0; an index of 1, below 1, negative, 0 or
+ *    infinite): 1 / index and Schlick's r0 may then be infinite or NaN.  For
+ *    the values named the frames stay the fp64 path's; under RT_FLAG_REALM
+ *    an infinite index gives the same colours in more segments (a NaN
+ *    product reflects here and refracts there).
+ *  - A negative radius gives the inward normal, as hittable.clj:25's division
+ *    by the radius does (a bubble inside glass as r < 0).
+ *  - A body with a NaN or infinite coordinate or radius, or with a radius of
+ *    2^64 or more (r * r overflows), is never hit; r = 0 neither, in
+ *    practice.  This differs from the Clojure comparisons, which let a NaN
+ *    root through.
+ *  - Coordinates: scene and camera may be scaled together from 2^-62 to 2^20
+ *    of unit scale with the fp64 meaning kept (the denormal range of r * r
+ *    included; below 2^-40 a bounced ray's t > 1e-3, which is absolute in
+ *    the reference too, ends every path at its second segment).  From 2^40
+ *    the fp32 range and that absolute 1e-3 give out: the frame stays finite
+ *    and equal across kernel variants, but no longer means what the fp64
+ *    path computes. */
 typedef struct rt_scene {
   int n;                  /* number of bodies                                  */
   const float* sphere;    /* n x 4: center x,y,z, radius  (hittable.clj:7)     */

@@ -33,7 +33,6 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <numeric>
 
 namespace rtclj {
 
@@ -199,38 +198,51 @@ int bvh_build(const float* sph, int n, BvhHost* out, int leaf_size, bool sah) {
   *out = BvhHost{};
   if (leaf_size != 2 && leaf_size != 4 && leaf_size != 8) leaf_size = 2;
   out->leaf_size = leaf_size;
+  // Bodies the body test can never accept stay out of the tree and out of the
+  // big-body list, however many there are (the scan variants still read them
+  // from the body table):
+  //  * a non-finite coordinate or radius (rt.h, rt_scene): a NaN or infinite
+  //    centre makes disc NaN, an infinite radius puts the roots at -+inf, a
+  //    NaN radius makes them NaN -- and such a body has no box: one in the
+  //    tree would make its boxes, centre and radius non-finite;
+  //  * a finite radius whose r * r overflows (|r| >= 2^64): -r^2 = -inf, the
+  //    roots are -+inf again.  The scan's `t < best_t` rejects t = +inf; the
+  //    walk's (t, index) compare (trace_kernel.h consider_tie) would take it
+  //    for a tie with "no hit yet" (+inf, -1) and accept it.
+  std::vector<char> finite(n, 0);
+  int n_finite = 0;
+  for (int i = 0; i < n; ++i) {
+    const float r = sph[4 * i + 3];
+    finite[i] = std::isfinite(sph[4 * i]) && std::isfinite(sph[4 * i + 1]) && std::isfinite(sph[4 * i + 2]) &&
+                std::isfinite(r * r);
+    n_finite += finite[i];
+  }
   // big bodies: scanned first, outside the tree
   std::vector<float> radii;
   for (int i = 0; i < n; ++i) radii.push_back(std::fabs(sph[4 * i + 3]));
   float med = 0.0f;
-  if (n > 0) {
-    std::vector<float> tmp = radii;
-    std::nth_element(tmp.begin(), tmp.begin() + n / 2, tmp.end());
-    med = tmp[n / 2];
+  if (n_finite > 0) {
+    std::vector<float> tmp;
+    for (int i = 0; i < n; ++i)
+      if (finite[i]) tmp.push_back(radii[i]);
+    std::nth_element(tmp.begin(), tmp.begin() + n_finite / 2, tmp.end());
+    med = tmp[n_finite / 2];
   }
   Builder b{sph, {}, out};
   b.leaf_size = leaf_size;
   b.sah = sah;
-  // non-finite bodies (no box) and the kBvhBigMax largest bodies of radius >
-  // g_bvh_big_ratio x the median (the r = 1000 ground, the cover scene's three
-  // r = 1 spheres: their boxes would enclose many small bodies' boxes)
+  // the kBvhBigMax largest bodies of radius > g_bvh_big_ratio x the median
+  // (the r = 1000 ground, the cover scene's three r = 1 spheres: their boxes
+  // would enclose many small bodies' boxes)
   std::vector<char> is_big(n, 0);
-  for (int i = 0; i < n; ++i) {
-    const bool finite = std::isfinite(sph[4 * i]) && std::isfinite(sph[4 * i + 1]) &&
-                        std::isfinite(sph[4 * i + 2]) && std::isfinite(sph[4 * i + 3]);
-    if (!finite && out->big.size() < 64) {
-      is_big[i] = 1;
-      out->big.push_back(i);
-    }
-  }
-  if (n > 8) {
-    std::vector<int> order(n);
-    std::iota(order.begin(), order.end(), 0);
+  if (n_finite > 8) {
+    std::vector<int> order;
+    for (int i = 0; i < n; ++i)
+      if (finite[i]) order.push_back(i);
     std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return radii[x] > radii[y]; });
     int added = 0;
     for (int i : order) {
       if (added == kBvhBigMax || !(radii[i] > g_bvh_big_ratio * med)) break;
-      if (is_big[i]) continue;
       is_big[i] = 1;
       out->big.push_back(i);
       ++added;
@@ -238,7 +250,7 @@ int bvh_build(const float* sph, int n, BvhHost* out, int leaf_size, bool sah) {
   }
   std::sort(out->big.begin(), out->big.end());
   for (int i = 0; i < n; ++i)
-    if (!is_big[i]) b.prim.push_back(i);
+    if (finite[i] && !is_big[i]) b.prim.push_back(i);
   // bounding sphere of the tree's bodies (centre of their box, radius to the
   // farthest surface): D = |O - centre| + radius bounds |oc| + r per ray
   Box all;

@@ -33,7 +33,8 @@ struct BvhHost {
 // depth + 2 <= kBvhStack (surface-area splits where the depth allows, median
 // splits below: depth <= ceil(log2(n/2)) + 1 = 13 for 8192 bodies)
 constexpr int kBvhStack = 16;
-// bodies kept out of the tree for their size (besides non-finite ones)
+// bodies kept out of the tree for their size (bodies that can never be hit --
+// non-finite ones, r * r = inf -- enter neither the tree nor this list: bvh.cpp)
 constexpr int kBvhBigMax = 8;
 
 // sah: surface-area-heuristic splits (else median splits)

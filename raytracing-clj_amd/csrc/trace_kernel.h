@@ -1137,6 +1137,9 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
         // (t, index) < (best_t, best) lexicographically as one 64-bit compare:
         // t > tmin > 0, so its bits order like the floats; best = -1 is the
         // largest u32 (and best_t = +inf the largest t) before any hit
+        // (a root of +inf would tie with that "no hit yet" and win on its
+        // index, where the scan's t < best_t rejects it: only a body with
+        // r * r = inf has one, and bvh.cpp keeps those out of every leaf)
         const uint64_t key = (static_cast<uint64_t>(__float_as_uint(t)) << 32) | static_cast<uint32_t>(s);
         const uint64_t bkey = (static_cast<uint64_t>(__float_as_uint(best_t)) << 32) | static_cast<uint32_t>(best);
         const bool acc = (t > tmin) & (key < bkey);
