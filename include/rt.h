@@ -63,8 +63,9 @@ enum { RT_LAMBERTIAN = 0, RT_METAL = 1, RT_DIELECTRIC = 2, RT_NONE = 3 };
 #define RT_MAX_SPHERES 8192
 
 /* Maximum samples per pixel of one call (the pixel's fixed-point colour sums,
- * 2^-24 units per sample, stay below 2^64; larger counts: several calls with
- * sample_begin).  A sample's colour channel enters that sum clamped to
+ * 2^-24 units per sample, stay below 2^64; larger counts: several passes with
+ * sample_begin into an rt_accum, below, which adds them up exactly, to
+ * 2^32 - 1 samples per pixel).  A sample's colour channel enters that sum clamped to
  * [0, 256): a negative or NaN channel counts as 0 (the Clojure code would sum
  * it), one of 256 or more as 256 - 2^-24. */
 #define RT_MAX_SPP (1 << 24)
@@ -322,6 +323,74 @@ int rt_scene_free(rt_dscene* ds);
  * stream (splits x rows x width x 3 x 8 bytes).  Bits never depend on it. */
 int rt_launch(const rt_dscene* ds, const rt_camera* c, const rt_params* p,
               float* d_out, uint64_t* d_counters, void* hip_stream);
+
+/* ---- progressive rendering: samples accumulated on the device -------------
+ * compute-pixel's loop over the samples of a pixel (raytracing.clj:141-155)
+ * continued across launches.  A pixel is an integer sum of its samples'
+ * colours in 2^-24 units, whatever the order; an rt_accum keeps those sums
+ * (rt_rows_out(shape) x width x 3 u64, on the scene's device, zeroed by the
+ * library) and the samples per pixel they hold, so that k passes of a frame
+ * are, bit for bit, the frame one rt_launch of the total spp gives -- for
+ * any pass sizes, launch shapes, order, streams or devices.
+ *
+ * rt_accum_create (raytracing.clj:141-155): an empty accumulator for frames
+ * of `shape`'s width, height and row selection (row_begin, row_end, row_tile,
+ * tile_first, tile_step; the other fields are not read) on ds's device.  It
+ * holds no reference to ds.  RT_E_ARG on an empty or bad selection. */
+typedef struct rt_accum rt_accum;
+int rt_accum_create(const rt_dscene* ds, const rt_params* shape, rt_accum** out);
+int rt_accum_free(rt_accum* acc);
+/* raytracing.clj:141-155, the loop's start: enqueue sums = 0 on hip_stream;
+ * the count is 0 from the call on. */
+int rt_accum_clear(rt_accum* acc, void* hip_stream);
+/* raytracing.clj:141-155, the loop's counter: samples per pixel of the passes
+ * enqueued (and sums added) so far. */
+int64_t rt_accum_samples(const rt_accum* acc);
+/* One pass of the loop (raytracing.clj:141-155).  Asynchronous: trace p->spp
+ * samples per pixel with the indices p->sample_begin ..., exactly as
+ * rt_launch would (seed, camera, flags, depth and sample_begin are the
+ * caller's: passes of one frame use consecutive sample ranges), and add their
+ * integer sums to acc instead of writing a mean; the count grows by p->spp
+ * at the call.  The adds are atomic: passes on several streams into one
+ * accumulator are legal and give the same sums.  The adaptive tile order,
+ * the sample split, RT_FLAG_STREAMED, interleaved shards, RT_FLAG_REALM and
+ * RT_FLAG_REJECTION_SAMPLERS apply as to rt_launch; so does the per-launch
+ * choice of the compact image (rt_set_variant: 22 / 26 where spp < 65536),
+ * which looks at the pass's spp, not at the accumulated count -- a long
+ * render in passes below 65536 spp stays on 22 / 26 (intended).  d_counters
+ * as rt_launch.  RT_E_ARG when p's width, height or row selection differ from
+ * the accumulator's, when ds is on another device, or when the count would
+ * pass 2^32 - 1 (the sample index is a uint32, and one sample adds less than
+ * 2^32 to a sum: the u64 cannot overflow before that); acc is unchanged then. */
+int rt_launch_accum(const rt_dscene* ds, const rt_camera* c, const rt_params* p, rt_accum* acc,
+                    uint64_t* d_counters, void* hip_stream);
+/* compute-pixel's accum / spp (raytracing.clj:141-155, :155).  Asynchronous:
+ * d_out (device, rt_rows_out x width x 3 floats) = per channel
+ * tot = RN(float(sum)) * 2^-24, then tot / RN(float(n)), or
+ * tot * (1 / RN(float(n))) with RT_FLAG_REALM in flags (the only flag read;
+ * rt_launch's other flags are accepted), n = max(count, 1) at the call.
+ * This is rt_launch's own conversion: for n <= RT_MAX_SPP the frame equals
+ * one launch of n spp bit for bit.  The sums are not touched: show the frame
+ * and go on adding passes.  Passes enqueued on other streams must have
+ * finished (or be ordered before hip_stream by the caller). */
+int rt_accum_resolve(const rt_accum* acc, int flags, float* d_out, void* hip_stream);
+/* The same, quantised in the same kernel (raytracing.clj:141-155, :19-26):
+ * d_out (device bytes) holds what rt_quantize gives for rt_accum_resolve's
+ * floats, by rt_quantize_device's threshold table. */
+int rt_accum_resolve_u8(const rt_accum* acc, int flags, uint8_t* d_out, void* hip_stream);
+/* The raw sums (raytracing.clj:141-155's accum, before the division) copied
+ * to host_sums (rt_rows_out x width x 3 u64) behind hip_stream's work; returns
+ * when they are there.  Ranks that rendered sample stripes exchange these
+ * (an int64 all-reduce) and resolve once: exact weak scaling. */
+int rt_accum_read(const rt_accum* acc, uint64_t* host_sums, void* hip_stream);
+/* The inverse (raytracing.clj:141-155): add host_sums (the same layout) and
+ * `samples` per pixel to acc, on hip_stream, atomically as a pass does;
+ * returns when they are added.  RT_E_ARG when the count would pass 2^32 - 1. */
+int rt_accum_add(rt_accum* acc, const uint64_t* host_sums, int64_t samples, void* hip_stream);
+/* rt_accum_resolve's conversion on the host, in plain C++ (no device;
+ * raytracing.clj:141-155, :155): out[i] for n sums holding `samples` per
+ * pixel (0 .. 2^32 - 1), flags as rt_accum_resolve. */
+int rt_resolve_sums(const uint64_t* sums, size_t n, int64_t samples, int flags, float* out);
 
 /* Asynchronous: enqueue rt_quantize on hip_stream's device for n channels
  * already in HBM (d_lin: n floats, d_out: n bytes, device pointers): the same

@@ -173,6 +173,25 @@ extern "C" int rt_quantize(const float* lin, uint8_t* out, size_t n) {
   return RT_OK;
 }
 
+// rt_accum_resolve's conversion on the host (trace.hip's resolve_kernel and
+// finalize_kernel, the kernel's write_mean): RN(float(sum)) * 2^-24, then
+// / RN(float(n)) (realm: * (1 / RN(float(n)))), every step one IEEE fp32
+// operation (the library is built with -ffp-contract=off)
+extern "C" int rt_resolve_sums(const uint64_t* sums, size_t n, int64_t samples, int flags, float* out) {
+  clear_error();
+  if ((!sums || !out) && n) return set_error(RT_E_ARG, "rt_resolve_sums: NULL argument");
+  if (samples < 0 || samples > 0xffffffffll ||
+      (flags & ~(RT_FLAG_REALM | RT_FLAG_STREAMED | RT_FLAG_REJECTION_SAMPLERS)) != 0)
+    return set_error(RT_E_ARG, "rt_resolve_sums: bad samples/flags");
+  const float nf = static_cast<float>(samples > 0 ? samples : 1);
+  const bool realm = (flags & RT_FLAG_REALM) != 0;
+  for (size_t i = 0; i < n; ++i) {
+    const float tot = static_cast<float>(sums[i]) * 0x1p-24f;
+    out[i] = realm ? tot * (1.0f / nf) : tot / nf;
+  }
+  return RT_OK;
+}
+
 extern "C" int rt_write_ppm(const char* path, const uint8_t* rgb, int width, int height) {
   clear_error();
   if (!path || !rgb || width <= 0 || height <= 0) return set_error(RT_E_ARG, "rt_write_ppm: bad argument");

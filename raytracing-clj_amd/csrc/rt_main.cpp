@@ -14,8 +14,11 @@
 //
 //   rt_main [spp] [depth] [--scene reference|cover] [--realm] [--width W]
 //           [--seed S] [--gpus N] [--out PATH] [--png PATH] [--no-png] [--json]
-//           [--host-quantize] [--rejection-samplers]
+//           [--host-quantize] [--rejection-samplers] [--passes K]
 // Defaults follow the reference: spp 100, depth 50, width 400, 16:9.
+// --passes K: the spp in K near-equal accumulating passes on device 0
+// (rt_launch_accum into an rt_accum, the sums read back, rt_resolve_sums and
+// rt_quantize on the host): the same PPM / PNG bytes as without it.
 // --json: one more line, a JSON object of where this one-frame process's time
 // went (the device start-up -- the HIP runtime's first rt_device_count, then
 // rt_prepare's context / code object / queue / pageable staging -- on a thread
@@ -36,7 +39,7 @@
 #include "../../include/rt.h"
 
 int main(int argc, char** argv) {
-  int spp = 100, depth = 50, width = 400, gpus = 0, grid = 11;
+  int spp = 100, depth = 50, width = 400, gpus = 0, grid = 11, passes = 0;
   unsigned long long seed = 1;
   std::string scene = "reference", out, png;
   bool realm = false, json = false, host_quantize = false, no_png = false, rejection = false;
@@ -54,7 +57,7 @@ int main(int argc, char** argv) {
   int gpus_arg = 0;
   // (a missing option value ends the process before the start-up thread
   // exists: no exit while that thread may be inside the HIP runtime)
-  static const char* const kValued[] = {"--scene", "--width", "--seed", "--gpus", "--grid", "--out", "--png"};
+  static const char* const kValued[] = {"--scene", "--width", "--seed", "--gpus", "--grid", "--out", "--png", "--passes"};
   for (int i = 1; i < argc; ++i) {
     const bool valued = std::any_of(std::begin(kValued), std::end(kValued),
                                     [&](const char* f) { return std::strcmp(argv[i], f) == 0; });
@@ -88,6 +91,7 @@ int main(int argc, char** argv) {
     else if (a == "--grid") grid = std::atoi(val());
     else if (a == "--out") out = val();
     else if (a == "--png") png = val();
+    else if (a == "--passes") passes = std::atoi(val());
     else if (a == "--realm") realm = true;
     else if (a == "--rejection-samplers") rejection = true;   // RT_FLAG_REJECTION_SAMPLERS
     else if (a == "--json") json = true;
@@ -153,7 +157,35 @@ int main(int argc, char** argv) {
   std::vector<uint8_t> q(nch);
   rt_stats st{};
   double render_ms = 0.0, quantize_ms = 0.0;
-  if (host_quantize) {
+  if (passes > 0) {
+    // compute-pixel's sample loop (raytracing.clj:141-155) in K launches
+    rt_dscene* ds = nullptr;
+    rt_accum* acc = nullptr;
+    std::vector<uint64_t> sums(nch);
+    std::vector<float> lin(nch);
+    const int k = std::max(1, std::min(passes, std::max(spp, 1)));
+    bool ok = rt_scene_upload(0, &s, &ds) == RT_OK && rt_accum_create(ds, &p, &acc) == RT_OK;
+    rt_params pp = p;
+    for (int i = 0; ok && i < k; ++i) {
+      pp.spp = spp / k + (i < spp % k ? 1 : 0);
+      ok = rt_launch_accum(ds, &cam, &pp, acc, nullptr, nullptr) == RT_OK;
+      pp.sample_begin += pp.spp;
+    }
+    ok = ok && rt_accum_read(acc, sums.data(), nullptr) == RT_OK &&
+         rt_resolve_sums(sums.data(), sums.size(), rt_accum_samples(acc), p.flags, lin.data()) == RT_OK;
+    if (!ok) {
+      std::fprintf(stderr, "--passes failed: %s\n", rt_last_error());
+      return 1;
+    }
+    rt_accum_free(acc);
+    rt_scene_free(ds);
+    render_ms = ms_since(t0);
+    const auto t_q = std::chrono::steady_clock::now();
+    rt_quantize(lin.data(), q.data(), q.size());
+    quantize_ms = ms_since(t_q);
+    st.n_devices = 1;
+    st.samples = static_cast<uint64_t>(width) * height * static_cast<uint64_t>(std::max(spp, 0));
+  } else if (host_quantize) {
     std::vector<float> lin(nch);
     if (rt_render(&s, &cam, &p, lin.data(), lin.size(), &st) != RT_OK) {
       std::fprintf(stderr, "rt_render failed: %s\n", rt_last_error());
@@ -186,9 +218,13 @@ int main(int argc, char** argv) {
   const double png_ms = png.empty() ? 0.0 : ms_since(t_p);
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   std::printf("\"Elapsed time: %.3f msecs\"\n", ms);  // (time ...) (:99)
-  std::printf("bodies %d, devices %d, kernel %.3f ms, %.1f Msamples/s, %.3f segments/sample\n", n,
-              st.n_devices, st.kernel_ms, st.samples / (st.kernel_ms * 1e3),
-              st.samples ? double(st.segments) / st.samples : 0.0);
+  if (passes > 0)
+    std::printf("bodies %d, devices 1, %d passes, %.3f ms, %.1f Msamples/s\n", n,
+                std::max(1, std::min(passes, std::max(spp, 1))), render_ms, st.samples / (render_ms * 1e3));
+  else
+    std::printf("bodies %d, devices %d, kernel %.3f ms, %.1f Msamples/s, %.3f segments/sample\n", n,
+                st.n_devices, st.kernel_ms, st.samples / (st.kernel_ms * 1e3),
+                st.samples ? double(st.segments) / st.samples : 0.0);
   if (json)
     std::printf(
         "{\"devices_visible\": %d, \"scene_ms\": %.3f, \"device_count_ms\": %.3f, \"prepare_ms\": {\"context\": %.3f, "
@@ -199,7 +235,7 @@ int main(int argc, char** argv) {
         "\"other_ms\": %.3f, \"kernel_ms\": %.3f, \"d2h_ms\": %.3f, \"segments\": %llu, \"samples\": %llu, "
         "\"n_devices\": %d}}\n",
         ndev, scene_ms, device_count_ms, prep_ms[0], prep_ms[1], prep_ms[2], prep_ms[3], prep_wait_ms, render_ms,
-        host_quantize ? "host" : "device", quantize_ms, write_ms, png_ms, ms_since(t_start), st.total_ms,
+        (host_quantize || passes > 0) ? "host" : "device", quantize_ms, write_ms, png_ms, ms_since(t_start), st.total_ms,
         st.upload_ms, st.setup_ms, st.enqueue_ms, st.wait_ms, st.scatter_ms, st.other_ms, st.kernel_ms, st.d2h_ms,
         static_cast<unsigned long long>(st.segments), static_cast<unsigned long long>(st.samples), st.n_devices);
   return 0;

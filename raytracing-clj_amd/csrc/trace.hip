@@ -1,7 +1,8 @@
 // trace.hip — the product library's gfx950 code object and host side: the
 // shipped kernel's instantiations (trace_kernel.h: the default BVH walk in its
 // two LDS images and its fallbacks), the schedule / split / quantise / fill
-// kernels, and rt_scene_upload / rt_launch.  The A/B scans, the
+// kernels, the accumulator's resolve / add kernels, and rt_scene_upload /
+// rt_launch / rt_launch_accum and the rt_accum entries.  The A/B scans, the
 // direction-coherent waves and the statistics builds live in trace_diag.hip
 // (librtclj_diag.so only).  DESIGN.md §3.
 #include "trace_kernel.h"
@@ -145,6 +146,55 @@ __global__ __launch_bounds__(256) void quantize_kernel(const float* __restrict__
     for (int step = 128; step > 0; step >>= 1)
       if (s_t[b + step] <= c) b += step;   // b + step <= 255
     out[i] = static_cast<uint8_t>(b);
+  }
+}
+
+// rt_accum_resolve / rt_accum_resolve_u8: an accumulator's integer sums as a
+// frame, by finalize_kernel's conversion -- RN(float(sum)) * 2^-24, / nf
+// (realm: * (1/nf)), nf = RN(float(samples per pixel)) -- and, for the bytes,
+// quantize_kernel's threshold search on that float, in one pass: a thread
+// reads two sums as 16 bytes and writes the floats (out_f) and / or the bytes
+// (out_u8) of both; an odd count's last sum is thread 0's.  The sums are only
+// read: the host shows the frame and goes on adding passes.
+__global__ __launch_bounds__(256) void resolve_kernel(const unsigned long long* __restrict__ sums, size_t n, float nf,
+                                                       int realm, float* __restrict__ out_f,
+                                                       uint8_t* __restrict__ out_u8, const QThr q) {
+  __shared__ float s_t[256];
+  if (out_u8) {   // (uniform)
+    s_t[threadIdx.x] = q.t[threadIdx.x];
+    __syncthreads();
+  }
+  auto put = [&](size_t i, unsigned long long sum) {
+    const float tot = static_cast<float>(sum) * 0x1p-24f;
+    const float c = realm ? tot * (1.0f / nf) : tot / nf;
+    if (out_f) out_f[i] = c;
+    if (out_u8) {
+      int b = 0;
+#pragma unroll
+      for (int step = 128; step > 0; step >>= 1)
+        if (s_t[b + step] <= c) b += step;   // b + step <= 255
+      out_u8[i] = static_cast<uint8_t>(b);
+    }
+  };
+  const ulonglong2* __restrict__ s2 = reinterpret_cast<const ulonglong2*>(sums);   // (hipMalloc's alignment)
+  const size_t pairs = n / 2, stride = static_cast<size_t>(gridDim.x) * 256;
+  for (size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; i < pairs; i += stride) {
+    const ulonglong2 v = s2[i];
+    put(2 * i, v.x);
+    put(2 * i + 1, v.y);
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) put(n - 1, sums[n - 1]);
+}
+
+// rt_accum_add: another accumulator's sums (staged in HBM) added to this
+// one's, by the atomics the trace kernel's units use, so that a pass running
+// on another stream may add to the same words.
+__global__ __launch_bounds__(256) void accum_add_kernel(unsigned long long* __restrict__ sums,
+                                                         const unsigned long long* __restrict__ add, size_t n) {
+  const size_t stride = static_cast<size_t>(gridDim.x) * 256;
+  for (size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; i < n; i += stride) {
+    const unsigned long long v = add[i];
+    if (v) __hip_atomic_fetch_add(&sums[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -898,15 +948,20 @@ int quantize_launch(const float* d_lin, uint8_t* d_out, size_t n, void* stream) 
 }
 }  // namespace rtclj
 
-extern "C" int rt_launch(const rt_dscene* ds, const rt_camera* c, const rt_params* p, float* d_out,
-                         uint64_t* d_counters, void* hip_stream) {
-  clear_error();
-  if (!ds || !c || !p || !d_out) return set_error(RT_E_ARG, "rt_launch: NULL argument");
+// rt_launch, and rt_launch_accum's pass (acc_sums: the accumulator's
+// [rows][width][3] sums; d_out NULL).  A pass is the launch with no whole
+// tiles (n_whole = 0: every unit, one per tile or `split` per tile, adds its
+// integer sums to part[] = acc_sums by atomics) and no finalize_kernel behind
+// it; the stream's own part buffer and its part_dirty flag are left alone.
+static int launch_impl(const rt_dscene* ds, const rt_camera* c, const rt_params* p, float* d_out,
+                       uint64_t* d_counters, void* hip_stream, unsigned long long* acc_sums,
+                       const char* who = "rt_launch") {
+  if (!ds || !c || !p || (!d_out && !acc_sums)) return set_error(RT_E_ARG, std::string(who) + ": NULL argument");
   if (p->width <= 0 || p->height <= 0 || p->spp < 0 || p->spp > RT_MAX_SPP ||
       (p->flags & ~(RT_FLAG_REALM | RT_FLAG_STREAMED | RT_FLAG_REJECTION_SAMPLERS)) != 0)
-    return set_error(RT_E_ARG, "rt_launch: bad width/height/spp/flags");
+    return set_error(RT_E_ARG, std::string(who) + ": bad width/height/spp/flags");
   const int rows = rows_out(*p);
-  if (rows < 0) return set_error(RT_E_ARG, "rt_launch: bad row selection");
+  if (rows < 0) return set_error(RT_E_ARG, std::string(who) + ": bad row selection");
   KArgs a{};
   a.geo = ds->geo;
   a.geo2 = reinterpret_cast<const Pair*>(ds->geo2);
@@ -942,7 +997,7 @@ extern "C" int rt_launch(const rt_dscene* ds, const rt_camera* c, const rt_param
   int vsel = launch_variant(*ds, *p);
   if (variant_table(vsel).scan == SCAN_BVHS && p->max_depth > 1023) vsel = 16;   // (a path's depth left: 10 bits in the exchange)
   const Variant& v = variant_table(vsel);
-  if (!v.fn) return set_error(RT_E_ARG, "rt_launch: no kernel for variant " + std::to_string(vsel));
+  if (!v.fn) return set_error(RT_E_ARG, std::string(who) + ": no kernel for variant " + std::to_string(vsel));
   const DTree& tr = ds->tree[variant_tree(vsel)];
   a.bvh_blob = tr.blob;
   a.bvh_blob_f4 = tr.blob_f4;
@@ -1021,7 +1076,7 @@ extern "C" int rt_launch(const rt_dscene* ds, const rt_camera* c, const rt_param
   // (profiles/r03/share_ab.txt).  RTCLJ_STEAL=0: never share.)
   int split = 1, n_whole = n_tiles;
   const bool steal = sch && env_int("RTCLJ_STEAL", 1, 0) != 0 && !v.stats && v.scan != SCAN_BVHS;
-  if (sch && p->spp > 1) {
+  if ((sch || acc_sums) && p->spp > 1) {
     if (const char* e = std::getenv("RTCLJ_SPLIT")) {
       split = std::max(1, std::atoi(e));
     } else {
@@ -1043,14 +1098,17 @@ extern "C" int rt_launch(const rt_dscene* ds, const rt_camera* c, const rt_param
     split = std::min(split, std::min(p->spp, kSplitMax));
     if (split > 1) n_whole = 0;
   }
+  if (acc_sums) n_whole = 0;   // an accumulating pass: every unit's sums go to part[]
   a.split = split;
   a.n_whole = n_whole;
   a.rt_magic = magic64(a.row_tile);
   const int64_t n_units64 = n_whole + static_cast<int64_t>(n_tiles - n_whole) * split;
-  if (n_units64 > INT_MAX) return set_error(RT_E_ARG, "rt_launch: frame too large");
+  if (n_units64 > INT_MAX) return set_error(RT_E_ARG, std::string(who) + ": frame too large");
   const int n_units = static_cast<int>(n_units64);
   const size_t n_elems = static_cast<size_t>(rows) * p->width * 3;
-  if (split > 1) {
+  if (acc_sums) {
+    a.part = acc_sums;
+  } else if (split > 1) {
     // the split tiles' integer sums: one u64 per channel, added to by the
     // splits, converted and zeroed by finalize_kernel
     const size_t need = n_elems;
@@ -1150,7 +1208,7 @@ extern "C" int rt_launch(const rt_dscene* ds, const rt_camera* c, const rt_param
   // 5.94 ms either way), while its claims and helpers' scans are HBM atomics
   // (C1: 31 vs 11 MB per launch; profiles/r04/share_rounds/): off there
   // unless RTCLJ_SHARE_RECORDED=1.
-  if (steal && split == 1 && (!a.tile_order || first_order || env_int("RTCLJ_SHARE_RECORDED", 0, 0) != 0)) {
+  if (steal && split == 1 && !acc_sums && (!a.tile_order || first_order || env_int("RTCLJ_SHARE_RECORDED", 0, 0) != 0)) {
     const int slots = std::max(1, launch_slots(ds->device, v.fn, lds, v.threads));
     const int n_owner = 2 * slots;   // owner entries: twice the resident workgroups
     // (at most 32 per slot: a tile's helper count stays below 2^16)
@@ -1240,7 +1298,7 @@ extern "C" int rt_launch(const rt_dscene* ds, const rt_camera* c, const rt_param
   // (default 64: as soon as its batches are spent) writes them out and
   // leaves, so a unit's workgroup frees its slot without draining; the sweep
   // launch runs the records.  At most one record per thread of a unit.
-  const bool xport = split > 1 && v.sweep && env_int("RTCLJ_EXPORT", 0, 0) != 0;
+  const bool xport = sch && split > 1 && v.sweep && env_int("RTCLJ_EXPORT", 0, 0) != 0;
   if (xport) {
     const size_t need = static_cast<size_t>(n_units) * v.threads;
     if (sch->xq_cap < need) {   // grow: this stream's kernels may still read the old records
@@ -1267,7 +1325,7 @@ extern "C" int rt_launch(const rt_dscene* ds, const rt_camera* c, const rt_param
                             dim3(256), fa, 0, stream));
   }
   void* args[] = {&a};
-  if (split > 1) sch->part_dirty = true;   // (cleared once finalize_kernel is enqueued)
+  if (split > 1 && !acc_sums) sch->part_dirty = true;   // (cleared once finalize_kernel is enqueued)
   HIP_TRY(hipLaunchKernel(v.fn, dim3(static_cast<unsigned>(grid)), block, args, lds, stream));
   if (xport) {
     // the sweep: one workgroup per slot the device holds, each starting on
@@ -1283,7 +1341,7 @@ extern "C" int rt_launch(const rt_dscene* ds, const rt_camera* c, const rt_param
     void* bargs[] = {&b};
     HIP_TRY(hipLaunchKernel(v.sweep, dim3(static_cast<unsigned>(sw)), block, bargs, lds, stream));
   }
-  if (split > 1) {
+  if (split > 1 && !acc_sums) {
     unsigned long long* part = a.part;
     const int* order = a.tile_order;
     int nw = n_whole, tx = gx, tht = th, w = p->width, nr = rows, spp = p->spp, realm = a.realm;
@@ -1315,6 +1373,182 @@ extern "C" int rt_launch(const rt_dscene* ds, const rt_camera* c, const rt_param
     if (env_int("RTCLJ_SORT_EAGER", 0, 0) != 0) HIP_TRY(static_cast<hipError_t>(sort_record(sch, n_tiles, p->spp, stream)));
   }
   HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+extern "C" int rt_launch(const rt_dscene* ds, const rt_camera* c, const rt_params* p, float* d_out,
+                         uint64_t* d_counters, void* hip_stream) {
+  clear_error();
+  if (!d_out) return set_error(RT_E_ARG, "rt_launch: NULL argument");
+  return launch_impl(ds, c, p, d_out, d_counters, hip_stream, nullptr);
+}
+
+// ---- progressive rendering: the accumulator (rt.h) ------------------------
+// The frame's integer sums outlive the launches: rows x width x 3 u64 on the
+// scene's device, and the samples per pixel they hold (host side; a pass
+// counts when it is enqueued).  mu orders the count's updates and the one
+// staging buffer of rt_accum_add.
+struct rt_accum {
+  int device = 0;
+  rt_params shape{};   // width, height and the row selection (row_tile resolved)
+  size_t n = 0;        // sums: rows_out x width x 3
+  unsigned long long* sums = nullptr;
+  unsigned long long* stage = nullptr;   // rt_accum_add's copy of the caller's sums (n, on first use)
+  mutable std::mutex mu;
+  int64_t samples = 0;
+};
+constexpr int64_t kAccumMaxSamples = 0xffffffffll;   // the sample index is a uint32
+
+static rt_params accum_shape(const rt_params& p) {
+  rt_params s{};
+  s.width = p.width;
+  s.height = p.height;
+  s.row_begin = p.row_begin;
+  s.row_end = p.row_end;
+  s.row_tile = p.row_tile > 0 ? p.row_tile : 8;
+  s.tile_first = p.tile_first;
+  s.tile_step = p.tile_step;
+  return s;
+}
+static bool same_shape(const rt_params& a, const rt_params& b) {
+  return a.width == b.width && a.height == b.height && a.row_begin == b.row_begin && a.row_end == b.row_end &&
+         a.row_tile == b.row_tile && a.tile_first == b.tile_first && a.tile_step == b.tile_step;
+}
+
+extern "C" int rt_accum_create(const rt_dscene* ds, const rt_params* shape, rt_accum** out) {
+  clear_error();
+  if (!ds || !shape || !out) return set_error(RT_E_ARG, "rt_accum_create: NULL argument");
+  *out = nullptr;
+  const int rows = rows_out(*shape);
+  if (shape->width <= 0 || shape->height <= 0 || rows <= 0)
+    return set_error(RT_E_ARG, "rt_accum_create: bad width/height/row selection");
+  HIP_TRY(hipSetDevice(ds->device));
+  rt_accum* acc = new rt_accum;
+  acc->device = ds->device;
+  acc->shape = accum_shape(*shape);
+  acc->n = static_cast<size_t>(rows) * shape->width * 3;
+  // zeroed before the call returns: the first pass may come on any stream
+  hipError_t e = hipMalloc(&acc->sums, acc->n * sizeof(unsigned long long));
+  if (e == hipSuccess) e = static_cast<hipError_t>(fill_async(acc->sums, 0, acc->n * sizeof(unsigned long long), nullptr));
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess) {
+    if (acc->sums) (void)hipFree(acc->sums);
+    delete acc;
+    return hip_fail(e, "rt_accum_create");
+  }
+  *out = acc;
+  return RT_OK;
+}
+
+extern "C" int rt_accum_free(rt_accum* acc) {
+  if (!acc) return RT_OK;
+  (void)hipSetDevice(acc->device);
+  if (acc->sums) (void)hipFree(acc->sums);
+  if (acc->stage) (void)hipFree(acc->stage);
+  delete acc;
+  return RT_OK;
+}
+
+extern "C" int rt_accum_clear(rt_accum* acc, void* hip_stream) {
+  clear_error();
+  if (!acc) return set_error(RT_E_ARG, "rt_accum_clear: NULL argument");
+  std::lock_guard<std::mutex> lk(acc->mu);
+  HIP_TRY(hipSetDevice(acc->device));
+  HIP_TRY(static_cast<hipError_t>(fill_async(acc->sums, 0, acc->n * sizeof(unsigned long long), hip_stream)));
+  acc->samples = 0;
+  return RT_OK;
+}
+
+extern "C" int64_t rt_accum_samples(const rt_accum* acc) {
+  if (!acc) return 0;
+  std::lock_guard<std::mutex> lk(acc->mu);
+  return acc->samples;
+}
+
+extern "C" int rt_launch_accum(const rt_dscene* ds, const rt_camera* c, const rt_params* p, rt_accum* acc,
+                               uint64_t* d_counters, void* hip_stream) {
+  clear_error();
+  if (!ds || !c || !p || !acc) return set_error(RT_E_ARG, "rt_launch_accum: NULL argument");
+  if (ds->device != acc->device)
+    return set_error(RT_E_ARG, "rt_launch_accum: the scene is on device " + std::to_string(ds->device) +
+                                   ", the accumulator on device " + std::to_string(acc->device));
+  if (!same_shape(accum_shape(*p), acc->shape))
+    return set_error(RT_E_ARG, "rt_launch_accum: width/height/row selection differ from the accumulator's");
+  std::lock_guard<std::mutex> lk(acc->mu);
+  if (p->spp > 0 && acc->samples + p->spp > kAccumMaxSamples)
+    return set_error(RT_E_ARG, "rt_launch_accum: more than 2^32 - 1 samples per pixel");
+  const int rc = launch_impl(ds, c, p, nullptr, d_counters, hip_stream, acc->sums, "rt_launch_accum");
+  if (rc == RT_OK) acc->samples += p->spp;
+  return rc;
+}
+
+static int accum_resolve(const rt_accum* acc, int flags, float* d_f, uint8_t* d_u8, void* hip_stream,
+                         const char* who) {
+  clear_error();
+  if (!acc || (!d_f && !d_u8)) return set_error(RT_E_ARG, std::string(who) + ": NULL argument");
+  if ((flags & ~(RT_FLAG_REALM | RT_FLAG_STREAMED | RT_FLAG_REJECTION_SAMPLERS)) != 0)
+    return set_error(RT_E_ARG, std::string(who) + ": bad flags");
+  static const QThr thr = [] {
+    QThr t;
+    std::memcpy(t.t, quantize_thresholds(), sizeof t.t);
+    return t;
+  }();
+  int64_t count;
+  {
+    std::lock_guard<std::mutex> lk(acc->mu);
+    count = acc->samples;
+  }
+  HIP_TRY(hipSetDevice(acc->device));
+  const unsigned long long* sums = acc->sums;
+  size_t n = acc->n;
+  float nf = static_cast<float>(count > 0 ? count : 1);   // RN(float(n))
+  int realm = (flags & RT_FLAG_REALM) ? 1 : 0;
+  QThr q = thr;
+  const size_t blocks = std::max<size_t>(1, std::min<size_t>((n / 2 + 255) / 256, 4096));
+  void* args[] = {&sums, &n, &nf, &realm, &d_f, &d_u8, &q};
+  HIP_TRY(hipLaunchKernel(reinterpret_cast<const void*>(&resolve_kernel), dim3(static_cast<unsigned>(blocks)), dim3(256),
+                          args, 0, static_cast<hipStream_t>(hip_stream)));
+  return RT_OK;
+}
+
+extern "C" int rt_accum_resolve(const rt_accum* acc, int flags, float* d_out, void* hip_stream) {
+  return accum_resolve(acc, flags, d_out, nullptr, hip_stream, "rt_accum_resolve");
+}
+
+extern "C" int rt_accum_resolve_u8(const rt_accum* acc, int flags, uint8_t* d_out, void* hip_stream) {
+  return accum_resolve(acc, flags, nullptr, d_out, hip_stream, "rt_accum_resolve_u8");
+}
+
+extern "C" int rt_accum_read(const rt_accum* acc, uint64_t* host_sums, void* hip_stream) {
+  clear_error();
+  if (!acc || !host_sums) return set_error(RT_E_ARG, "rt_accum_read: NULL argument");
+  HIP_TRY(hipSetDevice(acc->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  HIP_TRY(hipMemcpyAsync(host_sums, acc->sums, acc->n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return RT_OK;
+}
+
+extern "C" int rt_accum_add(rt_accum* acc, const uint64_t* host_sums, int64_t samples, void* hip_stream) {
+  clear_error();
+  if (!acc || !host_sums) return set_error(RT_E_ARG, "rt_accum_add: NULL argument");
+  std::lock_guard<std::mutex> lk(acc->mu);
+  if (samples < 0 || samples > kAccumMaxSamples || acc->samples + samples > kAccumMaxSamples)
+    return set_error(RT_E_ARG, "rt_accum_add: samples negative, or more than 2^32 - 1 per pixel in all");
+  HIP_TRY(hipSetDevice(acc->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (!acc->stage) HIP_TRY(hipMalloc(&acc->stage, acc->n * sizeof(unsigned long long)));
+  HIP_TRY(hipMemcpyAsync(acc->stage, host_sums, acc->n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+  unsigned long long* sums = acc->sums;
+  const unsigned long long* add = acc->stage;
+  size_t n = acc->n;
+  const size_t blocks = std::min<size_t>((n + 255) / 256, 4096);
+  void* args[] = {&sums, &add, &n};
+  HIP_TRY(hipLaunchKernel(reinterpret_cast<const void*>(&accum_add_kernel), dim3(static_cast<unsigned>(blocks)), dim3(256),
+                          args, 0, stream));
+  // the caller's array and the staging copy are free again when this returns
+  HIP_TRY(hipStreamSynchronize(stream));
+  acc->samples += samples;
   return RT_OK;
 }
 

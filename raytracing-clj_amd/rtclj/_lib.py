@@ -97,6 +97,17 @@ SIGNATURES = {
     "rt_scene_free": (C.c_int, [C.c_void_p]),
     "rt_launch": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.c_void_p,
                             C.c_void_p, C.c_void_p]),
+    "rt_accum_create": (C.c_int, [C.c_void_p, C.POINTER(rt_params), C.POINTER(C.c_void_p)]),
+    "rt_accum_free": (C.c_int, [C.c_void_p]),
+    "rt_accum_clear": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_accum_samples": (C.c_int64, [C.c_void_p]),
+    "rt_launch_accum": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    "rt_accum_resolve": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_accum_resolve_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_accum_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "rt_accum_add": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64, C.c_void_p]),
+    "rt_resolve_sums": (C.c_int, [C.POINTER(C.c_uint64), C.c_size_t, C.c_int64, C.c_int, C.POINTER(C.c_float)]),
     "rt_quantize_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rt_set_variant": (C.c_int, [C.c_int]),
     "rt_resolve_variant": (C.c_int, [C.c_void_p]),
@@ -115,7 +126,9 @@ SIGNATURES = {
 RT_ABI_VERSION = 3   # include/rt.h; the structures above are this revision's
 # functions added within the revision (a build from before them still loads)
 ADDITIVE = {"rt_prepare", "rt_render_u8", "rt_quantize_device", "rt_render_submit", "rt_render_submit_u8",
-            "rt_render_wait", "rt_export_stats"}
+            "rt_render_wait", "rt_export_stats", "rt_accum_create", "rt_accum_free", "rt_accum_clear",
+            "rt_accum_samples", "rt_launch_accum", "rt_accum_resolve", "rt_accum_resolve_u8", "rt_accum_read",
+            "rt_accum_add", "rt_resolve_sums"}
 
 
 def load(path: Path) -> C.CDLL:
@@ -168,6 +181,10 @@ def iptr(a):
 
 def u8ptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def u64ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint64))
 
 
 def dptr(a):

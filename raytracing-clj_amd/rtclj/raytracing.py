@@ -25,7 +25,7 @@ import numpy as np
 
 from . import hittable, material
 from ._lib import (RT_DIELECTRIC, RT_LAMBERTIAN, RT_METAL, RT_NONE, RTError, check, dptr, fptr, iptr, lib,
-                   rt_camera, rt_params, rt_scene, rt_stats, u8ptr)
+                   rt_camera, rt_params, rt_scene, rt_stats, u8ptr, u64ptr)
 
 # ---- scene (raytracing.clj:63-78) --------------------------------------------
 hittables = [
@@ -135,9 +135,130 @@ def _frame_args(scene, width, height, spp, max_depth, seed, n_devices, rows, sam
     return scene, p, out
 
 
+class Progressive:
+    """compute-pixel's sample loop (raytracing.clj:141-155) continued across
+    launches: a frame whose samples are added pass by pass on device `device`
+    (rt_accum, include/rt.h).  After any passes, frame() is bit for bit the
+    frame one launch of `samples` spp gives.
+
+        pr = Progressive(scene, cam, 400, 225)
+        pr.add(8); show(pr.frame_u8())       # 8 spp now
+        pr.add(24); show(pr.frame_u8())      # the 32-spp frame, refined
+
+    add() advances sample_begin itself.  `stream`: a HIP stream handle (int)
+    for the passes and copies, default the NULL stream.  frame(), frame_u8()
+    and sums() wait for the passes enqueued on it."""
+
+    def __init__(self, scene, cam: rt_camera, width: int, height: int, max_depth: int = 50, seed: int = 1,
+                 rows=None, row_tile: int = 8, tile_first: int = 0, tile_step: int = 0, flags: int = 0,
+                 sample_begin: int = 0, device: int = 0, stream=None, library=None):
+        self._dll = library if library is not None else lib
+        self.scene = scene if isinstance(scene, Scene) else Scene.from_bodies(scene)
+        self.cam = cam
+        r0, r1 = (0, height) if rows is None else rows
+        self._p = rt_params(width=width, height=height, row_begin=r0, row_end=r1, spp=0, max_depth=max_depth,
+                            seed=seed, sample_begin=sample_begin, row_tile=row_tile, tile_first=tile_first,
+                            tile_step=tile_step, flags=flags)
+        self._first, self._next = sample_begin, sample_begin
+        self._stream = C.c_void_p(stream) if stream else None
+        self._ds, self._acc = C.c_void_p(), C.c_void_p()
+        self._check(self._dll.rt_scene_upload(int(device), C.byref(self.scene.c), C.byref(self._ds)))
+        try:
+            self._check(self._dll.rt_accum_create(self._ds, C.byref(self._p), C.byref(self._acc)))
+        except RTError:
+            self.close()
+            raise
+        self.shape = (self._dll.rt_rows_out(C.byref(self._p)), width, 3)
+
+    def _check(self, code):
+        if code < 0:
+            raise RTError(code, self._dll.rt_last_error().decode(errors="replace"))
+        return code
+
+    @property
+    def samples(self) -> int:
+        """Samples per pixel added so far (rt_accum_samples)."""
+        return int(self._dll.rt_accum_samples(self._acc))
+
+    def add(self, spp: int) -> int:
+        """Enqueue one pass of `spp` more samples per pixel (rt_launch_accum);
+        returns the new count."""
+        if spp < 0:
+            raise ValueError("Progressive.add: spp < 0")
+        self._p.spp = int(spp)
+        self._p.sample_begin = self._next
+        self._check(self._dll.rt_launch_accum(self._ds, C.byref(self.cam), C.byref(self._p), self._acc, None,
+                                              self._stream))
+        self._next += int(spp)
+        return self.samples
+
+    def sums(self) -> np.ndarray:
+        """The raw integer sums, uint64 (rows, width, 3), in 2^-24 units
+        (rt_accum_read): what ranks exchange for shard.combine_exact."""
+        out = np.empty(self.shape, np.uint64)
+        self._check(self._dll.rt_accum_read(self._acc, u64ptr(out), self._stream))
+        return out
+
+    def add_sums(self, sums, samples: int) -> int:
+        """Add another accumulator's sums() and its sample count (rt_accum_add)."""
+        sums = np.ascontiguousarray(sums, np.uint64)
+        if sums.shape != self.shape:
+            raise ValueError(f"Progressive.add_sums: sums must be uint64 {self.shape}")
+        self._check(self._dll.rt_accum_add(self._acc, u64ptr(sums), int(samples), self._stream))
+        return self.samples
+
+    def frame(self) -> np.ndarray:
+        """The frame so far, float32 (rows, width, 3): the sums copied back
+        and converted by rt_resolve_sums, whose bits are rt_accum_resolve's."""
+        s = self.sums()
+        out = np.empty(self.shape, np.float32)
+        self._check(self._dll.rt_resolve_sums(u64ptr(s), s.size, self.samples, self._p.flags, fptr(out)))
+        return out
+
+    def frame_u8(self) -> np.ndarray:
+        """write-color!'s bytes of frame() (the bytes rt_accum_resolve_u8 gives)."""
+        return write_color(self.frame())
+
+    def resolve_into(self, d_out: int, u8: bool = False) -> None:
+        """Enqueue the conversion into a device buffer the caller owns (its
+        address; float32 or, with u8, bytes of `shape`): rt_accum_resolve /
+        rt_accum_resolve_u8 on the stream, no copy back."""
+        fn = self._dll.rt_accum_resolve_u8 if u8 else self._dll.rt_accum_resolve
+        self._check(fn(self._acc, self._p.flags, C.c_void_p(d_out), self._stream))
+
+    def clear(self) -> None:
+        """Back to no samples (rt_accum_clear); the next add() starts at the
+        first sample index again."""
+        self._check(self._dll.rt_accum_clear(self._acc, self._stream))
+        self._next = self._first
+
+    def close(self) -> None:
+        if getattr(self, "_acc", None):
+            self._dll.rt_accum_free(self._acc)
+            self._acc = C.c_void_p()
+        if getattr(self, "_ds", None):
+            self._dll.rt_scene_free(self._ds)
+            self._ds = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def pass_sizes(spp: int, passes: int):
+    """spp samples in `passes` near-equal passes (the larger ones first)."""
+    k = max(1, min(int(passes), max(int(spp), 1)))
+    return [spp // k + (1 if i < spp % k else 0) for i in range(k)]
+
+
 def render(scene, cam: rt_camera, width: int, height: int, spp: int = 100, max_depth: int = 50, seed: int = 1,
            n_devices: int = 0, rows=None, sample_begin: int = 0, row_tile: int = 8, stats: dict | None = None,
-           flags: int = 0, library=None, out=None, u8: bool = False):
+           flags: int = 0, library=None, out=None, u8: bool = False, passes: int | None = None):
     """compute-pixel for every pixel of rows [r0, r1) (default: all), on the GPU.
 
     Returns float32 (rows, width, 3) linear RGB, each pixel the mean of its spp
@@ -147,8 +268,25 @@ def render(scene, cam: rt_camera, width: int, height: int, spp: int = 100, max_d
     renderer drawing frames reuses its framebuffer; a fresh 10 MB array's
     pages are first touched by the copy into it).
     `u8`: return write-color!'s bytes instead (rt_render_u8: the frame is
-    quantised on the device; bit-identical to write_color(render(...)))."""
+    quantised on the device; bit-identical to write_color(render(...))).
+    `passes`: render the spp in that many near-equal accumulating passes on
+    device 0 (Progressive; the same bits as one launch; `stats` is not
+    filled)."""
     dll = library if library is not None else lib
+    if passes is not None:
+        if n_devices not in (0, 1):
+            raise ValueError("render: passes run on one device")
+        with Progressive(scene, cam, width, height, max_depth, seed, rows=rows, row_tile=row_tile, flags=flags,
+                         sample_begin=sample_begin, library=library) as pr:
+            for n in pass_sizes(spp, passes):
+                pr.add(n)
+            got = pr.frame_u8() if u8 else pr.frame()
+        if out is None:
+            return got
+        if out.shape != got.shape or out.dtype != got.dtype:
+            raise ValueError(f"render: out must be {got.dtype.name} {got.shape}")
+        out[...] = got
+        return out
     scene, p, out = _frame_args(scene, width, height, spp, max_depth, seed, n_devices, rows, sample_begin,
                                 row_tile, flags, out, u8)
     st = rt_stats()
@@ -273,5 +411,5 @@ if __name__ == "__main__":  # python -m rtclj.raytracing [spp] [depth]
         sys.exit(str(e))
 
 
-__all__ = ["hittables", "REFERENCE_CAMERA", "image_height", "flatten", "flatten64", "Scene", "camera", "render",
+__all__ = ["hittables", "REFERENCE_CAMERA", "image_height", "flatten", "flatten64", "Scene", "camera", "render", "Progressive", "pass_sizes",
            "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]

@@ -10,7 +10,9 @@ single device would for its pixels/samples):
            over every rank (contiguous halves, as the reference's 2-thread
            pool uses, would leave the top-of-frame rank idle).
   weak   — every rank renders the whole frame with its own sample stripe
-           [rank*spp, (rank+1)*spp); stripes average into a world*spp frame.
+           [rank*spp, (rank+1)*spp); stripes average into a world*spp frame
+           (floats: up to fp32 re-association), or their integer sums add up
+           to exactly the one-device frame (combine_exact).
 
 The host gather puts compacted tile rows back in image order.
 """
@@ -47,6 +49,26 @@ def shard_params(world, rank, width, height, spp, max_depth, seed=1, scaling="st
     if world == 1:
         return dict(base, row_tile=row_tile)
     return dict(base, row_tile=row_tile, tile_first=rank, tile_step=world)
+
+
+def combine_exact(list_of_sums, samples, realm=False):
+    """Weak scaling without the float average: the ranks' integer pixel sums
+    (Progressive.sums() / rt_accum_read: uint64, 2^-24 units, all of one
+    shape) added as integers and converted once by rt_resolve_sums.  `samples`
+    is the total per pixel over the stripes.  The result is bit for bit the
+    frame one device gives for all the samples; the float mean of the ranks'
+    frames agrees with it only up to fp32 re-association.  On a real cluster
+    the addition is an int64 all-reduce."""
+    from ._lib import RT_FLAG_REALM, check, fptr, lib, u64ptr
+    parts = [np.ascontiguousarray(s, np.uint64) for s in list_of_sums]
+    if not parts or any(s.shape != parts[0].shape for s in parts):
+        raise ValueError("combine_exact: sums of one shape, at least one")
+    total = parts[0].copy()
+    for s in parts[1:]:
+        total += s
+    out = np.empty(total.shape, np.float32)
+    check(lib.rt_resolve_sums(u64ptr(total), total.size, int(samples), RT_FLAG_REALM if realm else 0, fptr(out)))
+    return out
 
 
 def gather_rows(height, width, parts):
