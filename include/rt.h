@@ -392,6 +392,108 @@ int rt_accum_add(rt_accum* acc, const uint64_t* host_sums, int64_t samples, void
  * pixel (0 .. 2^32 - 1), flags as rt_accum_resolve. */
 int rt_resolve_sums(const uint64_t* sums, size_t n, int64_t samples, int flags, float* out);
 
+/* ---- adaptive sampling: stop tracing tiles whose two sample halves agree ----
+ * compute-pixel's loop (raytracing.clj:141-155) run only where it still
+ * changes the picture.  An rt_adapt keeps two accumulators' sums, H0 and H1
+ * (each rt_rows_out(shape) x width x 3 u64), one uint32 sample count per
+ * 8 x 8 tile of the output rows (gy x gx of them, gx = ceil(width / 8),
+ * gy = ceil(rt_rows_out / 8), row-major) and a device list of the tiles still
+ * active.  Step k = 0, 1, 2, ... traces step_spp samples per pixel, with the
+ * indices sample_begin + k * step_spp ..., in the active tiles only and adds
+ * them to H[k & 1].  After every odd step both halves of an active tile hold
+ * the same number of samples; once the tile's count has reached min_spp it is
+ * tested: over its pixels inside the frame and their three channels,
+ *   D = sum |H0 - H1|,  S = sum (H0 + H1),  converged iff D * 2^16 <= tol_q16 * S
+ * in unbounded integers.  A converged tile leaves the active set for good, and
+ * so does a tile that reaches max_spp: every active tile has the same count.
+ * The sums are exact integers in any order, so the counts and the frame are a
+ * function of scene, camera, seed, flags and options alone -- not of the
+ * kernel variant, the sample split, the stream or the device -- and every
+ * tile of the frame equals, bit for bit, the same tile of one rt_launch at
+ * spp = that tile's count.
+ *
+ * Two properties of the rule.  Stopping on the samples' own agreement biases
+ * the estimate slightly, as every half-buffer scheme does: a tile is the more
+ * likely to stop the closer its two halves happen to fall, and those samples
+ * are the ones kept.  And the measure is a relative L1 difference, |H0 - H1|
+ * against H0 + H1: a dim but noisy tile does not meet it and runs to max_spp.
+ *
+ * Options: step_spp >= 1; min_spp and max_spp positive multiples of
+ * 2 * step_spp with min_spp <= max_spp <= RT_MAX_SPP (sums stay below 2^56, a
+ * tile's 192-term S below 2^64); tol_q16 <= 65536, the tolerance in 2^-16
+ * units: 0 stops only tiles whose halves are identical, 65536 stops every
+ * tile at min_spp (|a - b| <= a + b). */
+typedef struct rt_adapt_opts {
+  int step_spp, min_spp, max_spp;
+  uint32_t tol_q16;
+} rt_adapt_opts;
+typedef struct rt_adapt rt_adapt;
+/* raytracing.clj:141-155: an adaptive frame for `shape` (read as by
+ * rt_accum_create) on ds's device: sums and counts zero, every tile active.
+ * It holds no reference to ds.  RT_E_ARG on a violated option rule, an empty
+ * or bad selection, or a frame of more than 65535 rows. */
+int rt_adapt_create(const rt_dscene* ds, const rt_params* shape, const rt_adapt_opts* opts, rt_adapt** out);
+int rt_adapt_free(rt_adapt* ad);
+/* raytracing.clj:141-155, the loop's start: back to step 0, sums and counts
+ * zero (enqueued on hip_stream), every tile active. */
+int rt_adapt_clear(rt_adapt* ad, void* hip_stream);
+/* One step of the loop (raytracing.clj:141-155).  Enqueues the trace of
+ * step_spp samples per pixel over the active tiles -- rt_launch_accum's pass
+ * with the active list as its tile order: the trace kernel is the same on
+ * every variant -- and behind it, after an odd step, the rule's kernel.
+ * p->spp is ignored; p->sample_begin is the frame's first index, the same at
+ * every step (the step's offset is the library's).  Seed, camera, depth,
+ * RT_FLAG_REALM, RT_FLAG_REJECTION_SAMPLERS, RT_FLAG_STREAMED and the sample
+ * split apply as to rt_launch_accum, the split computed from the number of
+ * active tiles, so that a thin late step still fills the device.  The steps
+ * neither read nor write the stream's tile-cost record (rt_set_schedule).
+ * Returns the number of tiles traced; 0 when no tile is active: nothing is
+ * enqueued then and d_counters is left alone.  The grid of a launch depends
+ * on the active count, so the step after a tested one first waits for that
+ * test and reads its two numbers back through pinned memory (8 bytes): one
+ * host sync every two steps.  The steps of a frame go on one stream (or are
+ * ordered by the caller).  RT_E_ARG when p's width, height or row selection
+ * differ from the frame's, when ds is on another device, or when the launch's
+ * kernel variant has no 8 x 8 tiles (rt_set_variant 28, the diagnostic
+ * 20 / 21); the frame is unchanged then. */
+int rt_adapt_step(const rt_dscene* ds, const rt_camera* c, const rt_params* p, rt_adapt* ad,
+                  uint64_t* d_counters, void* hip_stream);
+/* raytracing.clj:141-155: the tiles still active, as of the last test read
+ * back (no wait). */
+int rt_adapt_active(const rt_adapt* ad);
+/* raytracing.clj:141-155, the loop's counter: samples traced so far, summed
+ * over the frame's pixels. */
+int64_t rt_adapt_samples(const rt_adapt* ad);
+/* compute-pixel's accum / spp with each tile's own count
+ * (raytracing.clj:141-155, :155).  Asynchronous, non-destructive: d_out
+ * (device, rt_rows_out x width x 3 floats) = per channel
+ * RN(float(H0 + H1)) * 2^-24 / RN(float(count[tile])), or * (1 / RN(float(
+ * count))) with RT_FLAG_REALM in flags (the only flag read) -- rt_launch's own
+ * conversion; a count of 0 divides by 1. */
+int rt_adapt_resolve(const rt_adapt* ad, int flags, float* d_out, void* hip_stream);
+/* The same, quantised in the same kernel by rt_quantize_device's threshold
+ * table (raytracing.clj:141-155, :19-26): the bytes rt_quantize gives for
+ * rt_adapt_resolve's floats. */
+int rt_adapt_resolve_u8(const rt_adapt* ad, int flags, uint8_t* d_out, void* hip_stream);
+/* raytracing.clj:141-155: the gy x gx samples per pixel of the tiles, the
+ * frame's sample heat map, copied to host_counts behind hip_stream's work;
+ * returns when they are there. */
+int rt_adapt_counts(const rt_adapt* ad, uint32_t* host_counts, void* hip_stream);
+/* raytracing.clj:141-155's accum, both halves (rt_accum_read's layout each):
+ * the sums of the even steps into host_sums0, of the odd steps into
+ * host_sums1; returns when they are there. */
+int rt_adapt_read(const rt_adapt* ad, uint64_t* host_sums0, uint64_t* host_sums1, void* hip_stream);
+/* The rule on the host, in plain C++ (no device; raytracing.clj:141-155):
+ * converged[ty * gx + tx] = 1 where tile (tx, ty) of the rows x width frame
+ * whose halves are sums0 and sums1 meets D * 2^16 <= tol_q16 * S, else 0. */
+int rt_adapt_eval_host(const uint64_t* sums0, const uint64_t* sums1, int width, int rows, uint32_t tol_q16,
+                       uint8_t* converged);
+/* rt_adapt_resolve's conversion on the host, in plain C++ (no device;
+ * raytracing.clj:141-155, :155): out (rows x width x 3) from the two halves
+ * and the gy x gx counts, flags as rt_adapt_resolve. */
+int rt_adapt_resolve_host(const uint64_t* sums0, const uint64_t* sums1, const uint32_t* counts, int width,
+                          int rows, int flags, float* out);
+
 /* Asynchronous: enqueue rt_quantize on hip_stream's device for n channels
  * already in HBM (d_lin: n floats, d_out: n bytes, device pointers): the same
  * bytes as rt_quantize for every float (NaN, infinities and denormals

@@ -192,6 +192,59 @@ extern "C" int rt_resolve_sums(const uint64_t* sums, size_t n, int64_t samples, 
   return RT_OK;
 }
 
+// The adaptive sampler's rule on the host (trace.hip's adapt_eval_kernel):
+// per 8 x 8 tile, over its pixels inside the frame, D = sum |h0 - h1| and
+// S = sum (h0 + h1) (192 terms below 2^56 each: below 2^64), converged iff
+// D * 2^16 <= tol * S, the products in 128 bits.
+extern "C" int rt_adapt_eval_host(const uint64_t* sums0, const uint64_t* sums1, int width, int rows,
+                                  uint32_t tol_q16, uint8_t* converged) {
+  clear_error();
+  if (!sums0 || !sums1 || !converged) return set_error(RT_E_ARG, "rt_adapt_eval_host: NULL argument");
+  if (width <= 0 || rows <= 0 || tol_q16 > 65536u)
+    return set_error(RT_E_ARG, "rt_adapt_eval_host: bad width/rows/tol_q16");
+  const int gx = (width + 7) / 8, gy = (rows + 7) / 8;
+  for (int ty = 0; ty < gy; ++ty)
+    for (int tx = 0; tx < gx; ++tx) {
+      uint64_t d = 0, s = 0;
+      for (int y = ty * 8; y < std::min(rows, ty * 8 + 8); ++y)
+        for (int x = tx * 8; x < std::min(width, tx * 8 + 8); ++x)
+          for (int c = 0; c < 3; ++c) {
+            const size_t e = (static_cast<size_t>(y) * width + x) * 3 + c;
+            const uint64_t a = sums0[e], b = sums1[e];
+            d += a > b ? a - b : b - a;
+            s += a + b;
+          }
+      const unsigned __int128 lhs = static_cast<unsigned __int128>(d) << 16;
+      const unsigned __int128 rhs = static_cast<unsigned __int128>(tol_q16) * s;
+      converged[static_cast<size_t>(ty) * gx + tx] = lhs <= rhs ? 1 : 0;
+    }
+  return RT_OK;
+}
+
+// rt_adapt_resolve's conversion on the host (trace.hip's
+// adapt_resolve_kernel): rt_resolve_sums of h0 + h1 with the count of the
+// element's tile
+extern "C" int rt_adapt_resolve_host(const uint64_t* sums0, const uint64_t* sums1, const uint32_t* counts,
+                                     int width, int rows, int flags, float* out) {
+  clear_error();
+  if (!sums0 || !sums1 || !counts || !out) return set_error(RT_E_ARG, "rt_adapt_resolve_host: NULL argument");
+  if (width <= 0 || rows <= 0 || (flags & ~(RT_FLAG_REALM | RT_FLAG_STREAMED | RT_FLAG_REJECTION_SAMPLERS)) != 0)
+    return set_error(RT_E_ARG, "rt_adapt_resolve_host: bad width/rows/flags");
+  const int gx = (width + 7) / 8;
+  const bool realm = (flags & RT_FLAG_REALM) != 0;
+  for (int y = 0; y < rows; ++y)
+    for (int x = 0; x < width; ++x) {
+      const uint32_t n = counts[static_cast<size_t>(y / 8) * gx + x / 8];
+      const float nf = static_cast<float>(n > 0u ? n : 1u);
+      for (int c = 0; c < 3; ++c) {
+        const size_t e = (static_cast<size_t>(y) * width + x) * 3 + c;
+        const float tot = static_cast<float>(sums0[e] + sums1[e]) * 0x1p-24f;
+        out[e] = realm ? tot * (1.0f / nf) : tot / nf;
+      }
+    }
+  return RT_OK;
+}
+
 extern "C" int rt_write_ppm(const char* path, const uint8_t* rgb, int width, int height) {
   clear_error();
   if (!path || !rgb || width <= 0 || height <= 0) return set_error(RT_E_ARG, "rt_write_ppm: bad argument");

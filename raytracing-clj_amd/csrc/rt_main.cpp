@@ -15,10 +15,17 @@
 //   rt_main [spp] [depth] [--scene reference|cover] [--realm] [--width W]
 //           [--seed S] [--gpus N] [--out PATH] [--png PATH] [--no-png] [--json]
 //           [--host-quantize] [--rejection-samplers] [--passes K]
+//           [--adaptive TOLQ16 [--step S] [--min-spp A] [--max-spp B]]
 // Defaults follow the reference: spp 100, depth 50, width 400, 16:9.
 // --passes K: the spp in K near-equal accumulating passes on device 0
 // (rt_launch_accum into an rt_accum, the sums read back, rt_resolve_sums and
 // rt_quantize on the host): the same PPM / PNG bytes as without it.
+// --adaptive TOLQ16: adaptive sampling on device 0 (rt_adapt: steps of S
+// samples, default 10, until every 8 x 8 tile's two sample halves agree within
+// TOLQ16 / 65536 after at least A samples, default 2 S, or holds B, default
+// the spp argument); halves and counts are read back, rt_adapt_resolve_host
+// and rt_quantize on the host.  Prints the samples traced and the tiles at
+// the cap; --json carries them ("adaptive").
 // --json: one more line, a JSON object of where this one-frame process's time
 // went (the device start-up -- the HIP runtime's first rt_device_count, then
 // rt_prepare's context / code object / queue / pageable staging -- on a thread
@@ -40,6 +47,10 @@
 
 int main(int argc, char** argv) {
   int spp = 100, depth = 50, width = 400, gpus = 0, grid = 11, passes = 0;
+  int ad_step = 10, ad_min = 0, ad_max = 0;
+  long long ad_tol = -1;   // --adaptive: the tolerance (< 0: off)
+  long long ad_samples = 0;
+  int ad_tiles = 0, ad_cap_tiles = 0, ad_steps = 0;
   unsigned long long seed = 1;
   std::string scene = "reference", out, png;
   bool realm = false, json = false, host_quantize = false, no_png = false, rejection = false;
@@ -57,7 +68,8 @@ int main(int argc, char** argv) {
   int gpus_arg = 0;
   // (a missing option value ends the process before the start-up thread
   // exists: no exit while that thread may be inside the HIP runtime)
-  static const char* const kValued[] = {"--scene", "--width", "--seed", "--gpus", "--grid", "--out", "--png", "--passes"};
+  static const char* const kValued[] = {"--scene", "--width", "--seed", "--gpus", "--grid", "--out", "--png", "--passes",
+                                        "--adaptive", "--step", "--min-spp", "--max-spp"};
   for (int i = 1; i < argc; ++i) {
     const bool valued = std::any_of(std::begin(kValued), std::end(kValued),
                                     [&](const char* f) { return std::strcmp(argv[i], f) == 0; });
@@ -92,6 +104,10 @@ int main(int argc, char** argv) {
     else if (a == "--out") out = val();
     else if (a == "--png") png = val();
     else if (a == "--passes") passes = std::atoi(val());
+    else if (a == "--adaptive") ad_tol = std::atoll(val());
+    else if (a == "--step") ad_step = std::atoi(val());
+    else if (a == "--min-spp") ad_min = std::atoi(val());
+    else if (a == "--max-spp") ad_max = std::atoi(val());
     else if (a == "--realm") realm = true;
     else if (a == "--rejection-samplers") rejection = true;   // RT_FLAG_REJECTION_SAMPLERS
     else if (a == "--json") json = true;
@@ -157,7 +173,48 @@ int main(int argc, char** argv) {
   std::vector<uint8_t> q(nch);
   rt_stats st{};
   double render_ms = 0.0, quantize_ms = 0.0;
-  if (passes > 0) {
+  if (ad_tol >= 0) {
+    // compute-pixel's sample loop (raytracing.clj:141-155), tile by tile until
+    // the tile's two halves agree
+    rt_adapt_opts o{};
+    o.step_spp = ad_step;
+    o.min_spp = ad_min > 0 ? ad_min : 2 * ad_step;
+    o.max_spp = ad_max > 0 ? ad_max : spp;
+    o.tol_q16 = static_cast<uint32_t>(std::min<long long>(ad_tol, 0xffffffffll));
+    rt_dscene* ds = nullptr;
+    rt_adapt* ad = nullptr;
+    bool ok = rt_scene_upload(0, &s, &ds) == RT_OK && rt_adapt_create(ds, &p, &o, &ad) == RT_OK;
+    int traced = 1;
+    while (ok && traced > 0) {
+      traced = rt_adapt_step(ds, &cam, &p, ad, nullptr, nullptr);
+      ok = traced >= 0;
+      ad_steps += traced > 0;
+    }
+    ad_tiles = ((width + 7) / 8) * ((height + 7) / 8);
+    std::vector<uint32_t> tile_spp(static_cast<size_t>(ad_tiles));
+    ok = ok && rt_adapt_counts(ad, tile_spp.data(), nullptr) == RT_OK;
+    std::vector<uint64_t> h0, h1;
+    std::vector<float> lin;
+    if (ok) {
+      h0.resize(nch), h1.resize(nch), lin.resize(nch);
+      ok = rt_adapt_read(ad, h0.data(), h1.data(), nullptr) == RT_OK &&
+           rt_adapt_resolve_host(h0.data(), h1.data(), tile_spp.data(), width, height, p.flags, lin.data()) == RT_OK;
+    }
+    if (!ok) {
+      std::fprintf(stderr, "--adaptive failed: %s\n", rt_last_error());
+      return 1;
+    }
+    ad_samples = rt_adapt_samples(ad);
+    for (uint32_t n : tile_spp) ad_cap_tiles += n >= static_cast<uint32_t>(o.max_spp);
+    rt_adapt_free(ad);
+    rt_scene_free(ds);
+    render_ms = ms_since(t0);
+    const auto t_q = std::chrono::steady_clock::now();
+    rt_quantize(lin.data(), q.data(), q.size());
+    quantize_ms = ms_since(t_q);
+    st.n_devices = 1;
+    st.samples = static_cast<uint64_t>(ad_samples);
+  } else if (passes > 0) {
     // compute-pixel's sample loop (raytracing.clj:141-155) in K launches
     rt_dscene* ds = nullptr;
     rt_accum* acc = nullptr;
@@ -218,7 +275,11 @@ int main(int argc, char** argv) {
   const double png_ms = png.empty() ? 0.0 : ms_since(t_p);
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   std::printf("\"Elapsed time: %.3f msecs\"\n", ms);  // (time ...) (:99)
-  if (passes > 0)
+  if (ad_tol >= 0)
+    std::printf("bodies %d, devices 1, adaptive: %d steps, %lld samples traced of %lld at the cap, %d of %d tiles at "
+                "the cap, %.3f ms\n", n, ad_steps, ad_samples,
+                static_cast<long long>(width) * height * (ad_max > 0 ? ad_max : spp), ad_cap_tiles, ad_tiles, render_ms);
+  else if (passes > 0)
     std::printf("bodies %d, devices 1, %d passes, %.3f ms, %.1f Msamples/s\n", n,
                 std::max(1, std::min(passes, std::max(spp, 1))), render_ms, st.samples / (render_ms * 1e3));
   else
@@ -233,10 +294,12 @@ int main(int argc, char** argv) {
         "\"quantize_ms\": %.3f, \"write_ms\": %.3f, \"png_ms\": %.3f, \"process_ms\": %.3f, \"rt_stats\": {\"total_ms\": %.3f, "
         "\"upload_ms\": %.3f, \"setup_ms\": %.3f, \"enqueue_ms\": %.3f, \"wait_ms\": %.3f, \"scatter_ms\": %.3f, "
         "\"other_ms\": %.3f, \"kernel_ms\": %.3f, \"d2h_ms\": %.3f, \"segments\": %llu, \"samples\": %llu, "
-        "\"n_devices\": %d}}\n",
+        "\"n_devices\": %d}, \"adaptive\": {\"on\": %d, \"steps\": %d, \"samples_traced\": %lld, "
+        "\"tiles\": %d, \"tiles_at_cap\": %d}}\n",
         ndev, scene_ms, device_count_ms, prep_ms[0], prep_ms[1], prep_ms[2], prep_ms[3], prep_wait_ms, render_ms,
-        (host_quantize || passes > 0) ? "host" : "device", quantize_ms, write_ms, png_ms, ms_since(t_start), st.total_ms,
+        (host_quantize || passes > 0 || ad_tol >= 0) ? "host" : "device", quantize_ms, write_ms, png_ms, ms_since(t_start), st.total_ms,
         st.upload_ms, st.setup_ms, st.enqueue_ms, st.wait_ms, st.scatter_ms, st.other_ms, st.kernel_ms, st.d2h_ms,
-        static_cast<unsigned long long>(st.segments), static_cast<unsigned long long>(st.samples), st.n_devices);
+        static_cast<unsigned long long>(st.segments), static_cast<unsigned long long>(st.samples), st.n_devices,
+        ad_tol >= 0 ? 1 : 0, ad_steps, ad_samples, ad_tiles, ad_cap_tiles);
   return 0;
 }

@@ -1,8 +1,9 @@
 // trace.hip — the product library's gfx950 code object and host side: the
 // shipped kernel's instantiations (trace_kernel.h: the default BVH walk in its
 // two LDS images and its fallbacks), the schedule / split / quantise / fill
-// kernels, the accumulator's resolve / add kernels, and rt_scene_upload /
-// rt_launch / rt_launch_accum and the rt_accum entries.  The A/B scans, the
+// kernels, the accumulator's resolve / add kernels, the adaptive sampler's
+// evaluation / resolve kernels, and rt_scene_upload / rt_launch /
+// rt_launch_accum / rt_adapt_step and the rt_accum and rt_adapt entries.  The A/B scans, the
 // direction-coherent waves and the statistics builds live in trace_diag.hip
 // (librtclj_diag.so only).  DESIGN.md §3.
 #include "trace_kernel.h"
@@ -196,6 +197,151 @@ __global__ __launch_bounds__(256) void accum_add_kernel(unsigned long long* __re
     const unsigned long long v = add[i];
     if (v) __hip_atomic_fetch_add(&sums[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+
+// Adaptive sampling (rt_adapt, rt.h): the stopping rule over the two halves'
+// integer sums, for the tiles of the active list -- one wave per 8 x 8 tile,
+// one lane per pixel (row lane / 8, column lane % 8; a ragged tile's lanes
+// outside the frame hold nothing).  A lane reads its pixel's three u64 of
+// each half as a 16-byte and an 8-byte load (a pixel is 24 bytes: the pair
+// comes first where the pixel starts on 16 bytes, last where it does not),
+// adds D = sum |h0 - h1| and S = sum (h0 + h1) over its channels, and the
+// wave adds the lanes' by shuffles: 192 terms below 2^56 each, below 2^64 in
+// all.  Lane 0 then holds the tile's rule, D * 2^16 <= tol * S as 128-bit
+// integers (the high halves by shift and __umul64hi), writes the tile's count
+// and, when the tile goes on, appends it to the next list: a position from an
+// atomic on state[0], the tile's pixels added to state[1].  The order of the
+// next list is whatever the atomics give: no bit depends on it.  decide = 0
+// (a step after which no tile is tested): the counts only.  Block 0 zeroes
+// `state_next`, the pair the evaluation after this one counts in (the host
+// has read it back before this kernel was enqueued).
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t lo = __shfl_xor(static_cast<uint32_t>(v), off);
+    const uint32_t hi = __shfl_xor(static_cast<uint32_t>(v >> 32), off);
+    v += (static_cast<unsigned long long>(hi) << 32) | lo;
+  }
+  return v;
+}
+// a pixel's three sums at s[0..2], s = sums + e (e: the element index, whose
+// parity is the 16-byte alignment: hipMalloc's base is aligned)
+__device__ __forceinline__ void load_px3(const unsigned long long* __restrict__ s, bool even,
+                                         unsigned long long (&v)[3]) {
+  if (even) {
+    const ulonglong2 p = *reinterpret_cast<const ulonglong2*>(s);
+    v[0] = p.x;
+    v[1] = p.y;
+    v[2] = s[2];
+  } else {
+    const ulonglong2 p = *reinterpret_cast<const ulonglong2*>(s + 1);
+    v[0] = s[0];
+    v[1] = p.x;
+    v[2] = p.y;
+  }
+}
+constexpr int kEvalWaves = 4;   // tiles per block of adapt_eval_kernel
+__global__ __launch_bounds__(64 * kEvalWaves) void adapt_eval_kernel(
+    const unsigned long long* __restrict__ h0, const unsigned long long* __restrict__ h1, int width, int rows,
+    int tiles_x, const int* __restrict__ active, int n_active, int* __restrict__ next, unsigned* __restrict__ state,
+    unsigned* __restrict__ state_next, uint32_t* __restrict__ counts, uint32_t count, uint32_t tol_q16, int decide) {
+  if (state_next && blockIdx.x == 0 && threadIdx.x < 2) state_next[threadIdx.x] = 0u;
+  const int lane = static_cast<int>(threadIdx.x) & 63;
+  const int pos = static_cast<int>(blockIdx.x) * kEvalWaves + (static_cast<int>(threadIdx.x) >> 6);
+  if (pos >= n_active) return;   // (the whole wave)
+  const int tile = active[pos];
+  if (!decide) {
+    if (lane == 0) counts[tile] = count;
+    return;
+  }
+  const int tby = tile / tiles_x, tbx = tile - tby * tiles_x;
+  const int x = tbx * kTile + (lane & 7), y = tby * kTile + (lane >> 3);
+  unsigned long long d = 0ull, s = 0ull;
+  if (x < width && y < rows) {
+    const size_t px = static_cast<size_t>(y) * width + x;
+    unsigned long long a[3], b[3];
+    load_px3(h0 + px * 3, (px & 1) == 0, a);
+    load_px3(h1 + px * 3, (px & 1) == 0, b);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      d += a[c] > b[c] ? a[c] - b[c] : b[c] - a[c];
+      s += a[c] + b[c];
+    }
+  }
+  d = wave_sum_u64(d);
+  s = wave_sum_u64(s);
+  if (lane == 0) {
+    // D * 2^16 against tol * S, both as (high, low) u64 pairs
+    const unsigned long long l_hi = d >> 48, l_lo = d << 16;
+    const unsigned long long r_hi = __umul64hi(static_cast<unsigned long long>(tol_q16), s);
+    const unsigned long long r_lo = static_cast<unsigned long long>(tol_q16) * s;
+    const bool converged = l_hi < r_hi || (l_hi == r_hi && l_lo <= r_lo);
+    counts[tile] = count;
+    if (!converged) {
+      const int vw = min(kTile, width - tbx * kTile), vh = min(kTile, rows - tby * kTile);
+      const unsigned at = __hip_atomic_fetch_add(&state[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      next[at] = tile;
+      __hip_atomic_fetch_add(&state[1], static_cast<unsigned>(vw * vh), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+// rt_adapt_resolve / rt_adapt_resolve_u8: resolve_kernel's conversion of
+// h0 + h1 with the count of the element's own tile.  Block row y is frame row
+// y; a thread reads two sums of each half as 16 bytes (the row's first
+// element alone where the row starts off 16 bytes: `head`), thread 0 of the
+// row's first block the head and the odd tail.
+__global__ __launch_bounds__(256) void adapt_resolve_kernel(const unsigned long long* __restrict__ h0,
+                                                             const unsigned long long* __restrict__ h1,
+                                                             const uint32_t* __restrict__ counts, int width,
+                                                             int tiles_x, int realm, float* __restrict__ out_f,
+                                                             uint8_t* __restrict__ out_u8, const QThr q) {
+  __shared__ float s_t[256];
+  if (out_u8) {   // (uniform)
+    s_t[threadIdx.x] = q.t[threadIdx.x];
+    __syncthreads();
+  }
+  const int y = static_cast<int>(blockIdx.y), w3 = width * 3;
+  const size_t e0 = static_cast<size_t>(y) * w3;
+  const uint32_t* __restrict__ crow = counts + static_cast<size_t>(y / kTile) * tiles_x;
+  auto put = [&](int c, unsigned long long sum) {
+    const uint32_t n = crow[(c / 3) / kTile];
+    const float nf = static_cast<float>(n > 0u ? n : 1u);   // RN(float(count))
+    const float tot = static_cast<float>(sum) * 0x1p-24f;
+    const float v = realm ? tot * (1.0f / nf) : tot / nf;
+    if (out_f) out_f[e0 + c] = v;
+    if (out_u8) {
+      int b = 0;
+#pragma unroll
+      for (int step = 128; step > 0; step >>= 1)
+        if (s_t[b + step] <= v) b += step;   // b + step <= 255
+      out_u8[e0 + c] = static_cast<uint8_t>(b);
+    }
+  };
+  const int head = static_cast<int>(e0 & 1), pairs = (w3 - head) / 2;
+  const int stride = static_cast<int>(gridDim.x) * 256;
+  for (int j = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x); j < pairs; j += stride) {
+    const int c = head + 2 * j;
+    const ulonglong2 a = *reinterpret_cast<const ulonglong2*>(h0 + e0 + c);
+    const ulonglong2 b = *reinterpret_cast<const ulonglong2*>(h1 + e0 + c);
+    put(c, a.x + b.x);
+    put(c + 1, a.y + b.y);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (head) put(0, h0[e0] + h1[e0]);
+    if ((w3 - head) & 1) put(w3 - 1, h0[e0 + w3 - 1] + h1[e0 + w3 - 1]);
+  }
+}
+
+// The first active list: every tile, bottom-up as iota_rev_kernel's first
+// order (the expensive ground tiles first), and the counts' zeroing.
+__global__ __launch_bounds__(256) void adapt_reset_kernel(int* __restrict__ list, uint32_t* __restrict__ counts,
+                                                           unsigned* __restrict__ state, int n) {
+  const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+  if (i < n) {
+    list[i] = n - 1 - i;
+    counts[i] = 0u;
+  }
+  if (i < 4) state[i] = 0u;
 }
 
 // Cost-balanced splits: the next split launch of the shape deals its U units
@@ -953,9 +1099,13 @@ int quantize_launch(const float* d_lin, uint8_t* d_out, size_t n, void* stream) 
 // tiles (n_whole = 0: every unit, one per tile or `split` per tile, adds its
 // integer sums to part[] = acc_sums by atomics) and no finalize_kernel behind
 // it; the stream's own part buffer and its part_dirty flag are left alone.
+// rt_adapt_step's pass adds `active`, a device list of n_active tiles: the
+// launch's tile order, whose length stands for the tile count in the split and
+// the unit count -- the same launch with a shorter order.  It needs 8 x 8
+// tiles, and neither reads nor writes the stream's record (no cost, no order).
 static int launch_impl(const rt_dscene* ds, const rt_camera* c, const rt_params* p, float* d_out,
                        uint64_t* d_counters, void* hip_stream, unsigned long long* acc_sums,
-                       const char* who = "rt_launch") {
+                       const char* who = "rt_launch", const int* active = nullptr, int n_active = 0) {
   if (!ds || !c || !p || (!d_out && !acc_sums)) return set_error(RT_E_ARG, std::string(who) + ": NULL argument");
   if (p->width <= 0 || p->height <= 0 || p->spp < 0 || p->spp > RT_MAX_SPP ||
       (p->flags & ~(RT_FLAG_REALM | RT_FLAG_STREAMED | RT_FLAG_REJECTION_SAMPLERS)) != 0)
@@ -1023,7 +1173,9 @@ static int launch_impl(const rt_dscene* ds, const rt_camera* c, const rt_params*
   const int th = variant_rows(v);   // the variant's tile rows
   const int gx = (p->width + kTile - 1) / kTile, gy = (rows + th - 1) / th;
   const dim3 block(v.threads);
-  const int n_tiles = gx * gy;
+  if (active && (th != kTile || n_active <= 0 || n_active > gx * gy))
+    return set_error(RT_E_ARG, std::string(who) + ": variant " + std::to_string(vsel) + " has no 8 x 8 tiles");
+  const int n_tiles = active ? n_active : gx * gy;
   a.tiles_x = gx;
   if (v.stats) {
     const int rc = dbg_buffers(ds->device, &a.dbg, &a.dbgw);
@@ -1050,7 +1202,7 @@ static int launch_impl(const rt_dscene* ds, const rt_camera* c, const rt_params*
   // the stream's entry: adaptive schedule and split partial sums
   Schedule* sch = nullptr;
   std::unique_lock<std::mutex> sched_lock;
-  {
+  if (!active) {
     ScheduleSet& set = ds->sched;
     sched_lock = std::unique_lock<std::mutex>(set.mu);
     for (int k = 0; k < set.used && !sch; ++k)
@@ -1199,6 +1351,7 @@ static int launch_impl(const rt_dscene* ds, const rt_camera* c, const rt_params*
     // when this launch shape starts a new history
     if (!sch->ready) fills.add(sch->cost, 0, n_tiles * sizeof(unsigned));
   }
+  if (active) a.tile_order = active;
   // the grid: the units, then (stealing) the thieves, dispatched last, i.e.
   // as the units' slots free up in the launch's tail
   int64_t grid = n_units;
@@ -1549,6 +1702,275 @@ extern "C" int rt_accum_add(rt_accum* acc, const uint64_t* host_sums, int64_t sa
   // the caller's array and the staging copy are free again when this returns
   HIP_TRY(hipStreamSynchronize(stream));
   acc->samples += samples;
+  return RT_OK;
+}
+
+// ---- adaptive sampling: two half accumulators and a stopping rule (rt.h) -----
+// h[0], h[1]: the sums of the even and the odd steps, in the accumulator's
+// layout; counts: samples per pixel of each 8 x 8 tile of the output rows;
+// list[cur]: the tiles still traced, n_active of them holding px_active
+// pixels.  An evaluation (adapt_eval_kernel behind an odd step) writes
+// list[cur ^ 1] and counts its length and pixels in state[2 * (gen & 1) ..];
+// that pair is copied to `pinned` behind it, and the next step waits for `ev`
+// and takes the two numbers from there: the grid of its launch depends on
+// them.  The pairs alternate so that a kernel zeroes the one the evaluation
+// after it counts in.  mu orders the entries' host state.
+struct rt_adapt {
+  int device = 0;
+  rt_params shape{};
+  rt_adapt_opts opts{};
+  int rows = 0, gx = 0, gy = 0, n_tiles = 0;
+  size_t n = 0;   // sums per half: rows x width x 3
+  unsigned long long* h[2] = {nullptr, nullptr};
+  uint32_t* counts = nullptr;
+  int* list[2] = {nullptr, nullptr};
+  unsigned* state = nullptr;    // device u32[4]
+  unsigned* pinned = nullptr;   // host u32[2]
+  hipEvent_t ev = nullptr;
+  mutable std::mutex mu;
+  int step = 0, cur = 0, gen = 0;
+  bool pending = false;   // an evaluation's read-back is in flight
+  int n_active = 0;
+  int64_t px_active = 0, samples = 0;
+};
+
+static const char* adapt_opts_error(const rt_adapt_opts& o) {
+  if (o.step_spp < 1) return "step_spp < 1";
+  const int64_t two = 2 * static_cast<int64_t>(o.step_spp);
+  if (o.min_spp <= 0 || o.min_spp % two != 0) return "min_spp is no positive multiple of 2 * step_spp";
+  if (o.max_spp <= 0 || o.max_spp % two != 0) return "max_spp is no positive multiple of 2 * step_spp";
+  if (o.min_spp > o.max_spp) return "min_spp > max_spp";
+  if (o.max_spp > RT_MAX_SPP) return "max_spp > RT_MAX_SPP";
+  if (o.tol_q16 > 65536u) return "tol_q16 > 65536";
+  return nullptr;
+}
+
+static void adapt_release(rt_adapt* ad) {
+  (void)hipSetDevice(ad->device);
+  for (int k = 0; k < 2; ++k) {
+    if (ad->h[k]) (void)hipFree(ad->h[k]);
+    if (ad->list[k]) (void)hipFree(ad->list[k]);
+  }
+  if (ad->counts) (void)hipFree(ad->counts);
+  if (ad->state) (void)hipFree(ad->state);
+  if (ad->pinned) (void)hipHostFree(ad->pinned);
+  if (ad->ev) (void)hipEventDestroy(ad->ev);
+  delete ad;
+}
+
+// step 0, every tile active, sums and counts zero: enqueued on stream
+static hipError_t adapt_reset(rt_adapt* ad, hipStream_t stream) {
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 2 && e == hipSuccess; ++k)
+    e = static_cast<hipError_t>(fill_async(ad->h[k], 0, ad->n * sizeof(unsigned long long), stream));
+  if (e != hipSuccess) return e;
+  int* list = ad->list[0];
+  uint32_t* counts = ad->counts;
+  unsigned* state = ad->state;
+  int n = ad->n_tiles;
+  void* args[] = {&list, &counts, &state, &n};
+  e = hipLaunchKernel(reinterpret_cast<const void*>(&adapt_reset_kernel), dim3(static_cast<unsigned>((n + 255) / 256)),
+                      dim3(256), args, 0, stream);
+  ad->step = ad->cur = ad->gen = 0;
+  ad->pending = false;
+  ad->n_active = ad->n_tiles;
+  ad->px_active = static_cast<int64_t>(ad->rows) * ad->shape.width;
+  ad->samples = 0;
+  return e;
+}
+
+extern "C" int rt_adapt_create(const rt_dscene* ds, const rt_params* shape, const rt_adapt_opts* opts,
+                               rt_adapt** out) {
+  clear_error();
+  if (out) *out = nullptr;
+  if (!shape || !opts || !out) return set_error(RT_E_ARG, "rt_adapt_create: NULL argument");
+  if (const char* why = adapt_opts_error(*opts)) return set_error(RT_E_ARG, std::string("rt_adapt_create: ") + why);
+  if (!ds) return set_error(RT_E_ARG, "rt_adapt_create: NULL argument");
+  const int rows = rows_out(*shape);
+  if (shape->width <= 0 || shape->height <= 0 || rows <= 0)
+    return set_error(RT_E_ARG, "rt_adapt_create: bad width/height/row selection");
+  const int64_t tiles = static_cast<int64_t>((shape->width + kTile - 1) / kTile) * ((rows + kTile - 1) / kTile);
+  // (the resolve's grid has a block row per frame row; the pixel count is a u32)
+  if (rows > 65535 || tiles > INT_MAX / kSplitMax || static_cast<int64_t>(rows) * shape->width > 0xffffffffll)
+    return set_error(RT_E_ARG, "rt_adapt_create: frame too large (more than 65535 rows)");
+  HIP_TRY(hipSetDevice(ds->device));
+  rt_adapt* ad = new rt_adapt;
+  ad->device = ds->device;
+  ad->shape = accum_shape(*shape);
+  ad->opts = *opts;
+  ad->rows = rows;
+  ad->gx = (shape->width + kTile - 1) / kTile;
+  ad->gy = (rows + kTile - 1) / kTile;
+  ad->n_tiles = static_cast<int>(tiles);
+  ad->n = static_cast<size_t>(rows) * shape->width * 3;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+    e = hipMalloc(&ad->h[k], ad->n * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc(&ad->list[k], ad->n_tiles * sizeof(int));
+  }
+  if (e == hipSuccess) e = hipMalloc(&ad->counts, ad->n_tiles * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&ad->state, 4 * sizeof(unsigned));
+  if (e == hipSuccess) e = hipHostMalloc(&ad->pinned, 2 * sizeof(unsigned));
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&ad->ev, hipEventDisableTiming);
+  // ready before the call returns: the first step may come on any stream
+  if (e == hipSuccess) e = adapt_reset(ad, nullptr);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess) {
+    adapt_release(ad);
+    return hip_fail(e, "rt_adapt_create");
+  }
+  *out = ad;
+  return RT_OK;
+}
+
+extern "C" int rt_adapt_free(rt_adapt* ad) {
+  if (!ad) return RT_OK;
+  if (ad->pending) (void)hipEventSynchronize(ad->ev);   // (the copy into `pinned`)
+  adapt_release(ad);
+  return RT_OK;
+}
+
+extern "C" int rt_adapt_clear(rt_adapt* ad, void* hip_stream) {
+  clear_error();
+  if (!ad) return set_error(RT_E_ARG, "rt_adapt_clear: NULL argument");
+  std::lock_guard<std::mutex> lk(ad->mu);
+  HIP_TRY(hipSetDevice(ad->device));
+  if (ad->pending) HIP_TRY(hipEventSynchronize(ad->ev));
+  HIP_TRY(adapt_reset(ad, static_cast<hipStream_t>(hip_stream)));
+  return RT_OK;
+}
+
+// the evaluation in flight, if any: wait for it and take its two numbers
+static int adapt_settle(rt_adapt* ad) {
+  if (!ad->pending) return RT_OK;
+  HIP_TRY(hipEventSynchronize(ad->ev));
+  ad->pending = false;
+  ad->n_active = static_cast<int>(ad->pinned[0]);
+  ad->px_active = static_cast<int64_t>(ad->pinned[1]);
+  return RT_OK;
+}
+
+extern "C" int rt_adapt_step(const rt_dscene* ds, const rt_camera* c, const rt_params* p, rt_adapt* ad,
+                             uint64_t* d_counters, void* hip_stream) {
+  clear_error();
+  if (!ds || !c || !p || !ad) return set_error(RT_E_ARG, "rt_adapt_step: NULL argument");
+  if (ds->device != ad->device)
+    return set_error(RT_E_ARG, "rt_adapt_step: the scene is on device " + std::to_string(ds->device) +
+                                   ", the adaptive frame on device " + std::to_string(ad->device));
+  if (!same_shape(accum_shape(*p), ad->shape))
+    return set_error(RT_E_ARG, "rt_adapt_step: width/height/row selection differ from the adaptive frame's");
+  std::lock_guard<std::mutex> lk(ad->mu);
+  const rt_adapt_opts& o = ad->opts;
+  if (p->sample_begin < 0 || static_cast<int64_t>(p->sample_begin) + o.max_spp > INT_MAX)
+    return set_error(RT_E_ARG, "rt_adapt_step: sample_begin + max_spp passes 2^31 - 1");
+  HIP_TRY(hipSetDevice(ad->device));
+  if (const int rc = adapt_settle(ad)) return rc;
+  if (ad->n_active == 0) return 0;
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  rt_params q = *p;
+  q.spp = o.step_spp;
+  q.sample_begin = p->sample_begin + ad->step * o.step_spp;
+  const int traced = ad->n_active;
+  const int rc = launch_impl(ds, c, &q, nullptr, d_counters, hip_stream, ad->h[ad->step & 1], "rt_adapt_step",
+                             ad->list[ad->cur], traced);
+  if (rc != RT_OK) return rc;
+  ad->samples += ad->px_active * o.step_spp;
+  ++ad->step;
+  // behind the trace: the tiles' new count, and after an odd step that
+  // reached min_spp the rule (at max_spp every tile leaves untested)
+  uint32_t count = static_cast<uint32_t>(ad->step) * static_cast<uint32_t>(o.step_spp);
+  const bool even_halves = (ad->step & 1) == 0;
+  const bool at_cap = even_halves && count >= static_cast<uint32_t>(o.max_spp);
+  int decide = even_halves && !at_cap && count >= static_cast<uint32_t>(o.min_spp);
+  const unsigned long long *h0 = ad->h[0], *h1 = ad->h[1];
+  int width = ad->shape.width, rows = ad->rows, tiles_x = ad->gx, n_active = traced;
+  const int* active = ad->list[ad->cur];
+  int* next = ad->list[ad->cur ^ 1];
+  unsigned* state = ad->state + 2 * (ad->gen & 1);
+  unsigned* state_next = decide ? ad->state + 2 * ((ad->gen + 1) & 1) : nullptr;
+  uint32_t* counts = ad->counts;
+  uint32_t tol = o.tol_q16;
+  void* args[] = {&h0, &h1, &width, &rows, &tiles_x, &active, &n_active, &next, &state, &state_next, &counts,
+                  &count, &tol, &decide};
+  HIP_TRY(hipLaunchKernel(reinterpret_cast<const void*>(&adapt_eval_kernel),
+                          dim3(static_cast<unsigned>((n_active + kEvalWaves - 1) / kEvalWaves)), dim3(64 * kEvalWaves),
+                          args, 0, stream));
+  if (decide) {
+    HIP_TRY(hipMemcpyAsync(ad->pinned, state, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(ad->ev, stream));
+    ad->pending = true;
+    ad->cur ^= 1;
+    ++ad->gen;
+  } else if (at_cap) {
+    ad->n_active = 0;
+    ad->px_active = 0;
+  }
+  return traced;
+}
+
+extern "C" int rt_adapt_active(const rt_adapt* ad) {
+  if (!ad) return 0;
+  std::lock_guard<std::mutex> lk(ad->mu);
+  return ad->n_active;
+}
+
+extern "C" int64_t rt_adapt_samples(const rt_adapt* ad) {
+  if (!ad) return 0;
+  std::lock_guard<std::mutex> lk(ad->mu);
+  return ad->samples;
+}
+
+static int adapt_resolve(const rt_adapt* ad, int flags, float* d_f, uint8_t* d_u8, void* hip_stream,
+                         const char* who) {
+  clear_error();
+  if (!ad || (!d_f && !d_u8)) return set_error(RT_E_ARG, std::string(who) + ": NULL argument");
+  if ((flags & ~(RT_FLAG_REALM | RT_FLAG_STREAMED | RT_FLAG_REJECTION_SAMPLERS)) != 0)
+    return set_error(RT_E_ARG, std::string(who) + ": bad flags");
+  static const QThr thr = [] {
+    QThr t;
+    std::memcpy(t.t, quantize_thresholds(), sizeof t.t);
+    return t;
+  }();
+  HIP_TRY(hipSetDevice(ad->device));
+  const unsigned long long *h0 = ad->h[0], *h1 = ad->h[1];
+  const uint32_t* counts = ad->counts;
+  int width = ad->shape.width, tiles_x = ad->gx, realm = (flags & RT_FLAG_REALM) ? 1 : 0;
+  QThr q = thr;
+  const unsigned bx = static_cast<unsigned>(std::max(1, std::min((width * 3 / 2 + 255) / 256, 64)));
+  void* args[] = {&h0, &h1, &counts, &width, &tiles_x, &realm, &d_f, &d_u8, &q};
+  // (the rows are the grid's y: rt_adapt_create admits at most 65535)
+  HIP_TRY(hipLaunchKernel(reinterpret_cast<const void*>(&adapt_resolve_kernel),
+                          dim3(bx, static_cast<unsigned>(ad->rows)), dim3(256), args, 0,
+                          static_cast<hipStream_t>(hip_stream)));
+  return RT_OK;
+}
+
+extern "C" int rt_adapt_resolve(const rt_adapt* ad, int flags, float* d_out, void* hip_stream) {
+  return adapt_resolve(ad, flags, d_out, nullptr, hip_stream, "rt_adapt_resolve");
+}
+
+extern "C" int rt_adapt_resolve_u8(const rt_adapt* ad, int flags, uint8_t* d_out, void* hip_stream) {
+  return adapt_resolve(ad, flags, nullptr, d_out, hip_stream, "rt_adapt_resolve_u8");
+}
+
+extern "C" int rt_adapt_counts(const rt_adapt* ad, uint32_t* host_counts, void* hip_stream) {
+  clear_error();
+  if (!ad || !host_counts) return set_error(RT_E_ARG, "rt_adapt_counts: NULL argument");
+  HIP_TRY(hipSetDevice(ad->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  HIP_TRY(hipMemcpyAsync(host_counts, ad->counts, ad->n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return RT_OK;
+}
+
+extern "C" int rt_adapt_read(const rt_adapt* ad, uint64_t* host_sums0, uint64_t* host_sums1, void* hip_stream) {
+  clear_error();
+  if (!ad || !host_sums0 || !host_sums1) return set_error(RT_E_ARG, "rt_adapt_read: NULL argument");
+  HIP_TRY(hipSetDevice(ad->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  HIP_TRY(hipMemcpyAsync(host_sums0, ad->h[0], ad->n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(host_sums1, ad->h[1], ad->n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
   return RT_OK;
 }
 

@@ -70,6 +70,10 @@ class rt_stats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class rt_adapt_opts(C.Structure):
+    _fields_ = [("step_spp", C.c_int), ("min_spp", C.c_int), ("max_spp", C.c_int), ("tol_q16", C.c_uint32)]
+
+
 # symbol -> (restype, argtypes); every function include/rt.h declares
 SIGNATURES = {
     "rt_camera_setup": (C.c_int, [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -108,6 +112,21 @@ SIGNATURES = {
     "rt_accum_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     "rt_accum_add": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64, C.c_void_p]),
     "rt_resolve_sums": (C.c_int, [C.POINTER(C.c_uint64), C.c_size_t, C.c_int64, C.c_int, C.POINTER(C.c_float)]),
+    "rt_adapt_create": (C.c_int, [C.c_void_p, C.POINTER(rt_params), C.POINTER(rt_adapt_opts), C.POINTER(C.c_void_p)]),
+    "rt_adapt_free": (C.c_int, [C.c_void_p]),
+    "rt_adapt_clear": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_adapt_step": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.c_void_p,
+                                C.c_void_p, C.c_void_p]),
+    "rt_adapt_active": (C.c_int, [C.c_void_p]),
+    "rt_adapt_samples": (C.c_int64, [C.c_void_p]),
+    "rt_adapt_resolve": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_adapt_resolve_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_adapt_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),
+    "rt_adapt_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
+    "rt_adapt_eval_host": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_uint32,
+                                     C.POINTER(C.c_uint8)]),
+    "rt_adapt_resolve_host": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_int,
+                                        C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "rt_quantize_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rt_set_variant": (C.c_int, [C.c_int]),
     "rt_resolve_variant": (C.c_int, [C.c_void_p]),
@@ -128,7 +147,9 @@ RT_ABI_VERSION = 3   # include/rt.h; the structures above are this revision's
 ADDITIVE = {"rt_prepare", "rt_render_u8", "rt_quantize_device", "rt_render_submit", "rt_render_submit_u8",
             "rt_render_wait", "rt_export_stats", "rt_accum_create", "rt_accum_free", "rt_accum_clear",
             "rt_accum_samples", "rt_launch_accum", "rt_accum_resolve", "rt_accum_resolve_u8", "rt_accum_read",
-            "rt_accum_add", "rt_resolve_sums"}
+            "rt_accum_add", "rt_resolve_sums", "rt_adapt_create", "rt_adapt_free", "rt_adapt_clear", "rt_adapt_step",
+            "rt_adapt_active", "rt_adapt_samples", "rt_adapt_resolve", "rt_adapt_resolve_u8", "rt_adapt_counts",
+            "rt_adapt_read", "rt_adapt_eval_host", "rt_adapt_resolve_host"}
 
 
 def load(path: Path) -> C.CDLL:
@@ -181,6 +202,10 @@ def iptr(a):
 
 def u8ptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def u32ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
 
 
 def u64ptr(a):

@@ -25,7 +25,7 @@ import numpy as np
 
 from . import hittable, material
 from ._lib import (RT_DIELECTRIC, RT_LAMBERTIAN, RT_METAL, RT_NONE, RTError, check, dptr, fptr, iptr, lib,
-                   rt_camera, rt_params, rt_scene, rt_stats, u8ptr, u64ptr)
+                   rt_adapt_opts, rt_camera, rt_params, rt_scene, rt_stats, u8ptr, u32ptr, u64ptr)
 
 # ---- scene (raytracing.clj:63-78) --------------------------------------------
 hittables = [
@@ -250,6 +250,126 @@ class Progressive:
         self.close()
 
 
+class Adaptive:
+    """compute-pixel's sample loop (raytracing.clj:141-155) run only where it
+    still changes the picture (rt_adapt, include/rt.h): the samples go into
+    two half accumulators by turns, and an 8 x 8 tile whose halves agree
+    within tol_q16 / 65536 (relative L1) after at least min_spp samples, or
+    which reaches max_spp, is traced no more.  Every tile of frame() is bit
+    for bit that tile of one launch at spp = counts()[tile].
+
+        ad = Adaptive(scene, cam, 400, 225, tol_q16=2048, step=10, min_spp=20, max_spp=100)
+        ad.run(); show(ad.frame_u8()); heat = ad.counts()
+
+    `stream`: a HIP stream handle (int) for the steps and copies, default the
+    NULL stream."""
+
+    def __init__(self, scene, cam: rt_camera, width: int, height: int, tol_q16: int = 2048, step: int = 8,
+                 min_spp: int = 16, max_spp: int = 64, max_depth: int = 50, seed: int = 1, rows=None,
+                 row_tile: int = 8, tile_first: int = 0, tile_step: int = 0, flags: int = 0, sample_begin: int = 0,
+                 device: int = 0, stream=None, library=None):
+        self._dll = library if library is not None else lib
+        self.scene = scene if isinstance(scene, Scene) else Scene.from_bodies(scene)
+        self.cam = cam
+        r0, r1 = (0, height) if rows is None else rows
+        self._p = rt_params(width=width, height=height, row_begin=r0, row_end=r1, spp=0, max_depth=max_depth,
+                            seed=seed, sample_begin=sample_begin, row_tile=row_tile, tile_first=tile_first,
+                            tile_step=tile_step, flags=flags)
+        self.opts = rt_adapt_opts(step_spp=int(step), min_spp=int(min_spp), max_spp=int(max_spp), tol_q16=int(tol_q16))
+        self._stream = C.c_void_p(stream) if stream else None
+        self._ds, self._ad = C.c_void_p(), C.c_void_p()
+        self._check(self._dll.rt_scene_upload(int(device), C.byref(self.scene.c), C.byref(self._ds)))
+        try:
+            self._check(self._dll.rt_adapt_create(self._ds, C.byref(self._p), C.byref(self.opts), C.byref(self._ad)))
+        except RTError:
+            self.close()
+            raise
+        self.shape = (self._dll.rt_rows_out(C.byref(self._p)), width, 3)
+        self.tiles = ((self.shape[0] + 7) // 8, (width + 7) // 8)
+
+    def _check(self, code):
+        if code < 0:
+            raise RTError(code, self._dll.rt_last_error().decode(errors="replace"))
+        return code
+
+    @property
+    def samples_traced(self) -> int:
+        """Samples traced so far, summed over pixels (rt_adapt_samples)."""
+        return int(self._dll.rt_adapt_samples(self._ad))
+
+    @property
+    def active(self) -> int:
+        """Tiles still active as of the last test read back (rt_adapt_active)."""
+        return int(self._dll.rt_adapt_active(self._ad))
+
+    def step(self) -> int:
+        """Enqueue one step (rt_adapt_step); returns the tiles it traces, 0
+        once every tile has stopped."""
+        return self._check(self._dll.rt_adapt_step(self._ds, C.byref(self.cam), C.byref(self._p), self._ad, None,
+                                                   self._stream))
+
+    def run(self) -> int:
+        """Steps until no tile is active; returns their number."""
+        n = 0
+        while self.step() > 0:
+            n += 1
+        return n
+
+    def counts(self) -> np.ndarray:
+        """Samples per pixel of each 8 x 8 tile, uint32 (gy, gx): the heat map."""
+        out = np.empty(self.tiles, np.uint32)
+        self._check(self._dll.rt_adapt_counts(self._ad, u32ptr(out), self._stream))
+        return out
+
+    def halves(self):
+        """The two halves' integer sums, uint64 (rows, width, 3) each (rt_adapt_read)."""
+        h0, h1 = np.empty(self.shape, np.uint64), np.empty(self.shape, np.uint64)
+        self._check(self._dll.rt_adapt_read(self._ad, u64ptr(h0), u64ptr(h1), self._stream))
+        return h0, h1
+
+    def frame(self) -> np.ndarray:
+        """The frame so far, float32 (rows, width, 3): the halves and counts
+        copied back and converted by rt_adapt_resolve_host, whose bits are
+        rt_adapt_resolve's."""
+        h0, h1 = self.halves()
+        counts = self.counts()
+        out = np.empty(self.shape, np.float32)
+        self._check(self._dll.rt_adapt_resolve_host(u64ptr(h0), u64ptr(h1), u32ptr(counts), self.shape[1],
+                                                    self.shape[0], self._p.flags, fptr(out)))
+        return out
+
+    def frame_u8(self) -> np.ndarray:
+        """write-color!'s bytes of frame() (the bytes rt_adapt_resolve_u8 gives)."""
+        return write_color(self.frame())
+
+    def resolve_into(self, d_out: int, u8: bool = False) -> None:
+        """Enqueue the conversion into a device buffer the caller owns
+        (rt_adapt_resolve / rt_adapt_resolve_u8 on the stream, no copy back)."""
+        fn = self._dll.rt_adapt_resolve_u8 if u8 else self._dll.rt_adapt_resolve
+        self._check(fn(self._ad, self._p.flags, C.c_void_p(d_out), self._stream))
+
+    def clear(self) -> None:
+        """Back to step 0 with every tile active (rt_adapt_clear)."""
+        self._check(self._dll.rt_adapt_clear(self._ad, self._stream))
+
+    def close(self) -> None:
+        if getattr(self, "_ad", None):
+            self._dll.rt_adapt_free(self._ad)
+            self._ad = C.c_void_p()
+        if getattr(self, "_ds", None):
+            self._dll.rt_scene_free(self._ds)
+            self._ds = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
 def pass_sizes(spp: int, passes: int):
     """spp samples in `passes` near-equal passes (the larger ones first)."""
     k = max(1, min(int(passes), max(int(spp), 1)))
@@ -258,7 +378,8 @@ def pass_sizes(spp: int, passes: int):
 
 def render(scene, cam: rt_camera, width: int, height: int, spp: int = 100, max_depth: int = 50, seed: int = 1,
            n_devices: int = 0, rows=None, sample_begin: int = 0, row_tile: int = 8, stats: dict | None = None,
-           flags: int = 0, library=None, out=None, u8: bool = False, passes: int | None = None):
+           flags: int = 0, library=None, out=None, u8: bool = False, passes: int | None = None,
+           adaptive: dict | None = None):
     """compute-pixel for every pixel of rows [r0, r1) (default: all), on the GPU.
 
     Returns float32 (rows, width, 3) linear RGB, each pixel the mean of its spp
@@ -271,16 +392,28 @@ def render(scene, cam: rt_camera, width: int, height: int, spp: int = 100, max_d
     quantised on the device; bit-identical to write_color(render(...))).
     `passes`: render the spp in that many near-equal accumulating passes on
     device 0 (Progressive; the same bits as one launch; `stats` is not
-    filled)."""
+    filled).
+    `adaptive`: dict(tol_q16=, step=, min_spp=, max_spp=) -- sample adaptively
+    on device 0 (Adaptive, run to the end; `spp` and `passes` are not read;
+    with a dict `stats`, its "samples" and "tile_spp" are filled)."""
     dll = library if library is not None else lib
-    if passes is not None:
+    if adaptive is not None or passes is not None:
         if n_devices not in (0, 1):
-            raise ValueError("render: passes run on one device")
+            raise ValueError("render: passes and adaptive sampling run on one device")
+    if adaptive is not None:
+        with Adaptive(scene, cam, width, height, max_depth=max_depth, seed=seed, rows=rows, row_tile=row_tile,
+                      flags=flags, sample_begin=sample_begin, library=library, **adaptive) as ad:
+            ad.run()
+            got = ad.frame_u8() if u8 else ad.frame()
+            if stats is not None:
+                stats.update(samples=ad.samples_traced, tile_spp=ad.counts())
+    elif passes is not None:
         with Progressive(scene, cam, width, height, max_depth, seed, rows=rows, row_tile=row_tile, flags=flags,
                          sample_begin=sample_begin, library=library) as pr:
             for n in pass_sizes(spp, passes):
                 pr.add(n)
             got = pr.frame_u8() if u8 else pr.frame()
+    if adaptive is not None or passes is not None:
         if out is None:
             return got
         if out.shape != got.shape or out.dtype != got.dtype:
@@ -411,5 +544,5 @@ if __name__ == "__main__":  # python -m rtclj.raytracing [spp] [depth]
         sys.exit(str(e))
 
 
-__all__ = ["hittables", "REFERENCE_CAMERA", "image_height", "flatten", "flatten64", "Scene", "camera", "render", "Progressive", "pass_sizes",
+__all__ = ["hittables", "REFERENCE_CAMERA", "image_height", "flatten", "flatten64", "Scene", "camera", "render", "Progressive", "Adaptive", "pass_sizes",
            "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]
