@@ -494,6 +494,96 @@ int rt_adapt_eval_host(const uint64_t* sums0, const uint64_t* sums1, int width, 
 int rt_adapt_resolve_host(const uint64_t* sums0, const uint64_t* sums1, const uint32_t* counts, int width,
                           int rows, int flags, float* out);
 
+/* ---- first-hit features: albedo, normal, depth and coverage -----------------
+ * Noise-free per-pixel guides for a denoiser or a compositor: what the first
+ * surface a camera ray meets looks like.  For pixel (i, j) and sample index k
+ * a feature launch traces exactly the camera ray rt_launch traces for that
+ * (seed, pixel, sample) -- the same RNG stream, jitter, defocus draw (loop-free
+ * or by rejection, RT_FLAG_REJECTION_SAMPLERS) and d = s - o
+ * (raytracing.clj:144-151) -- runs one hit-anything on it (raytracing.clj:33-43,
+ * the kernel's fp32 body test and first-wins tie rule) and adds the result to
+ * integer sums, so that passes, shards and streams combine exactly, in any
+ * order, as they do for an rt_accum.  Per sample:
+ *   hit:  albedo = the body's ::attenuation (material.clj:13-46): its rgb for
+ *         RT_LAMBERTIAN and RT_METAL, (1, 1, 1) for RT_DIELECTRIC (:46),
+ *         (0, 0, 0) for RT_NONE; normal = the hit record's face-corrected unit
+ *         normal (hittable.clj:24-31, hit.clj:14-15: (P - C) / r, turned
+ *         against the ray, then scaled by 1 / its own length: the fp32 root
+ *         leaves P off the surface, and (P - C) / r up to 1e-3 off unit
+ *         length for a small distant body); t = the Euclidean distance from
+ *         the ray's origin
+ *         (the reference's ::hit/t times |d|);
+ *   miss: albedo = the sky colour of that ray (raytracing.clj:55-58), normal 0,
+ *         no distance, not counted as a hit.
+ * Kept per pixel: six 64-bit sums in 2^-24 units (albedo rgb, each sample
+ * clamped as a colour is, RT_MAX_SPP; normal xyz, signed, toward zero), a
+ * uint32 count of hit samples, and the MINIMUM of t over the hit samples
+ * (+inf: none) -- the nearest surface in the pixel, not a mean distance: a
+ * minimum is exact in any order at every scene scale.  The resolved normal is
+ * the mean over all samples with misses as zero and is NOT re-normalised: its
+ * length falls below 1 where a pixel sees several surfaces or the sky.
+ * RT_FLAG_REALM is accepted and changes nothing (both namespaces share the
+ * camera and the sphere), RT_FLAG_STREAMED likewise; max_depth is not read.
+ *
+ * rt_feat_create (raytracing.clj:141-155, the loop's state): empty feature
+ * buffers for frames of `shape` (read and checked as rt_accum_create does) on
+ * ds's device, cleared (depth +inf).  It holds no reference to ds. */
+#define RT_FEAT_CHANNELS 8
+typedef struct rt_feat rt_feat;
+int rt_feat_create(const rt_dscene* ds, const rt_params* shape, rt_feat** out);
+int rt_feat_free(rt_feat* f);
+/* raytracing.clj:141-155, the loop's start: enqueue sums = 0, hits = 0,
+ * depth = +inf on hip_stream; the count is 0 from the call on. */
+int rt_feat_clear(rt_feat* f, void* hip_stream);
+/* raytracing.clj:141-155, the loop's counter: samples per pixel of the passes
+ * enqueued so far. */
+int64_t rt_feat_samples(const rt_feat* f);
+/* One pass (raytracing.clj:144-151, :33-43, hittable.clj:7-31,
+ * material.clj:13-46).  Asynchronous: trace the first segment of p->spp
+ * samples per pixel, indices p->sample_begin ..., and add them to f by
+ * atomics: passes from several streams into one rt_feat are legal and give the
+ * same contents.  Interleaved row selections as rt_launch_accum.  d_counters:
+ * NULL or device u64[2] += {samples traced, samples traced} (one segment per
+ * sample).  rt_set_variant chooses where the kernel reads the bodies (5: the
+ * linear scan; 12: the BVH in global memory; otherwise the BVH in LDS where it
+ * fits): the contents never depend on it.  The stream's tile-cost record
+ * (rt_set_schedule) is neither read nor written.  RT_E_ARG when p's width,
+ * height or row selection differ from f's, when ds is on another device, or
+ * when the count would pass 2^32 - 1; f is unchanged then. */
+int rt_launch_feat(const rt_dscene* ds, const rt_camera* c, const rt_params* p, rt_feat* f,
+                   uint64_t* d_counters, void* hip_stream);
+/* compute-pixel's accum / spp for the features (raytracing.clj:155).
+ * Asynchronous, non-destructive: d_out (device, rt_rows_out x width x
+ * RT_FEAT_CHANNELS floats) = per pixel, with nf = RN(float(max(count, 1))):
+ *   [0..2] albedo rgb  RN(float(sum)) * 2^-24 / nf  (rt_launch's conversion)
+ *   [3..5] normal xyz  the same from the signed sums
+ *   [6]    depth       the minimum, or +inf
+ *   [7]    coverage    RN(float(hits)) / nf */
+int rt_feat_resolve(const rt_feat* f, float* d_out, void* hip_stream);
+/* raytracing.clj:141-155's accum, raw: host_sums (rt_rows_out x width x 6
+ * int64: albedo rgb, normal xyz), host_hits and host_depth (rt_rows_out x
+ * width each) copied behind hip_stream's work; returns when they are there. */
+int rt_feat_read(const rt_feat* f, int64_t* host_sums, uint32_t* host_hits, float* host_depth, void* hip_stream);
+/* The inverse (raytracing.clj:141-155): merge rt_feat_read's arrays of another
+ * rt_feat of the same shape (a rank's sample stripe) and its `samples` per
+ * pixel into f, on hip_stream, atomically as a pass does -- sums and hit
+ * counts added, the depth by minimum; returns when they are merged.  RT_E_ARG
+ * when the count would pass 2^32 - 1 or a depth is not a positive distance
+ * or +inf; f is unchanged then. */
+int rt_feat_add(rt_feat* f, const int64_t* host_sums, const uint32_t* host_hits, const float* host_depth,
+                int64_t samples, void* hip_stream);
+/* rt_feat_resolve's conversion on the host, in plain C++ (no device;
+ * raytracing.clj:155): out (n_px x RT_FEAT_CHANNELS) from rt_feat_read's
+ * arrays holding `samples` per pixel (0 .. 2^32 - 1).  The albedo sums are
+ * read as unsigned. */
+int rt_feat_resolve_host(const int64_t* sums, const uint32_t* hits, const float* depth, size_t n_px,
+                         int64_t samples, float* out);
+/* The feature kernel a launch on ds would run under the current selector
+ * (diagnostic; raytracing.clj:33-43's scan as it is run): out4 = {workgroups
+ * per CU, VGPRs per lane, LDS bytes per workgroup, the bodies' source: 0 = BVH
+ * in LDS, 1 = BVH in global memory, 2 = linear scan}. */
+int rt_feat_occupancy(const rt_dscene* ds, int* out4);
+
 /* Asynchronous: enqueue rt_quantize on hip_stream's device for n channels
  * already in HBM (d_lin: n floats, d_out: n bytes, device pointers): the same
  * bytes as rt_quantize for every float (NaN, infinities and denormals

@@ -30,6 +30,7 @@
 #include <thread>
 #include <vector>
 
+#include "first_hit.h"
 #include "rt_internal.h"
 
 namespace rtclj {
@@ -242,6 +243,22 @@ extern "C" int rt_adapt_resolve_host(const uint64_t* sums0, const uint64_t* sums
         out[e] = realm ? tot * (1.0f / nf) : tot / nf;
       }
     }
+  return RT_OK;
+}
+
+// rt_feat_resolve's conversion on the host (first_hit.h's fh_resolve, the text
+// feat_resolve_kernel runs)
+extern "C" int rt_feat_resolve_host(const int64_t* sums, const uint32_t* hits, const float* depth, size_t n_px,
+                                    int64_t samples, float* out) {
+  clear_error();
+  if ((!sums || !hits || !depth || !out) && n_px) return set_error(RT_E_ARG, "rt_feat_resolve_host: NULL argument");
+  if (samples < 0 || samples > 0xffffffffll) return set_error(RT_E_ARG, "rt_feat_resolve_host: bad samples");
+  const float nf = static_cast<float>(samples > 0 ? samples : 1);
+  for (size_t i = 0; i < n_px; ++i) {
+    long long s[6];
+    for (int c = 0; c < 6; ++c) s[c] = sums[i * 6 + c];
+    rtclj::fh_resolve(s, hits[i], depth[i], nf, out + i * RT_FEAT_CHANNELS);
+  }
   return RT_OK;
 }
 

@@ -16,6 +16,7 @@
 //           [--seed S] [--gpus N] [--out PATH] [--png PATH] [--no-png] [--json]
 //           [--host-quantize] [--rejection-samplers] [--passes K]
 //           [--adaptive TOLQ16 [--step S] [--min-spp A] [--max-spp B]]
+//           [--features STEM]
 // Defaults follow the reference: spp 100, depth 50, width 400, 16:9.
 // --passes K: the spp in K near-equal accumulating passes on device 0
 // (rt_launch_accum into an rt_accum, the sums read back, rt_resolve_sums and
@@ -26,6 +27,12 @@
 // the spp argument); halves and counts are read back, rt_adapt_resolve_host
 // and rt_quantize on the host.  Prints the samples traced and the tiles at
 // the cap; --json carries them ("adaptive").
+// --features STEM: after the render, the first-hit features of the frame's
+// camera rays (rt_feat on device 0, the frame's spp and seed; include/rt.h):
+// STEM.feat.f32 holds the resolved floats (rows x width x 8: albedo rgb,
+// normal xyz, depth = the nearest hit, coverage; row-major, as the host
+// stores them), STEM.albedo.png the albedo through rt_quantize,
+// STEM.normal.png the bytes floor(255 * clamp(0.5 n + 0.5, 0, 1) + 0.5), linear.
 // --json: one more line, a JSON object of where this one-frame process's time
 // went (the device start-up -- the HIP runtime's first rt_device_count, then
 // rt_prepare's context / code object / queue / pageable staging -- on a thread
@@ -52,7 +59,7 @@ int main(int argc, char** argv) {
   long long ad_samples = 0;
   int ad_tiles = 0, ad_cap_tiles = 0, ad_steps = 0;
   unsigned long long seed = 1;
-  std::string scene = "reference", out, png;
+  std::string scene = "reference", out, png, features;
   bool realm = false, json = false, host_quantize = false, no_png = false, rejection = false;
   int pos = 0;
   const auto t_start = std::chrono::steady_clock::now();
@@ -69,7 +76,7 @@ int main(int argc, char** argv) {
   // (a missing option value ends the process before the start-up thread
   // exists: no exit while that thread may be inside the HIP runtime)
   static const char* const kValued[] = {"--scene", "--width", "--seed", "--gpus", "--grid", "--out", "--png", "--passes",
-                                        "--adaptive", "--step", "--min-spp", "--max-spp"};
+                                        "--adaptive", "--step", "--min-spp", "--max-spp", "--features"};
   for (int i = 1; i < argc; ++i) {
     const bool valued = std::any_of(std::begin(kValued), std::end(kValued),
                                     [&](const char* f) { return std::strcmp(argv[i], f) == 0; });
@@ -108,6 +115,7 @@ int main(int argc, char** argv) {
     else if (a == "--step") ad_step = std::atoi(val());
     else if (a == "--min-spp") ad_min = std::atoi(val());
     else if (a == "--max-spp") ad_max = std::atoi(val());
+    else if (a == "--features") features = val();
     else if (a == "--realm") realm = true;
     else if (a == "--rejection-samplers") rejection = true;   // RT_FLAG_REJECTION_SAMPLERS
     else if (a == "--json") json = true;
@@ -273,6 +281,46 @@ int main(int argc, char** argv) {
     return 1;
   }
   const double png_ms = png.empty() ? 0.0 : ms_since(t_p);
+  if (!features.empty()) {
+    // the features of the rays the frame traced (raytracing.clj:144-151, :33-43)
+    const size_t npx = static_cast<size_t>(width) * height;
+    rt_dscene* ds = nullptr;
+    rt_feat* ft = nullptr;
+    std::vector<int64_t> sums(npx * 6);
+    std::vector<uint32_t> hits(npx);
+    std::vector<float> fdepth(npx), feat(npx * RT_FEAT_CHANNELS), alb(npx * 3);
+    std::vector<uint8_t> b8(npx * 3);
+    bool ok = rt_scene_upload(0, &s, &ds) == RT_OK && rt_feat_create(ds, &p, &ft) == RT_OK &&
+              rt_launch_feat(ds, &cam, &p, ft, nullptr, nullptr) == RT_OK &&
+              rt_feat_read(ft, sums.data(), hits.data(), fdepth.data(), nullptr) == RT_OK &&
+              rt_feat_resolve_host(sums.data(), hits.data(), fdepth.data(), npx, rt_feat_samples(ft), feat.data()) == RT_OK;
+    if (ok) {
+      FILE* f = std::fopen((features + ".feat.f32").c_str(), "wb");
+      ok = f && std::fwrite(feat.data(), sizeof(float), feat.size(), f) == feat.size();
+      if (f) ok = std::fclose(f) == 0 && ok;
+      if (!ok) std::fprintf(stderr, "cannot write %s.feat.f32\n", features.c_str());
+    } else {
+      std::fprintf(stderr, "--features failed: %s\n", rt_last_error());
+    }
+    if (ok) {
+      for (size_t i = 0; i < npx; ++i)
+        for (int c = 0; c < 3; ++c) alb[3 * i + c] = feat[RT_FEAT_CHANNELS * i + c];
+      ok = rt_quantize(alb.data(), b8.data(), b8.size()) == RT_OK &&
+           rt_write_png((features + ".albedo.png").c_str(), b8.data(), width, height) == RT_OK;
+      for (size_t i = 0; i < npx; ++i)
+        for (int c = 0; c < 3; ++c) {
+          const double v = 0.5 * static_cast<double>(feat[RT_FEAT_CHANNELS * i + 3 + c]) + 0.5;   // (the product is exact)
+          const double cl = v > 0.0 ? (v < 1.0 ? v : 1.0) : 0.0;
+          const double sc = cl * 255.0;
+          b8[3 * i + c] = static_cast<uint8_t>(std::floor(sc + 0.5));
+        }
+      ok = ok && rt_write_png((features + ".normal.png").c_str(), b8.data(), width, height) == RT_OK;
+      if (!ok) std::fprintf(stderr, "%s\n", rt_last_error());
+    }
+    rt_feat_free(ft);
+    rt_scene_free(ds);
+    if (!ok) return 1;
+  }
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   std::printf("\"Elapsed time: %.3f msecs\"\n", ms);  // (time ...) (:99)
   if (ad_tol >= 0)

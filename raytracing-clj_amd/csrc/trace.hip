@@ -5,8 +5,12 @@
 // evaluation / resolve kernels, and rt_scene_upload / rt_launch /
 // rt_launch_accum / rt_adapt_step and the rt_accum and rt_adapt entries.  The A/B scans, the
 // direction-coherent waves and the statistics builds live in trace_diag.hip
-// (librtclj_diag.so only).  DESIGN.md §3.
+// (librtclj_diag.so only).  DESIGN.md §3.  The first-hit feature pass
+// (first_hit.h: feat_kernel, feat_resolve_kernel) and the rt_feat entries are
+// here too.
 #include "trace_kernel.h"
+#define RT_FIRST_HIT_KERNEL
+#include "first_hit.h"
 
 #include <algorithm>
 #include <chrono>
@@ -1971,6 +1975,275 @@ extern "C" int rt_adapt_read(const rt_adapt* ad, uint64_t* host_sums0, uint64_t*
   HIP_TRY(hipMemcpyAsync(host_sums0, ad->h[0], ad->n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipMemcpyAsync(host_sums1, ad->h[1], ad->n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
+  return RT_OK;
+}
+
+// ---- first-hit features: albedo, normal, depth, coverage (rt.h, first_hit.h) ----
+// Per pixel six 64-bit sums (albedo rgb, normal xyz, 2^-24 units), a u32 hit
+// count and the nearest hit distance as float bits, on the scene's device; the
+// samples per pixel they hold on the host side, as rt_accum keeps them.
+struct rt_feat {
+  int device = 0;
+  rt_params shape{};   // width, height and the row selection (row_tile resolved)
+  size_t n_px = 0;     // rows_out x width
+  unsigned long long* sums = nullptr;   // n_px x 6
+  unsigned* hits = nullptr;             // n_px
+  unsigned* depth = nullptr;            // n_px, float bits (+inf: no hit yet)
+  mutable std::mutex mu;
+  int64_t samples = 0;
+};
+
+// Where a feature launch on ds takes its bodies from, classed as
+// resolve_variant classes the path kernel's variants: the selector's scan
+// variants (5, the diagnostic 1-10) and a tree too deep for the stack give the
+// linear scan; 12, or a tree image beyond the LDS budget, the tree in global
+// memory; everything else the tree in LDS.  The tree is the 4-body-leaf one
+// (tree[1]): half the nodes of the 2-body tree, and int body indices (the
+// 8-body tree's are u16).  Budget: blob + stack rows within 160 KB / 5 less
+// the kernel's 3.6 KB of static LDS, five workgroups per CU.
+constexpr size_t kFeatLdsBudget = 160 * 1024 / 5 - 4096;
+static int feat_stack_rows(const DTree& t) { return t.depth + 1; }
+static size_t feat_stack_bytes(const DTree& t) { return static_cast<size_t>(feat_stack_rows(t)) * kFeatThreads * 2; }
+static int feat_source(const rt_dscene& ds, int vsel) {
+  const int v = resolve_variant(ds, vsel);
+  const DTree& t = ds.tree[1];
+  if (v < 11 || t.depth + 2 > kBvhStack) return FEAT_SCAN;
+  if (v == 12 || static_cast<size_t>(t.blob_f4) * 16 + feat_stack_bytes(t) > kFeatLdsBudget) return FEAT_GLOBAL;
+  return FEAT_LDS;
+}
+static const void* feat_fn(int src) {
+  return src == FEAT_LDS      ? reinterpret_cast<const void*>(&feat_kernel<FEAT_LDS>)
+         : src == FEAT_GLOBAL ? reinterpret_cast<const void*>(&feat_kernel<FEAT_GLOBAL>)
+                              : reinterpret_cast<const void*>(&feat_kernel<FEAT_SCAN>);
+}
+static size_t feat_lds(const rt_dscene& ds, int src) {
+  const DTree& t = ds.tree[1];
+  return src == FEAT_SCAN ? 0 : feat_stack_bytes(t) + (src == FEAT_LDS ? static_cast<size_t>(t.blob_f4) * 16 : 0);
+}
+
+// words of a feature buffer set to v (fill_kernel takes any word: +inf's bits)
+static hipError_t feat_fill(void* p, uint32_t v, size_t words, hipStream_t stream) {
+  uint32_t* w = static_cast<uint32_t*>(p);
+  size_t n = words;
+  const size_t blocks = std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 2048));
+  void* args[] = {&w, &v, &n};
+  return hipLaunchKernel(reinterpret_cast<const void*>(&fill_kernel), dim3(static_cast<unsigned>(blocks)), dim3(256),
+                         args, 0, stream);
+}
+static hipError_t feat_reset(rt_feat* f, hipStream_t stream) {
+  hipError_t e = feat_fill(f->sums, 0u, f->n_px * 12, stream);
+  if (e == hipSuccess) e = feat_fill(f->hits, 0u, f->n_px, stream);
+  if (e == hipSuccess) e = feat_fill(f->depth, 0x7f800000u, f->n_px, stream);
+  return e;
+}
+
+extern "C" int rt_feat_create(const rt_dscene* ds, const rt_params* shape, rt_feat** out) {
+  clear_error();
+  if (!ds || !shape || !out) return set_error(RT_E_ARG, "rt_feat_create: NULL argument");
+  *out = nullptr;
+  const int rows = rows_out(*shape);
+  if (shape->width <= 0 || shape->height <= 0 || rows <= 0)
+    return set_error(RT_E_ARG, "rt_feat_create: bad width/height/row selection");
+  HIP_TRY(hipSetDevice(ds->device));
+  rt_feat* f = new rt_feat;
+  f->device = ds->device;
+  f->shape = accum_shape(*shape);
+  f->n_px = static_cast<size_t>(rows) * shape->width;
+  // cleared before the call returns: the first pass may come on any stream
+  hipError_t e = hipMalloc(&f->sums, f->n_px * 6 * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMalloc(&f->hits, f->n_px * sizeof(unsigned));
+  if (e == hipSuccess) e = hipMalloc(&f->depth, f->n_px * sizeof(unsigned));
+  if (e == hipSuccess) e = feat_reset(f, nullptr);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess) {
+    rt_feat_free(f);
+    return hip_fail(e, "rt_feat_create");
+  }
+  *out = f;
+  return RT_OK;
+}
+
+extern "C" int rt_feat_free(rt_feat* f) {
+  if (!f) return RT_OK;
+  (void)hipSetDevice(f->device);
+  if (f->sums) (void)hipFree(f->sums);
+  if (f->hits) (void)hipFree(f->hits);
+  if (f->depth) (void)hipFree(f->depth);
+  delete f;
+  return RT_OK;
+}
+
+extern "C" int rt_feat_clear(rt_feat* f, void* hip_stream) {
+  clear_error();
+  if (!f) return set_error(RT_E_ARG, "rt_feat_clear: NULL argument");
+  std::lock_guard<std::mutex> lk(f->mu);
+  HIP_TRY(hipSetDevice(f->device));
+  HIP_TRY(feat_reset(f, static_cast<hipStream_t>(hip_stream)));
+  f->samples = 0;
+  return RT_OK;
+}
+
+extern "C" int64_t rt_feat_samples(const rt_feat* f) {
+  if (!f) return 0;
+  std::lock_guard<std::mutex> lk(f->mu);
+  return f->samples;
+}
+
+extern "C" int rt_launch_feat(const rt_dscene* ds, const rt_camera* c, const rt_params* p, rt_feat* f,
+                              uint64_t* d_counters, void* hip_stream) {
+  clear_error();
+  if (!ds || !c || !p || !f) return set_error(RT_E_ARG, "rt_launch_feat: NULL argument");
+  if (p->width <= 0 || p->height <= 0 || p->spp < 0 || p->spp > RT_MAX_SPP ||
+      (p->flags & ~(RT_FLAG_REALM | RT_FLAG_STREAMED | RT_FLAG_REJECTION_SAMPLERS)) != 0)
+    return set_error(RT_E_ARG, "rt_launch_feat: bad width/height/spp/flags");
+  if (ds->device != f->device)
+    return set_error(RT_E_ARG, "rt_launch_feat: the scene is on device " + std::to_string(ds->device) +
+                                   ", the feature buffers on device " + std::to_string(f->device));
+  if (!same_shape(accum_shape(*p), f->shape))
+    return set_error(RT_E_ARG, "rt_launch_feat: width/height/row selection differ from the feature buffers'");
+  std::lock_guard<std::mutex> lk(f->mu);
+  if (p->spp > 0 && f->samples + p->spp > kAccumMaxSamples)
+    return set_error(RT_E_ARG, "rt_launch_feat: more than 2^32 - 1 samples per pixel");
+  if (p->spp == 0) return RT_OK;
+  const int rows = rows_out(*p);
+  HIP_TRY(hipSetDevice(ds->device));
+  const int src = feat_source(*ds, g_variant.load());
+  const DTree& tr = ds->tree[1];
+  FeatArgs a{};
+  a.geo = ds->geo;
+  a.sph = ds->sph;
+  a.mat = ds->mat;
+  a.kind = ds->kind;
+  a.blob = tr.blob;
+  a.blob_f4 = tr.blob_f4;
+  a.off_pairs = tr.off_pairs;
+  a.off_pidx = tr.off_pidx;
+  a.leaf_pairs = 2;
+  a.big_pair0 = tr.big_pair0;
+  a.n_big_leaves = tr.n_big_leaves;
+  a.ref_mul = 1;   // (rt_scene_upload made the 4-body tree's inner refs byte offsets)
+  for (int k = 0; k < 3; ++k) a.bvh_c[k] = tr.c[k];
+  a.bvh_r = tr.r;
+  a.bvh_c0 = tr.c0;
+  std::memcpy(a.cam + 0, c->center, 12);
+  std::memcpy(a.cam + 3, c->p00, 12);
+  std::memcpy(a.cam + 6, c->du, 12);
+  std::memcpy(a.cam + 9, c->dv, 12);
+  std::memcpy(a.cam + 12, c->disk_u, 12);
+  std::memcpy(a.cam + 15, c->disk_v, 12);
+  a.defocus = c->defocus ? 1 : 0;
+  a.sampler = (p->flags & RT_FLAG_REJECTION_SAMPLERS) ? 0 : (RT_SAMPLER_SPHERE | RT_SAMPLER_DISK);
+  a.n = ds->n;
+  a.width = p->width;
+  a.rows_out = rows;
+  a.row_begin = p->row_begin;
+  a.row_tile = p->row_tile > 0 ? p->row_tile : 8;
+  a.tile_first = p->tile_first;
+  a.tile_step = p->tile_step;
+  a.tiles_x = (p->width + kTile - 1) / kTile;
+  a.spp = p->spp;
+  a.sample_begin = p->sample_begin;
+  a.key = seed_key(p->seed);
+  a.sums = f->sums;
+  a.hits = f->hits;
+  a.depth = f->depth;
+  a.counters = reinterpret_cast<unsigned long long*>(d_counters);
+  const int gy = (rows + kTile - 1) / kTile;
+  void* args[] = {&a};
+  HIP_TRY(hipLaunchKernel(feat_fn(src), dim3(static_cast<unsigned>(a.tiles_x * gy)), dim3(kFeatThreads), args,
+                          feat_lds(*ds, src), static_cast<hipStream_t>(hip_stream)));
+  f->samples += p->spp;
+  return RT_OK;
+}
+
+extern "C" int rt_feat_resolve(const rt_feat* f, float* d_out, void* hip_stream) {
+  clear_error();
+  if (!f || !d_out) return set_error(RT_E_ARG, "rt_feat_resolve: NULL argument");
+  int64_t count;
+  {
+    std::lock_guard<std::mutex> lk(f->mu);
+    count = f->samples;
+  }
+  HIP_TRY(hipSetDevice(f->device));
+  const unsigned long long* sums = f->sums;
+  const unsigned *hits = f->hits, *depth = f->depth;
+  size_t n_px = f->n_px;
+  float nf = static_cast<float>(count > 0 ? count : 1);   // RN(float(n))
+  const size_t blocks = std::max<size_t>(1, std::min<size_t>((n_px + 255) / 256, 4096));
+  void* args[] = {&sums, &hits, &depth, &n_px, &nf, &d_out};
+  HIP_TRY(hipLaunchKernel(reinterpret_cast<const void*>(&feat_resolve_kernel), dim3(static_cast<unsigned>(blocks)),
+                          dim3(256), args, 0, static_cast<hipStream_t>(hip_stream)));
+  return RT_OK;
+}
+
+extern "C" int rt_feat_read(const rt_feat* f, int64_t* host_sums, uint32_t* host_hits, float* host_depth,
+                            void* hip_stream) {
+  clear_error();
+  if (!f || !host_sums || !host_hits || !host_depth) return set_error(RT_E_ARG, "rt_feat_read: NULL argument");
+  HIP_TRY(hipSetDevice(f->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  HIP_TRY(hipMemcpyAsync(host_sums, f->sums, f->n_px * 6 * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(host_hits, f->hits, f->n_px * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(host_depth, f->depth, f->n_px * sizeof(float), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return RT_OK;
+}
+
+extern "C" int rt_feat_add(rt_feat* f, const int64_t* host_sums, const uint32_t* host_hits, const float* host_depth,
+                           int64_t samples, void* hip_stream) {
+  clear_error();
+  if (!f || !host_sums || !host_hits || !host_depth) return set_error(RT_E_ARG, "rt_feat_add: NULL argument");
+  std::lock_guard<std::mutex> lk(f->mu);
+  if (samples < 0 || samples > kAccumMaxSamples || f->samples + samples > kAccumMaxSamples)
+    return set_error(RT_E_ARG, "rt_feat_add: samples negative, or more than 2^32 - 1 per pixel in all");
+  for (size_t i = 0; i < f->n_px; ++i)   // (a depth is a positive distance or +inf: the minimum runs on the bits)
+    if (!(host_depth[i] > 0.0f)) return set_error(RT_E_ARG, "rt_feat_add: a depth is not a positive distance or +inf");
+  HIP_TRY(hipSetDevice(f->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  // one staging block: sums | hits | depth (freed when the call returns)
+  const size_t sb = f->n_px * 6 * sizeof(uint64_t), wb = f->n_px * sizeof(uint32_t);
+  char* stage = nullptr;
+  HIP_TRY(hipMalloc(&stage, sb + 2 * wb));
+  hipError_t e = hipMemcpyAsync(stage, host_sums, sb, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(stage + sb, host_hits, wb, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(stage + sb + wb, host_depth, wb, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) {
+    unsigned long long* sums = f->sums;
+    unsigned *hits = f->hits, *depth = f->depth;
+    const unsigned long long* as = reinterpret_cast<const unsigned long long*>(stage);
+    const unsigned* ah = reinterpret_cast<const unsigned*>(stage + sb);
+    const unsigned* ad = reinterpret_cast<const unsigned*>(stage + sb + wb);
+    size_t n_px = f->n_px;
+    const size_t blocks = std::max<size_t>(1, std::min<size_t>((n_px + 255) / 256, 4096));
+    void* args[] = {&sums, &hits, &depth, &as, &ah, &ad, &n_px};
+    e = hipLaunchKernel(reinterpret_cast<const void*>(&feat_add_kernel), dim3(static_cast<unsigned>(blocks)), dim3(256),
+                        args, 0, stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  (void)hipFree(stage);
+  if (e != hipSuccess) return hip_fail(e, "rt_feat_add");
+  f->samples += samples;
+  return RT_OK;
+}
+
+// The feature kernel a launch on ds would run under the current selector
+// (diagnostic, tools/feat_time.py): out4 = {workgroups per CU, VGPRs per lane,
+// LDS bytes per workgroup, the bodies' source: 0 tree in LDS, 1 tree in global
+// memory, 2 linear scan}.
+extern "C" int rt_feat_occupancy(const rt_dscene* ds, int* out4) {
+  clear_error();
+  if (!ds || !out4) return set_error(RT_E_ARG, "rt_feat_occupancy: NULL argument");
+  HIP_TRY(hipSetDevice(ds->device));
+  const int src = feat_source(*ds, g_variant.load());
+  const size_t lds = feat_lds(*ds, src);
+  int blocks = 0;
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, feat_fn(src), kFeatThreads, lds));
+  hipFuncAttributes fa{};
+  HIP_TRY(hipFuncGetAttributes(&fa, feat_fn(src)));
+  out4[0] = blocks;
+  out4[1] = fa.numRegs;
+  out4[2] = static_cast<int>(lds + fa.sharedSizeBytes);
+  out4[3] = src;
   return RT_OK;
 }
 

@@ -127,6 +127,20 @@ SIGNATURES = {
                                      C.POINTER(C.c_uint8)]),
     "rt_adapt_resolve_host": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_int,
                                         C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "rt_feat_create": (C.c_int, [C.c_void_p, C.POINTER(rt_params), C.POINTER(C.c_void_p)]),
+    "rt_feat_free": (C.c_int, [C.c_void_p]),
+    "rt_feat_clear": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_feat_samples": (C.c_int64, [C.c_void_p]),
+    "rt_launch_feat": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
+    "rt_feat_resolve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_feat_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_float),
+                               C.c_void_p]),
+    "rt_feat_add": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_float),
+                              C.c_int64, C.c_void_p]),
+    "rt_feat_resolve_host": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_size_t,
+                                       C.c_int64, C.POINTER(C.c_float)]),
+    "rt_feat_occupancy": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rt_quantize_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rt_set_variant": (C.c_int, [C.c_int]),
     "rt_resolve_variant": (C.c_int, [C.c_void_p]),
@@ -149,7 +163,11 @@ ADDITIVE = {"rt_prepare", "rt_render_u8", "rt_quantize_device", "rt_render_submi
             "rt_accum_samples", "rt_launch_accum", "rt_accum_resolve", "rt_accum_resolve_u8", "rt_accum_read",
             "rt_accum_add", "rt_resolve_sums", "rt_adapt_create", "rt_adapt_free", "rt_adapt_clear", "rt_adapt_step",
             "rt_adapt_active", "rt_adapt_samples", "rt_adapt_resolve", "rt_adapt_resolve_u8", "rt_adapt_counts",
-            "rt_adapt_read", "rt_adapt_eval_host", "rt_adapt_resolve_host"}
+            "rt_adapt_read", "rt_adapt_eval_host", "rt_adapt_resolve_host", "rt_feat_create", "rt_feat_free",
+            "rt_feat_clear", "rt_feat_samples", "rt_launch_feat", "rt_feat_resolve", "rt_feat_read",
+            "rt_feat_add", "rt_feat_resolve_host", "rt_feat_occupancy"}
+
+RT_FEAT_CHANNELS = 8   # rt_feat_resolve's floats per pixel: albedo rgb, normal xyz, depth, coverage
 
 
 def load(path: Path) -> C.CDLL:
@@ -210,6 +228,10 @@ def u32ptr(a):
 
 def u64ptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def i64ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
 
 
 def dptr(a):

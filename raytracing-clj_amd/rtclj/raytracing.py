@@ -24,8 +24,8 @@ from fractions import Fraction
 import numpy as np
 
 from . import hittable, material
-from ._lib import (RT_DIELECTRIC, RT_LAMBERTIAN, RT_METAL, RT_NONE, RTError, check, dptr, fptr, iptr, lib,
-                   rt_adapt_opts, rt_camera, rt_params, rt_scene, rt_stats, u8ptr, u32ptr, u64ptr)
+from ._lib import (RT_DIELECTRIC, RT_FEAT_CHANNELS, RT_LAMBERTIAN, RT_METAL, RT_NONE, RTError, check, dptr, fptr,
+                   i64ptr, iptr, lib, rt_adapt_opts, rt_camera, rt_params, rt_scene, rt_stats, u8ptr, u32ptr, u64ptr)
 
 # ---- scene (raytracing.clj:63-78) --------------------------------------------
 hittables = [
@@ -356,6 +356,126 @@ class Adaptive:
         if getattr(self, "_ad", None):
             self._dll.rt_adapt_free(self._ad)
             self._ad = C.c_void_p()
+        if getattr(self, "_ds", None):
+            self._dll.rt_scene_free(self._ds)
+            self._ds = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+class Features:
+    """First-hit feature buffers (rt_feat, include/rt.h): per pixel the albedo,
+    normal, depth and coverage of the first surface the pixel's camera rays
+    meet -- the very rays render() / Progressive trace for the same seed and
+    sample indices -- accumulated pass by pass as exact integer sums.
+
+        ft = Features(scene, cam, 400, 225, seed=1)
+        ft.add(16)
+        f = ft.frame()          # (rows, width, 8): albedo rgb, normal xyz, depth, coverage
+
+    Two choices to know: depth is the NEAREST hit of the pixel's samples (+inf
+    where none hit), not a mean; the normal is the mean over all samples with
+    misses as zero, not re-normalised.  add() advances sample_begin itself;
+    frame() and raw() wait for the passes enqueued on `stream`."""
+
+    def __init__(self, scene, cam: rt_camera, width: int, height: int, seed: int = 1, flags: int = 0, rows=None,
+                 row_tile: int = 8, tile_first: int = 0, tile_step: int = 0, sample_begin: int = 0,
+                 device: int = 0, stream=None, library=None):
+        self._dll = library if library is not None else lib
+        self.scene = scene if isinstance(scene, Scene) else Scene.from_bodies(scene)
+        self.cam = cam
+        r0, r1 = (0, height) if rows is None else rows
+        self._p = rt_params(width=width, height=height, row_begin=r0, row_end=r1, spp=0, max_depth=1, seed=seed,
+                            sample_begin=sample_begin, row_tile=row_tile, tile_first=tile_first,
+                            tile_step=tile_step, flags=flags)
+        self._first, self._next = sample_begin, sample_begin
+        self._stream = C.c_void_p(stream) if stream else None
+        self._ds, self._ft = C.c_void_p(), C.c_void_p()
+        self._check(self._dll.rt_scene_upload(int(device), C.byref(self.scene.c), C.byref(self._ds)))
+        try:
+            self._check(self._dll.rt_feat_create(self._ds, C.byref(self._p), C.byref(self._ft)))
+        except RTError:
+            self.close()
+            raise
+        self.shape = (self._dll.rt_rows_out(C.byref(self._p)), width, RT_FEAT_CHANNELS)
+
+    def _check(self, code):
+        if code < 0:
+            raise RTError(code, self._dll.rt_last_error().decode(errors="replace"))
+        return code
+
+    @property
+    def samples(self) -> int:
+        """Samples per pixel added so far (rt_feat_samples)."""
+        return int(self._dll.rt_feat_samples(self._ft))
+
+    def add(self, spp: int) -> int:
+        """Enqueue one pass of `spp` more samples per pixel (rt_launch_feat);
+        returns the new count."""
+        if spp < 0:
+            raise ValueError("Features.add: spp < 0")
+        self._p.spp = int(spp)
+        self._p.sample_begin = self._next
+        self._check(self._dll.rt_launch_feat(self._ds, C.byref(self.cam), C.byref(self._p), self._ft, None,
+                                             self._stream))
+        self._next += int(spp)
+        return self.samples
+
+    def raw(self):
+        """(sums int64 (rows, width, 6), hits uint32 (rows, width), depth
+        float32 (rows, width)): the integer sums in 2^-24 units (albedo rgb,
+        normal xyz), the hit counts and the nearest distances (rt_feat_read)."""
+        rows, width, _ = self.shape
+        sums = np.empty((rows, width, 6), np.int64)
+        hits = np.empty((rows, width), np.uint32)
+        depth = np.empty((rows, width), np.float32)
+        self._check(self._dll.rt_feat_read(self._ft, i64ptr(sums), u32ptr(hits), fptr(depth), self._stream))
+        return sums, hits, depth
+
+    def add_raw(self, sums, hits, depth, samples: int) -> int:
+        """Merge another Features' raw() and its sample count (rt_feat_add):
+        sums and hits added, depth by minimum."""
+        rows, width, _ = self.shape
+        sums = np.ascontiguousarray(sums, np.int64)
+        hits = np.ascontiguousarray(hits, np.uint32)
+        depth = np.ascontiguousarray(depth, np.float32)
+        if sums.shape != (rows, width, 6) or hits.shape != (rows, width) or depth.shape != (rows, width):
+            raise ValueError(f"Features.add_raw: arrays must be ({rows}, {width}[, 6])")
+        self._check(self._dll.rt_feat_add(self._ft, i64ptr(sums), u32ptr(hits), fptr(depth), int(samples),
+                                          self._stream))
+        return self.samples
+
+    def frame(self) -> np.ndarray:
+        """The features so far, float32 (rows, width, 8): raw() converted by
+        rt_feat_resolve_host, whose bits are rt_feat_resolve's."""
+        sums, hits, depth = self.raw()
+        out = np.empty(self.shape, np.float32)
+        self._check(self._dll.rt_feat_resolve_host(i64ptr(sums), u32ptr(hits), fptr(depth), hits.size, self.samples,
+                                                   fptr(out)))
+        return out
+
+    def resolve_into(self, d_out: int) -> None:
+        """Enqueue the conversion into a device buffer the caller owns (its
+        address; float32 of `shape`): rt_feat_resolve on the stream."""
+        self._check(self._dll.rt_feat_resolve(self._ft, C.c_void_p(d_out), self._stream))
+
+    def clear(self) -> None:
+        """Back to no samples (rt_feat_clear); the next add() starts at the
+        first sample index again."""
+        self._check(self._dll.rt_feat_clear(self._ft, self._stream))
+        self._next = self._first
+
+    def close(self) -> None:
+        if getattr(self, "_ft", None):
+            self._dll.rt_feat_free(self._ft)
+            self._ft = C.c_void_p()
         if getattr(self, "_ds", None):
             self._dll.rt_scene_free(self._ds)
             self._ds = C.c_void_p()
