@@ -7,10 +7,14 @@
 // direction-coherent waves and the statistics builds live in trace_diag.hip
 // (librtclj_diag.so only).  DESIGN.md §3.  The first-hit feature pass
 // (first_hit.h: feat_kernel, feat_resolve_kernel) and the rt_feat entries are
-// here too.
+// here too.  Which variant a launch runs and the LDS it needs
+// is variant_policy.h's (pure functions, checked on the CPU); the device
+// buffers the host side owns are dev_buf.h's DevBuf.
 #include "trace_kernel.h"
 #define RT_FIRST_HIT_KERNEL
 #include "first_hit.h"
+#include "variant_policy.h"
+#include "dev_buf.h"
 
 #include <algorithm>
 #include <chrono>
@@ -24,6 +28,7 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace rtclj {
@@ -420,68 +425,56 @@ __global__ __launch_bounds__(1024) void plan_kernel(const unsigned* __restrict__
 }
 
 // ------------------------------------------------------------- host ------
-// Kernel variants (rt_set_variant).  The product library carries the default
-// traversal and its fallbacks:
-//   22 BVH in LDS, 4-body leaves, compact image (u8 node-index stack, u32
-//      pixel sums with counted wraps, 8-byte pixel table): seven workgroups
-//      per CU -- the default where spp < 65536, albedos lie in [-1, 1], the
-//      tree has <= 256 nodes and the frame is at most 65536 pixels wide and high
-//   16 the same walk in the full image (u16 stack of node addresses, u64 sums)
-//   26 22's compact image in 16-wave workgroups (one tree image per 16
-//      waves, 64 VGPRs: 8 waves per SIMD): the default for scenes whose
-//      4-body image is too big for 22 (C4), where 22 applies and two fit a CU
-//   24 the same in 8-wave workgroups: where three of those fit and not two of 26's
-//   28 22 on 8 x 4-pixel pools (whole pools for launches of few 8 x 8 tiles
-//      instead of sample splits: measured slower, selected only explicitly
-//      or by RTCLJ_TH4)
-//   18 BVH in LDS, 8-body leaves (large scenes where 24 does not fit)
-//   12 BVH (2-body leaves) read from global memory: a tree too big for LDS
-//    5 linear scan, grouped, table through the scalar cache: a tree too deep
-//    0 = default (22 where it applies, else 16; 26, 24, else 18, when the 4-body tree's LDS image is large)
-// The diagnostic library (lib/librtclj_diag.so) adds, from trace_diag.hip, the
-// A/B variants -- 1, 2 simple scan (LDS, scalar cache), 4 grouped scan in LDS
-// (north_star's LDS-staged scan), 8, 9 packed pairs, 11 BVH with 2-body leaves
-// in LDS, 20 / 21 direction-coherent waves (sorted_kernel) -- and the
-// statistics builds 3, 6, 7, 10, 13, 17 (= 16 + stats), 19 (= 18 + stats).
-// Every variant renders the same bits.
-// the tree a traversal variant walks: 0 = 2-body leaves, 1 = 4, 2 = 8
+// Kernel variants (rt_set_variant): variant_policy.h lists them and holds each
+// one's traits; its kernel is looked up here, and in trace_diag.hip for what
+// only the diagnostic library (lib/librtclj_diag.so) carries.
+#ifdef RTCLJ_DIAG
+constexpr bool kDiag = true;
+#else
+constexpr bool kDiag = false;
+#endif
+// the policy's copies of the kernels' shapes, and its table's columns against
+// trace_kernel.h's traits of each row's scan
+static_assert(policy::kTile == kTile && policy::kPoolPx == kPoolPx && policy::kXBytes == kXBytes &&
+                  policy::kFeatThreads == kFeatThreads && static_cast<int>(policy::FEAT_LDS) == FEAT_LDS &&
+                  static_cast<int>(policy::FEAT_GLOBAL) == FEAT_GLOBAL && static_cast<int>(policy::FEAT_SCAN) == FEAT_SCAN,
+              "variant_policy.h: the kernels' shapes");
+constexpr bool traits_agree() {
+  for (const policy::Traits& t : policy::kTraits) {
+    if (t.build == policy::BUILD_NONE) continue;
+    const int walk = t.scan == SCAN_BVHS ? policy::WALK_SORTED : is_bvh_scan(t.scan) ? policy::WALK_BVH : policy::WALK_NONE;
+    if (t.walk != walk || t.tree != scan_tree(t.scan) || t.compact != is_compact_scan(t.scan) ||
+        t.entry_bytes != stack_entry_bytes(t.scan) || policy::variant_rows(t) != (t.th ? t.th : tile_rows(t.scan)) ||
+        (walk == policy::WALK_SORTED && t.threads != kSortThreads))
+      return false;
+  }
+  return true;
+}
+static_assert(traits_agree(), "variant_policy.h: a row's columns against its scan's traits");
+
 const void* trace_kernel_w16();   // trace_w16.hip
-static int variant_tree(int v) { return v >= 20 ? 1 : v >= 18 ? 2 : v >= 16 ? 1 : 0; }
-static const Variant& variant_table(int v) {
-  static const Variant none{nullptr, false, false, 0};
-  static const Variant placeholder{RT_K(SRC_LDS, SCAN_BVHQ, false), true, false, SCAN_BVHQ};   // 0: resolved per scene
-  static const Variant v5{RT_K(SRC_SCALAR, SCAN_GROUP4, false), false, false, SCAN_GROUP4};
-  static const Variant v12{RT_K(SRC_SCALAR, SCAN_BVH, false), false, false, SCAN_BVH};
-  static const Variant v16{RT_K(SRC_LDS, SCAN_BVHQ, false), true, false, SCAN_BVHQ};
-  // (8-wave workgroups: one tree image for twice the waves)
-  static const Variant v18{RT_KW(SRC_LDS, SCAN_BVHO, false, 8), true, false, SCAN_BVHO, 512};
-  static const Variant v22{RT_K(SRC_LDS, SCAN_BVHQ7, false), true, false, SCAN_BVHQ7, 256, 0,
-                           RT_KSW(SRC_LDS, SCAN_BVHQ7, 4, 0)};
-  // (22's image in 8-wave workgroups: one tree image per 8 waves, for trees
-  // too big for 22's 4-wave workgroups)
-  static const Variant v24{RT_KW(SRC_LDS, SCAN_BVHQ7, false, 8), true, false, SCAN_BVHQ7, 512};
-  // (and in 16-wave workgroups, 64 VGPRs: 8 waves per SIMD)
-  // (trace_w16.hip, compiled with its own scheduler flag)
-  static const Variant v26{trace_kernel_w16(), true, false, SCAN_BVHQ7, 1024};
-  // (22 on 8 x 4-pixel pools: whole pools of half the pixels for launches of
-  // few 8 x 8 tiles instead of sample splits; measured slower)
-  static const Variant v28{RT_KWT(SRC_LDS, SCAN_BVHQ7, false, 4, 4), true, false, SCAN_BVHQ7, 256, 4};
+static const policy::Traits& variant_traits(int v) { return policy::traits(v, kDiag); }
+static const void* variant_fn(int v) {
   switch (v) {
-    case 0: return placeholder;
-    case 5: return v5;
-    case 12: return v12;
-    case 16: return v16;
-    case 18: return v18;
-    case 22: return v22;
-    case 24: return v24;
-    case 26: return v26;
-    case 28: return v28;
+    case policy::kDefault: return RT_K(SRC_LDS, SCAN_BVHQ, false);   // (resolved per scene)
+    case policy::kScan: return RT_K(SRC_SCALAR, SCAN_GROUP4, false);
+    case policy::kGlobal: return RT_K(SRC_SCALAR, SCAN_BVH, false);
+    case policy::kFull4: return RT_K(SRC_LDS, SCAN_BVHQ, false);
+    case policy::kLeaf8: return RT_KW(SRC_LDS, SCAN_BVHO, false, 8);
+    case policy::kCompact: return RT_K(SRC_LDS, SCAN_BVHQ7, false);
+    case policy::kCompactW8: return RT_KW(SRC_LDS, SCAN_BVHQ7, false, 8);
+    case policy::kCompactW16: return trace_kernel_w16();   // (trace_w16.hip, compiled with its own scheduler flag)
+    case policy::kCompactTh4: return RT_KWT(SRC_LDS, SCAN_BVHQ7, false, 4, 4);
   }
 #ifdef RTCLJ_DIAG
-  if (const Variant* d = diag_variant(v)) return *d;
+  return diag_kernel(v);
+#else
+  return nullptr;
 #endif
-  return none;
 }
+// the variant's sweep kernel (path export, KArgs::xq), or NULL
+static const void* variant_sweep(int v) { return v == policy::kCompact ? RT_KSW(SRC_LDS, SCAN_BVHQ7, 4, 0) : nullptr; }
+
 // selectors (rt_set_variant / rt_set_schedule): atomics, read once per launch
 static std::atomic<int> g_variant{0};
 // tile schedule: 0 = adaptive longest-first, 1 = dispatch order
@@ -510,6 +503,70 @@ static unsigned long long* g_dbgw[kDbgDevices] = {};
 
 using namespace rtclj;
 
+static int hip_fail(hipError_t e, const char* what) {
+  return set_error(RT_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+#define HIP_TRY(call)                                  \
+  do {                                                 \
+    hipError_t _e = (call);                            \
+    if (_e != hipSuccess) return hip_fail(_e, #call);  \
+  } while (0)
+
+// A launch of one of this file's kernels: each argument converted to the
+// kernel's parameter type at compile time (a narrowing one is an error), then
+// the pointer array hipLaunchKernel takes.
+template <class... P, class... Args>
+static hipError_t enqueue(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args&&... args) {
+  static_assert(sizeof...(P) == sizeof...(Args), "enqueue: the kernel's parameter count");
+  const auto launch = [&](P... v) {
+    void* ptrs[] = {const_cast<void*>(static_cast<const void*>(&v))...};
+    return hipLaunchKernel(reinterpret_cast<const void*>(kernel), grid, block, ptrs, lds, stream);
+  };
+  return launch(P{std::forward<Args>(args)}...);
+}
+// ... of a variant-table kernel: one KArgs / FeatArgs by value
+template <class A>
+static hipError_t enqueue(const void* fn, dim3 grid, dim3 block, size_t lds, hipStream_t stream, A& a) {
+  void* ptrs[] = {&a};
+  return hipLaunchKernel(fn, grid, block, ptrs, lds, stream);
+}
+
+// The library's fill: n words of p set to `word` (fill_kernel takes any
+// word: +inf's bits for the feature depths)
+static hipError_t fill_words(void* p, uint32_t word, size_t n, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  const size_t blocks = std::min<size_t>((n + 255) / 256, 2048);
+  return enqueue(fill_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, static_cast<uint32_t*>(p), word, n);
+}
+template <class T>
+static hipError_t fill_zero(const DevBuf<T>& b, size_t n, hipStream_t stream) {
+  static_assert(sizeof(T) % 4 == 0, "whole words");
+  return fill_words(b.p, 0u, n * (sizeof(T) / 4), stream);
+}
+static const QThr& quantize_table() {
+  static const QThr thr = [] {
+    QThr t;
+    std::memcpy(t.t, quantize_thresholds(), sizeof t.t);
+    return t;
+  }();
+  return thr;
+}
+
+namespace rtclj {
+int fill_async(void* p, int byte_value, size_t bytes, void* stream) {
+  if (bytes % 4 != 0) return hipErrorInvalidValue;   // (every buffer the product fills is whole words)
+  return fill_words(p, static_cast<uint32_t>(byte_value & 0xff) * 0x01010101u, bytes / 4, static_cast<hipStream_t>(stream));
+}
+
+int quantize_launch(const float* d_lin, uint8_t* d_out, size_t n, void* stream) {
+  if (n == 0) return hipSuccess;
+  const size_t blocks = std::min<size_t>((n + 255) / 256, 4096);
+  return enqueue(quantize_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, static_cast<hipStream_t>(stream), d_lin,
+                 d_out, n, quantize_table());
+}
+}  // namespace rtclj
+
 // one BVH on the device: blob = nodes | pairs | pidx (the big bodies' leaves after the tree's)
 struct DTree {
   float4* blob;
@@ -529,15 +586,15 @@ struct DTree {
 // stream; a dscene serves up to kSchedStreams streams this way, launches on
 // further streams run unscheduled.
 // The same per-stream entry holds the split tiles' partial sums (rt_launch).
+// Its methods are rt_launch's stages (below, above launch_impl).
 struct ScheduleKey {
   int width, rows, row_begin, row_tile, tile_first, tile_step, gx, gy;
 };
 struct Schedule {
   hipStream_t stream = nullptr;
-  unsigned* cost = nullptr;
-  int* order = nullptr;
-  int cap = 0;          // tiles the buffers hold
-  bool ready = false;   // order[] holds a permutation of key's tiles (stream-ordered)
+  DevBuf<unsigned> cost;   // per tile
+  DevBuf<int> order;       // per tile
+  bool ready = false;      // order[] holds a permutation of key's tiles (stream-ordered)
   // The sort of the last launch's record (order_kernel, and plan_kernel for a
   // planned split) is enqueued at the start of the next launch of the shape
   // on the stream, not behind the trace kernel: a frame's launch ends with
@@ -547,66 +604,65 @@ struct Schedule {
   bool sort_pending = false;
   int sort_plan = -1;
   ScheduleKey key{};
-  unsigned long long* part = nullptr;   // [rows][width][3] pixel sums of split tiles (zero between launches)
-  size_t part_cap = 0;                  // u64 elements
+  DevBuf<unsigned long long> part;   // [rows][width][3] pixel sums of split tiles (zero between launches)
   // a split launch's trace kernel was enqueued but its finalize_kernel (which
   // re-zeroes the sums) was not: the next split launch zeroes them first
   bool part_dirty = false;
   // the stealing state (KArgs word, done, sum, owner, stealc)
-  unsigned long long* word = nullptr;   // per tile
-  unsigned* done = nullptr;             // per tile
-  unsigned long long* sum = nullptr;    // per tile x kPoolPx x 3, zero between uses
-  int steal_cap = 0;                    // tiles those hold
-  int* owner = nullptr;                 // KArgs n_owner entries
-  int owner_cap = 0;
-  unsigned long long* stealc = nullptr; // [helpers that got samples, their first samples] since rt_steal_stats
-  unsigned epoch = 0;                   // launches with sharing on this stream (mod 2^16, 1 .. 65535)
+  DevBuf<unsigned long long> word;     // per tile
+  DevBuf<unsigned> done;               // per tile
+  DevBuf<unsigned long long> sum;      // per tile x kPoolPx x 3, zero between uses
+  DevBuf<int> owner;                   // KArgs n_owner entries
+  DevBuf<unsigned long long> stealc;   // [helpers that got samples, their first samples] since rt_steal_stats
+  unsigned epoch = 0;                  // launches with sharing on this stream (mod 2^16, 1 .. 65535)
   bool epoch_started = false;
-  int2* units = nullptr;                // cost-balanced split plan (plan_kernel) of the next split launch
-  int units_cap = 0;
-  int plan_units = -1;                  // the plan's unit count (-1: none)
+  DevBuf<int2> units;                  // cost-balanced split plan (plan_kernel) of the next split launch
+  int plan_units = -1;                 // the plan's unit count (-1: none)
   // path export (KArgs xq, xq_n): the records of a split launch's exported
-  // paths, and [written, the sweep's claims] (zeroed before each launch)
-  uint4* xq = nullptr;
-  size_t xq_cap = 0;                    // records
-  unsigned* xq_n = nullptr;
+  // paths (four uint4 each), and [written, the sweep's claims] (zeroed before each launch)
+  DevBuf<uint4> xq;
+  DevBuf<unsigned> xq_n;
   unsigned long long xq_launches = 0;   // export launches since rt_export_stats
+
+  bool rekey(const ScheduleKey& k);
+  int sort_record(int n_tiles, int spp);
+  int bind_part(KArgs& a, size_t n_elems);
+  int bind_order(KArgs& a, FillSet& fills, int n_tiles, int spp, int split_units, bool* first_order);
+  int bind_sharing(KArgs& a, FillSet& fills, int n_tiles, int n_units, int slots, bool new_shape, bool first_order,
+                   int64_t* grid);
+  int bind_export(KArgs& a, FillSet& fills, size_t records);
+  int record(int n_tiles, int spp, int plan_units_next);
 };
 constexpr int kSchedStreams = 16;
 struct ScheduleSet {
   std::mutex mu;
   int used = 0;
   Schedule s[kSchedStreams];
-  static void free_entry(Schedule& e) {
-    if (e.cost) (void)hipFree(e.cost);
-    if (e.order) (void)hipFree(e.order);
-    if (e.part) (void)hipFree(e.part);
-    if (e.word) (void)hipFree(e.word);
-    if (e.done) (void)hipFree(e.done);
-    if (e.sum) (void)hipFree(e.sum);
-    if (e.owner) (void)hipFree(e.owner);
-    if (e.stealc) (void)hipFree(e.stealc);
-    if (e.units) (void)hipFree(e.units);
-    if (e.xq) (void)hipFree(e.xq);
-    if (e.xq_n) (void)hipFree(e.xq_n);
-    e = Schedule{};
-  }
   void release() {
-    for (int k = 0; k < used; ++k) free_entry(s[k]);
+    for (int k = 0; k < used; ++k) s[k] = Schedule{};
     used = 0;
   }
   // drop `stream`'s entry (its kernels have finished), keeping the others packed
   void release_stream(hipStream_t stream) {
     for (int k = 0; k < used; ++k)
       if (s[k].stream == stream) {
-        free_entry(s[k]);
-        if (k != used - 1) {
-          s[k] = s[used - 1];
-          s[used - 1] = Schedule{};
-        }
+        if (k != used - 1) s[k] = std::move(s[used - 1]);
+        s[used - 1] = Schedule{};
         --used;
         return;
       }
+  }
+  Schedule* find(hipStream_t stream) {
+    for (int k = 0; k < used; ++k)
+      if (s[k].stream == stream) return &s[k];
+    return nullptr;
+  }
+  // `stream`'s entry, or a free one taken for it; NULL: every entry serves another stream
+  Schedule* entry(hipStream_t stream) {
+    Schedule* e = find(stream);
+    if (e || used == kSchedStreams) return e;
+    s[used].stream = stream;
+    return &s[used++];
   }
 };
 
@@ -659,19 +715,9 @@ void rtclj::rebind_stream_schedules(void* from, void* to, const uint64_t* uids, 
   });
 }
 
-static int hip_fail(hipError_t e, const char* what) {
-  return set_error(RT_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-#define HIP_TRY(call)                                  \
-  do {                                                 \
-    hipError_t _e = (call);                            \
-    if (_e != hipSuccess) return hip_fail(_e, #call);  \
-  } while (0)
-
 extern "C" int rt_set_variant(int v) {
   clear_error();
-  if (v != 0 && !variant_table(v).fn)
+  if (!policy::has_variant(v, kDiag))
     return set_error(RT_E_ARG, "rt_set_variant: variant " + std::to_string(v) +
                                    " is not in this build (diagnostic variants: lib/librtclj_diag.so)");
   return g_variant.exchange(v);
@@ -835,31 +881,6 @@ extern "C" int rt_scene_free(rt_dscene* d) {
   return RT_OK;
 }
 
-// traversal stack bytes: u8 entries for the 8-body-leaf tree (tree[2], at
-// most 256 nodes when its variant runs), u16 otherwise
-static int stack_entries(const DTree& t, int tree) { return tree == 0 ? t.depth + 2 : std::max(t.depth, 1); }
-// (threads: the workgroup's lanes, a stack row each)
-static size_t stack_of(const DTree& t, int tree, int threads = 256) {
-  return static_cast<size_t>(stack_entries(t, tree)) * threads * (tree == 2 ? 1 : 2);
-}
-static size_t lds_of(const DTree& t, int tree, int threads = 256) {
-  return static_cast<size_t>(t.blob_f4) * 16 + stack_of(t, tree, threads);
-}
-// variant 22 (the compact image): u8 node indices, depth rows (the dead
-// far-child write goes one above the top, as in 16)
-static int stack_entries_compact(const DTree& t) { return std::max(t.depth, 1); }
-static size_t lds_of_compact(const DTree& t, int threads) {
-  return static_cast<size_t>(t.blob_f4) * 16 + static_cast<size_t>(stack_entries_compact(t)) * threads;
-}
-// LDS a CU can give each of 5 workgroups (160 KB / 5), less the 4-body-leaf
-// kernel's static LDS (pool counter, the 64 pixels' colour sums and pixel
-// table).  (Its registers allow 6; C1's 24.0 KB image fits 6 as well.)
-constexpr size_t kStaticLds = 4 + kPoolPx * 3 * 8 + kPoolPx * 16 + 12;   // (the 8-body traversal: no table, 1 KB less)
-constexpr size_t kLds5 = 160 * 1024 / 5 - kStaticLds;
-// (variants 24 / 26's static LDS, 1.4 / 1.5 KB: the 64 pixels' u32 sums and
-// keys, the wrap counts, 8 or 16 waves' compaction counters; 2 KB allowed for)
-constexpr size_t kStaticLds8 = 2048;
-
 // Tile sharing, A/B knobs read at every launch:
 // RTCLJ_STEAL=0 (off: the static sample split for launches of few tiles, as
 // before), RTCLJ_THIEVES (helper workgroups per workgroup slot of the
@@ -868,7 +889,6 @@ static int env_int(const char* name, int dflt, int lo) {
   const char* e = std::getenv(name);
   return e ? std::max(lo, std::atoi(e)) : dflt;
 }
-static int split_rounds() { return env_int("RTCLJ_SPLIT_ROUNDS", 3, 1); }   // (kSplitRounds above)
 
 // workgroups device `device` holds at once for kernel fn with `lds` bytes of
 // dynamic LDS (CUs x the occupancy query), cached per (device, fn, lds)
@@ -887,134 +907,48 @@ static int launch_slots(int device, const void* fn, size_t lds, int threads = 25
   return cus * per;
 }
 
-// the most splits of one tile (rt_launch's sample split, below)
-constexpr int kSplitMax = 64;
-
-// The pending sort of a stream's tile-cost record (Schedule::sort_pending):
-// order_kernel, and plan_kernel for a planned split; the order is ready for
-// the next launch of the shape.  Returns the launches' hipError_t.
-static int sort_record(Schedule* sch, int n_tiles, int spp, hipStream_t stream) {
-  unsigned* cost = sch->cost;
-  int* order = sch->order;
-  int n = n_tiles;
-  void* sargs[] = {&cost, &order, &n};
-  hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(&order_kernel), dim3(1), dim3(1024), sargs, 0, stream);
-  if (e != hipSuccess) return e;
-  sch->ready = true;
-  sch->sort_pending = false;
-  sch->plan_units = -1;
-  if (sch->sort_plan > 0 && sch->units_cap >= sch->sort_plan) {
-    // the next split launch's cost-balanced units, from this record
-    int2* units = sch->units;
-    int Uk = sch->sort_plan, smax = std::min(spp, kSplitMax);
-    void* pargs[] = {&cost, &order, &n, &Uk, &smax, &units};
-    e = hipLaunchKernel(reinterpret_cast<const void*>(&plan_kernel), dim3(1), dim3(1024), pargs, 0, stream);
-    if (e != hipSuccess) return e;
-    sch->plan_units = sch->sort_plan;
-  }
-  return hipSuccess;
+// what the selection policy (variant_policy.h) reads of a scene, of a frame
+static policy::Scene scene_info(const rt_dscene& ds) {
+  policy::Scene s{};
+  for (int k = 0; k < 3; ++k) s.tree[k] = policy::Tree{ds.tree[k].n_nodes, ds.tree[k].depth, ds.tree[k].blob_f4};
+  s.n_pad = ds.n_pad;
+  s.unit_albedo = ds.unit_albedo;
+  return s;
 }
-
-// the variants of the compact image (u8 node-index stack, u32 sums)
-static bool compact_variant(int v) { return v == 22 || v == 24 || v == 26 || v == 28; }
-
-// selector -> the variant a launch on ds runs
-static int resolve_variant(const rt_dscene& ds, int vsel) {
-  // default: 4-body leaves, unless that tree's LDS image limits a CU below
-  // 5 workgroups (160 KB / 5) and the 8-body-leaf tree's is smaller
-  // (measured: 1025 bodies 12.9 vs 14.0 ms; 484: 10.8 vs 12.2); each image
-  // with the stack rows of its own variant's workgroup (18: 512 lanes)
-  if (vsel == 0)
-    vsel = (lds_of(ds.tree[1], 1) > kLds5 && ds.tree[2].n_nodes <= 256 &&
-            lds_of(ds.tree[2], 2, variant_table(18).threads) < lds_of(ds.tree[1], 1)) ? 18 : 16;
-  if ((vsel == 18 || vsel == 19) && ds.tree[2].n_nodes > 256) vsel -= 2;   // u8 stack: 256 nodes at most
-  // u16 stack of node LDS addresses: the kernel's static LDS (< 4 KB; 8 KB
-  // allowed for) plus the node region must stay below 64 KB
-  if ((vsel == 16 || vsel == 17) && ds.tree[1].n_nodes * 80 + 8192 > 65535) vsel = 12;
-  // the sorted kernels: the 4-body tree's byte-offset refs in a u16 stack
-  // inside a wave's exchange slots, the blob beside the exchange buffer
-  if ((vsel == 20 || vsel == 21) &&
-      (ds.tree[1].n_nodes * 80 > 65535 || ds.tree[1].depth + 2 > kBvhStack ||
-       static_cast<size_t>(ds.tree[1].blob_f4) * 16 + kXBytes > 96 * 1024))
-    vsel = 16;
-  if (vsel >= 11) {
-    const DTree& t = ds.tree[variant_tree(vsel)];
-    if (t.depth + 2 > kBvhStack) return 5;                       // tree too deep for the stack
-    // (the stack rows of the variant's own workgroup size, as launch_lds)
-    if (vsel != 12 && lds_of(t, variant_tree(vsel), variant_table(vsel).threads) > 96 * 1024)
-      vsel = 12;   // tree too big for LDS: 2-body leaves, global
-    if (vsel == 12 && ds.tree[0].depth + 2 > kBvhStack) return 5;
-  }
-  if (compact_variant(vsel) && ds.tree[1].n_nodes > 256) vsel = 16;   // (u8 node indices)
-  return vsel;
-}
-
-// The compact variant (22) for a launch: the 4-body tree's node indices fit
-// a byte, and a pixel's u32 sum with its byte of wrap counts cannot overflow
-// -- every sample's colour is at most 1 per channel (albedos within [-1, 1]:
-// the sky and the dielectric give at most 1), so a channel wraps at most spp /
-// 256 < 256 times for spp < 65536 (none for spp <= 255, where the kernel adds
-// without counting).  Its pixel table packs no coordinates above 65535 (the
-// key table plus one image row per tile row).  The default selector runs it
-// wherever it applies (and an explicit 22 too); elsewhere the launch runs 16.
-// Seven workgroups per CU instead of six, in 72 VGPRs without a spill.
-static bool compact_ok(const rt_dscene& ds, const rt_params& p) {
-  return ds.unit_albedo && ds.tree[1].n_nodes <= 256 && p.spp < 65536 && ds.tree[1].depth + 2 <= kBvhStack &&
-         p.width <= 65536 && p.height <= 65536;
-}
+// the variant a launch of p on ds runs under the current selector
 static int launch_variant(const rt_dscene& ds, const rt_params& p) {
   const int sel = g_variant.load();
-  int vsel = resolve_variant(ds, sel);
-  if ((sel == 0 && vsel == 16) || vsel == 22) vsel = compact_ok(ds, p) ? 22 : 16;
-  // A scene the default sends to the 8-body-leaf walk (its 4-body image too
-  // big for five 4-wave workgroups a CU) runs 22's compact image on the
-  // 4-body walk's leaf records instead, in workgroups that share one image
-  // among more waves: 16-wave workgroups (26) where two fit a CU -- 8 waves
-  // per SIMD in 64 VGPRs -- else 8-wave ones (24) where three fit -- 6 per
-  // SIMD, as 18.  C4: 4.295 s (26) vs 4.570 (24) vs 4.931 (18), same boxes
-  // (profiles/r05/c4_v26/, c4_v24/); C2's frame on 26 instead of 22: 260.4 vs
-  // 251.8 ms (a pool's 32,000 samples over 1,024 lanes drain too often).
-  if (sel == 0 && vsel == 18 && compact_ok(ds, p)) {
-    if (lds_of_compact(ds.tree[1], 1024) + kStaticLds8 <= 160 * 1024 / 2)
-      vsel = 26;
-    else if (lds_of_compact(ds.tree[1], 512) + kStaticLds8 <= 160 * 1024 / 3)
-      vsel = 24;
-  }
-  if ((vsel == 24 || vsel == 26 || vsel == 28) && !compact_ok(ds, p)) vsel = 16;
-  // RTCLJ_TH4=r (A/B knob, default 0 = never): a launch of 22 with fewer
-  // 8 x 8 tiles than r x the workgroups the device holds -- a shard of a
-  // multi-GPU frame -- runs 28: the same image on 8 x 4-pixel pools, whole,
-  // where 22 splits every tile's samples over 2-3 workgroups.  Measured at r
-  // = 2 (profiles/r06/th4/): C1's 8-rank shard 1.62 ms against 0.84 with the
-  // splits, the 4-rank 1.56 against 1.37 (the whole 8 x 4 pools are 1.84
-  // rounds of 3,200-sample units: the last round's long units are the tail),
-  // and 28 costs 5 % more per sample on the whole C1 frame (4.95 vs 4.71 ms:
-  // a pool of half the pixels drains twice as often).  DESIGN.md §6.
-  if (sel == 0 && vsel == 22) {
+  const policy::Scene s = scene_info(ds);
+  const policy::Frame f{p.width, p.height, rows_out(p), p.spp};
+  int vsel = policy::launch_variant(s, f, sel, kDiag, 0, 0);
+  // RTCLJ_TH4 (policy::launch_variant): read, and the device asked for 22's
+  // resident workgroups, only where the default runs 22
+  if (sel == policy::kDefault && vsel == policy::kCompact) {
     const int ratio = env_int("RTCLJ_TH4", 0, 0);
     if (ratio > 0) {
-      const int rows = rows_out(p);
-      const int64_t n8 = static_cast<int64_t>((p.width + kTile - 1) / kTile) * ((rows + kTile - 1) / kTile);
-      const Variant& v22 = variant_table(22);
-      const int slots = launch_slots(ds.device, v22.fn, lds_of_compact(ds.tree[1], v22.threads), v22.threads);
-      if (slots > 0 && n8 < static_cast<int64_t>(ratio) * slots) vsel = 28;
+      const int threads = variant_traits(vsel).threads;
+      const int slots = launch_slots(ds.device, variant_fn(vsel), policy::lds_of_compact(s.tree[1], threads), threads);
+      vsel = policy::launch_variant(s, f, sel, kDiag, ratio, slots);
     }
   }
   return vsel;
 }
 
-extern "C" int rt_resolve_variant(const rt_dscene* ds) { return ds ? resolve_variant(*ds, g_variant.load()) : -1; }
+extern "C" int rt_resolve_variant(const rt_dscene* ds) {
+  return ds ? policy::resolve_variant(scene_info(*ds), g_variant.load(), kDiag) : -1;
+}
 
-// dynamic LDS of a launch of variant vsel on ds
-static size_t launch_lds(const rt_dscene& ds, int vsel) {
-  const Variant& v = variant_table(vsel);
-  if (v.scan == SCAN_BVHS) return static_cast<size_t>(ds.tree[1].blob_f4) * 16 + kXBytes;   // blob | exchange
-  if (compact_variant(vsel)) return lds_of_compact(ds.tree[1], v.threads);
-  if (vsel >= 11) {
-    const DTree& tr = ds.tree[variant_tree(vsel)];
-    return v.lds ? lds_of(tr, variant_tree(vsel), v.threads) : stack_of(tr, variant_tree(vsel), v.threads);
-  }
-  return v.lds ? static_cast<size_t>(ds.n_pad) * sizeof(float4) : 0;
+// The HIP occupancy query on a kernel at a workgroup size and dynamic LDS:
+// out4[0..2] = {workgroups per CU, VGPRs per lane, LDS bytes per workgroup}
+static int occupancy_report(const void* fn, int threads, size_t lds, int* out4) {
+  int blocks = 0;
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, threads, lds));
+  hipFuncAttributes fa{};
+  HIP_TRY(hipFuncGetAttributes(&fa, fn));
+  out4[0] = blocks;
+  out4[1] = fa.numRegs;
+  out4[2] = static_cast<int>(lds + fa.sharedSizeBytes);
+  return RT_OK;
 }
 
 // Occupancy of the launch rt_launch would make for (ds, p): the HIP occupancy
@@ -1026,18 +960,14 @@ extern "C" int rt_launch_occupancy(const rt_dscene* ds, const rt_params* p, int*
   if (rows <= 0 || p->width <= 0) return set_error(RT_E_ARG, "rt_launch_occupancy: empty frame");
   HIP_TRY(hipSetDevice(ds->device));
   const int vsel = launch_variant(*ds, *p);
-  const void* fn = variant_table(vsel).fn;
+  const void* fn = variant_fn(vsel);
   if (!fn) return set_error(RT_E_ARG, "rt_launch_occupancy: no kernel for variant " + std::to_string(vsel));
-  const size_t lds = launch_lds(*ds, vsel);
+  const size_t lds = policy::launch_lds(scene_info(*ds), vsel, kDiag);
   if (lds > 64 * 1024)
     HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-  int blocks = 0;
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, variant_table(vsel).threads, lds));
-  hipFuncAttributes fa{};
-  HIP_TRY(hipFuncGetAttributes(&fa, fn));
-  out4[0] = blocks * variant_table(vsel).threads / 256;   // (in 256-thread workgroups) per CU
-  out4[1] = fa.numRegs;           // VGPRs per lane
-  out4[2] = static_cast<int>(lds + fa.sharedSizeBytes);   // LDS bytes per workgroup
+  const int threads = variant_traits(vsel).threads;
+  if (const int rc = occupancy_report(fn, threads, lds, out4)) return rc;
+  out4[0] = out4[0] * threads / 256;   // (in 256-thread workgroups) per CU
   out4[3] = vsel;
   return RT_OK;
 }
@@ -1061,42 +991,333 @@ static int dbg_buffers(int device, unsigned long long** dbg, unsigned long long*
 // quotient)
 static uint64_t magic64(int d) { return d <= 1 ? 0 : ~0ull / static_cast<uint64_t>(d) + 1ull; }
 
-// Sample split (rt_launch): split every tile of a launch with fewer tiles
-// than kSplitRounds (RTCLJ_SPLIT_ROUNDS, default 3) x (resident workgroups), into enough splits to reach that
-// (at most kSplitMax).  tools/shard_time.py on C1's 1/2/4/8-GPU shards
-// (profiles/r02/shard_split_rounds.txt): 3-4 rounds best (8 GPUs: 5.88x at 3,
-// 5.72x at 4, 5.30x at 6, 3.96x at 16; unsplit 2.57x)
-// (kSplitMax, the most splits of a tile: defined above sort_record)
-
-namespace rtclj {
-int fill_async(void* p, int byte_value, size_t bytes, void* stream) {
-  if (bytes == 0) return hipSuccess;
-  if (bytes % 4 != 0) return hipErrorInvalidValue;   // (every buffer the product fills is whole words)
-  uint32_t* w = static_cast<uint32_t*>(p);
-  uint32_t v = static_cast<uint32_t>(byte_value & 0xff) * 0x01010101u;
-  size_t n = bytes / 4;
-  const size_t blocks = std::min<size_t>((n + 255) / 256, 2048);
-  void* args[] = {&w, &v, &n};
-  return hipLaunchKernel(reinterpret_cast<const void*>(&fill_kernel), dim3(static_cast<unsigned>(blocks)), dim3(256),
-                         args, 0, static_cast<hipStream_t>(stream));
+// ---- rt_launch's stages ----------------------------------------------------
+// a launch's frame arguments (rt_launch, rt_launch_accum, rt_adapt_step, rt_launch_feat)
+static int check_frame_args(const char* who, const rt_params& p) {
+  if (p.width <= 0 || p.height <= 0 || p.spp < 0 || p.spp > RT_MAX_SPP ||
+      (p.flags & ~(RT_FLAG_REALM | RT_FLAG_STREAMED | RT_FLAG_REJECTION_SAMPLERS)) != 0)
+    return set_error(RT_E_ARG, std::string(who) + ": bad width/height/spp/flags");
+  return RT_OK;
 }
 
-int quantize_launch(const float* d_lin, uint8_t* d_out, size_t n, void* stream) {
-  static const QThr thr = [] {
-    QThr t;
-    std::memcpy(t.t, quantize_thresholds(), sizeof t.t);
-    return t;
-  }();
-  if (n == 0) return hipSuccess;
-  const size_t blocks = std::min<size_t>((n + 255) / 256, 4096);
-  QThr q = thr;
-  const float* in = d_lin;
-  uint8_t* out = d_out;
-  void* args[] = {&in, &out, &n, &q};
-  return hipLaunchKernel(reinterpret_cast<const void*>(&quantize_kernel), dim3(static_cast<unsigned>(blocks)),
-                         dim3(256), args, 0, static_cast<hipStream_t>(stream));
+// The camera, sampler, seed key and row selection of a launch: the fields
+// KArgs and FeatArgs share by name
+template <class A>
+static void pack_frame(A& a, const rt_camera& c, const rt_params& p, int rows) {
+  std::memcpy(a.cam + 0, c.center, 12);
+  std::memcpy(a.cam + 3, c.p00, 12);
+  std::memcpy(a.cam + 6, c.du, 12);
+  std::memcpy(a.cam + 9, c.dv, 12);
+  std::memcpy(a.cam + 12, c.disk_u, 12);
+  std::memcpy(a.cam + 15, c.disk_v, 12);
+  a.defocus = c.defocus ? 1 : 0;
+  a.width = p.width;
+  a.rows_out = rows;
+  a.row_begin = p.row_begin;
+  a.row_tile = p.row_tile > 0 ? p.row_tile : 8;
+  a.tile_first = p.tile_first;
+  a.tile_step = p.tile_step;
+  a.spp = p.spp;
+  a.sample_begin = p.sample_begin;
+  // the loop-free samplers unless the caller asks for the reference's rejection loops
+  a.sampler = (p.flags & RT_FLAG_REJECTION_SAMPLERS) ? 0 : (RT_SAMPLER_SPHERE | RT_SAMPLER_DISK);
+  a.key = seed_key(p.seed);
 }
-}  // namespace rtclj
+
+// The variant a launch runs: its number, traits and kernels
+struct Kernel {
+  int vsel;
+  policy::Traits t;
+  const void* fn;
+  const void* sweep;
+};
+// ... chosen for (ds, p), and its tree and stack bound to the arguments
+static int bind_variant(const char* who, const rt_dscene& ds, const rt_params& p, KArgs& a, Kernel* out) {
+  int vsel = launch_variant(ds, p);
+  if (variant_traits(vsel).walk == policy::WALK_SORTED && p.max_depth > 1023)
+    vsel = policy::kFull4;   // (a path's depth left: 10 bits in the exchange)
+  const Kernel v{vsel, variant_traits(vsel), variant_fn(vsel), variant_sweep(vsel)};
+  if (!v.fn) return set_error(RT_E_ARG, std::string(who) + ": no kernel for variant " + std::to_string(vsel));
+  const DTree& tr = ds.tree[v.t.tree];
+  a.bvh_blob = tr.blob;
+  a.bvh_blob_f4 = tr.blob_f4;
+  a.bvh_off_pairs = tr.off_pairs;
+  a.bvh_off_pidx = tr.off_pidx;
+  a.big_pair0 = tr.big_pair0;
+  a.n_big_leaves = tr.n_big_leaves;
+  a.bvh_stack = policy::launch_stack(scene_info(ds), v.t);
+  for (int k = 0; k < 3; ++k) a.bvh_c[k] = tr.c[k];
+  a.bvh_r = tr.r;
+  a.bvh_c0 = tr.c0;
+  // drain compaction: a post holds as many paths as a wave's stack slice has
+  // room for (RTCLJ_COMPACT: post at or below that many paths; 0 off)
+  const int words = a.bvh_stack * 16 * v.t.entry_bytes;   // a wave's stack slice
+  a.mb_paths = std::min(32, words / kMbFields);
+  a.compact = is_bvh_scan(v.t.scan) ? std::min(a.mb_paths, env_int("RTCLJ_COMPACT", a.mb_paths, 0)) : 0;
+  *out = v;
+  return RT_OK;
+}
+
+// the statistics builds' counters and the wave timeline
+static int bind_debug(int device, const Kernel& v, KArgs& a) {
+  if (v.t.stats) return dbg_buffers(device, &a.dbg, &a.dbgw);
+#ifdef RTCLJ_DIAG
+  if (g_timeline) {   // wave timeline only (rt_debug_waves), no counters
+    unsigned long long* unused = nullptr;
+    return dbg_buffers(device, &unused, &a.dbgw);
+  }
+#endif
+  return RT_OK;
+}
+
+// the launch's dynamic LDS, allowed for on the variant's kernels
+static int bind_lds(const rt_dscene& ds, const Kernel& v, size_t* out) {
+  size_t lds = policy::launch_lds(scene_info(ds), v.vsel, kDiag);
+#ifdef RTCLJ_DIAG
+  // (diagnostic: RTCLJ_LDS_PAD bytes of dynamic LDS added to the launch, to
+  // measure the kernel at fewer workgroups per CU)
+  lds += static_cast<size_t>(env_int("RTCLJ_LDS_PAD", 0, 0));
+#endif
+  if (lds > 64 * 1024) {
+    HIP_TRY(hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+    if (v.sweep) HIP_TRY(hipFuncSetAttribute(v.sweep, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+  }
+  *out = lds;
+  return RT_OK;
+}
+
+// Sample split: a frame of fewer tiles than
+// kSplitRounds x the workgroups the GPU holds at once (a shard of a
+// multi-GPU frame, a small image) runs every tile as `split` workgroups,
+// one contiguous sample range each, so that the launch does not end on a
+// few whole tiles running alone (its length would be the longest tile's).
+// The integer pixel sums add up to the same bits in any grouping.
+// (The kernel also takes a whole-tile prefix of the order, n_whole; the
+// split tiles' partial sums go through finalize_kernel.)
+// (Tile sharing, below, takes the launches that are not split: a split
+// launch has about one unit per workgroup slot, all of which end together,
+// and on C1's 8-GPU shard the split is faster -- 1.05 vs 1.09-1.18 ms --
+// while sharing balances the tail of a long launch in plain order, C1
+// 6.78 -> 6.47 ms, and in the record's longest-first order costs nothing
+// (profiles/r03/share_ab.txt).  RTCLJ_STEAL=0: never share.)
+// The knobs and the device's slots for policy::choose_split, spp > 1.
+static int launch_split(const rt_dscene& ds, const Kernel& v, size_t lds, int n_tiles, const rt_params& p) {
+  int forced = 0, slots = 0, rounds = 0;
+  if (const char* e = std::getenv("RTCLJ_SPLIT")) {
+    forced = std::max(1, std::atoi(e));
+  } else {
+    slots = launch_slots(ds.device, v.fn, lds, v.t.threads);
+    // (28: its pools are the split's answer already; they split only when
+    // fewer than RTCLJ_TH4_SPLIT_ROUNDS (1) rounds of them fill the device)
+    rounds = v.t.th ? env_int("RTCLJ_TH4_SPLIT_ROUNDS", 1, 1) : env_int("RTCLJ_SPLIT_ROUNDS", 3, 1);
+  }
+  return policy::choose_split(n_tiles, p.spp, forced, slots, rounds, (p.flags & RT_FLAG_STREAMED) != 0);
+}
+
+// the fills a launch needs before its trace kernel, as one launch
+static hipError_t enqueue_fills(const FillSet& fills, hipStream_t stream) {
+  size_t most = 0;
+  for (int k = 0; k < fills.count; ++k) most = std::max(most, fills.n[k]);
+  const size_t blocks = std::max<size_t>(1, std::min<size_t>((most + 255) / 256, 2048));
+  return enqueue(fill_set_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, fills);
+}
+
+// A launch of another shape re-keys the entry: that record was another
+// shape's.  Returns whether it did.
+bool Schedule::rekey(const ScheduleKey& k) {
+  if (std::memcmp(&key, &k, sizeof k) == 0) return false;
+  ready = false;
+  sort_pending = false;
+  key = k;
+  return true;
+}
+
+// The pending sort of the stream's tile-cost record (sort_pending):
+// order_kernel, and plan_kernel for a planned split; the order is ready for
+// the next launch of the shape.
+int Schedule::sort_record(int n_tiles, int spp) {
+  HIP_TRY(enqueue(order_kernel, dim3(1), dim3(1024), 0, stream, cost.p, order.p, n_tiles));
+  ready = true;
+  sort_pending = false;
+  plan_units = -1;
+  if (sort_plan > 0 && units.cap >= static_cast<size_t>(sort_plan)) {
+    // the next split launch's cost-balanced units, from this record
+    HIP_TRY(enqueue(plan_kernel, dim3(1), dim3(1024), 0, stream, cost.p, order.p, n_tiles, sort_plan,
+                    std::min(spp, policy::kSplitMax), units.p));
+    plan_units = sort_plan;
+  }
+  return RT_OK;
+}
+
+// the split tiles' integer sums: one u64 per channel, added to by the
+// splits, converted and zeroed by finalize_kernel
+int Schedule::bind_part(KArgs& a, size_t n_elems) {
+  bool grew = false;
+  HIP_TRY(part.reserve(n_elems, stream, &grew));
+  if (grew) {
+    HIP_TRY(fill_zero(part, n_elems, stream));
+    part_dirty = false;
+  }
+  if (part_dirty) {   // an earlier launch failed between its trace and finalize kernels
+    HIP_TRY(fill_zero(part, part.cap, stream));
+    part_dirty = false;
+  }
+  a.part = part.p;
+  return RT_OK;
+}
+
+// adaptive schedule: dispatch tiles longest first, by the durations the
+// previous launches of this launch shape on this scene and stream measured
+// (each launch's added to half the record before it).  split_units: a split
+// launch's split units (-1: not split).  *first_order: a shape's first launch
+// in a heuristic order.
+int Schedule::bind_order(KArgs& a, FillSet& fills, int n_tiles, int spp, int split_units, bool* first_order) {
+  bool grew_cost = false, grew_order = false;
+  hipError_t e = cost.reserve(n_tiles, stream, &grew_cost);
+  if (e == hipSuccess) e = order.reserve(n_tiles, stream, &grew_order);
+  if (grew_cost || grew_order || e != hipSuccess) {   // (the record and the order went with the old buffers)
+    ready = false;
+    sort_pending = false;
+  }
+  HIP_TRY(e);
+  // the previous launch's record, sorted now (stream-ordered after it)
+  if (sort_pending)
+    if (const int rc = sort_record(n_tiles, spp)) return rc;
+  if (ready) {
+    a.tile_order = order.p;
+  } else if (env_int("RTCLJ_FIRST_ORDER", 1, 0) == 1) {
+    // No record yet: the tiles bottom-up.  The reference's scenes (and
+    // C1-C4) put the ground and its bodies below the sky: the expensive
+    // tiles start first and the launch ends on sky tiles, where row-major
+    // order ended on the ground's.  C1's first frame of a shape 5.13-5.19
+    // ms against 5.25 row-major (tools/first_frame.py, 9 pairs, two
+    // rounds; profiles/r06/first_order/); RTCLJ_FIRST_ORDER=0: row-major.
+    // Tile sharing still balances the tail, as in plain order.
+    HIP_TRY(enqueue(iota_rev_kernel, dim3(static_cast<unsigned>((n_tiles + 255) / 256)), dim3(256), 0, stream, order.p,
+                    n_tiles));
+    a.tile_order = order.p;
+    *first_order = true;
+  }
+  a.tile_cost = cost.p;
+  // a split launch in the recorded order: with RTCLJ_SPLIT_PLAN=1, the
+  // cost-balanced units the previous launch of the shape planned (when it
+  // planned this many).  Off by default: C1's 8-GPU shard 1.10-1.15 ms
+  // against 0.99-1.02 with uniform splits, the 4-GPU one 1.93 vs 1.69
+  // (profiles/r04/split_plan/; round 2's cost-sized splits lost the same
+  // way): a heavy tile's many short pools each end with idle lanes.
+  if (split_units >= 0 && ready && plan_units == split_units && env_int("RTCLJ_SPLIT_PLAN", 0, 0) != 0)
+    a.unit_tab = units.p;
+  // the costs decay (order_kernel halves them after sorting): zeroed only
+  // when this launch shape starts a new history
+  if (!ready) fills.add(cost.p, 0, n_tiles * sizeof(unsigned));
+  return RT_OK;
+}
+
+// Tile sharing for a launch of whole tiles: the stream's words, counts, sums
+// and owner table bound to the arguments, this launch's epoch, and the
+// helpers added to *grid (the units, then the thieves, dispatched last, i.e.
+// as the units' slots free up in the launch's tail).  slots: the workgroups
+// the device holds at once (>= 1).
+int Schedule::bind_sharing(KArgs& a, FillSet& fills, int n_tiles, int n_units, int slots, bool new_shape,
+                           bool first_order, int64_t* grid) {
+  const int n_owner = 2 * slots;   // owner entries: twice the resident workgroups
+  // (at most 32 per slot: a tile's helper count stays below 2^16)
+  *grid += static_cast<int64_t>(std::min(32, env_int("RTCLJ_THIEVES", 4, 0))) * slots;
+  if (*grid > INT_MAX) *grid = n_units;
+  if (!stealc) {
+    HIP_TRY(stealc.alloc(2));
+    HIP_TRY(fill_zero(stealc, 2, stream));
+  }
+  const size_t nsum = static_cast<size_t>(n_tiles) * kPoolPx * 3;
+  bool grew[3] = {false, false, false};
+  hipError_t e = word.reserve(n_tiles, stream, &grew[0]);
+  if (e == hipSuccess) e = done.reserve(n_tiles, stream, &grew[1]);
+  if (e == hipSuccess) e = sum.reserve(nsum, stream, &grew[2]);
+  HIP_TRY(e);   // (one that failed is empty, and grows again at the next launch)
+  if (grew[0] || grew[1] || grew[2]) {
+    // words 0: lo = hi, nothing to steal until an owner publishes; sums
+    // and done counts 0 (the kernel keeps them so between uses)
+    HIP_TRY(fill_zero(word, n_tiles, stream));
+    HIP_TRY(fill_zero(done, n_tiles, stream));
+    HIP_TRY(fill_zero(sum, nsum, stream));
+    new_shape = true;
+  }
+  bool grew_owner = false;
+  HIP_TRY(owner.resize(n_owner, stream, &grew_owner));
+  if (grew_owner) new_shape = true;
+  if (!epoch_started) {   // (RTCLJ_EPOCH_START: tests start a stream near the wrap)
+    epoch = static_cast<unsigned>(std::min(0xffff, env_int("RTCLJ_EPOCH_START", 1, 1)) - 1);
+    epoch_started = true;
+  }
+  epoch = (epoch + 1) & 0xffffu;
+  if (epoch == 0) {   // wrapped: no word or owner entry may carry the epoch's last use
+    epoch = 1;
+    new_shape = true;
+  }
+  a.epoch = epoch;
+  // a new shape (or a wrap): no tile is being run, and no word holds this
+  // launch's epoch.  (Old owner entries would only name words of other
+  // epochs, but tile indices of another shape may exceed this one's; a word
+  // last published 65,535 launches ago carries the epoch a wrap reuses.)
+  if (new_shape) {
+    fills.add(owner.p, 0xff, n_owner * sizeof(int));
+    fills.add(word.p, 0, n_tiles * sizeof(unsigned long long));
+  }
+  // owners publish only in the launch's last RTCLJ_SHARE_ROUNDS rounds of
+  // units (default 2; a round = the workgroups the device holds at once.
+  // C4 plain order: WRITE_SIZE 2.90 GB per launch at every round, 0.44 at
+  // 2, 0.60 at 3; C1's timing the same at 1, 2, 3 or every round:
+  // profiles/r04/share_rounds/)
+  a.share_from = static_cast<int>(std::max<int64_t>(
+      0, n_units - static_cast<int64_t>(env_int("RTCLJ_SHARE_ROUNDS", 2, 0)) * slots));
+  a.word = word.p;
+  a.done = done.p;
+  a.sum = sum.p;
+  a.owner = owner.p;
+  a.n_owner = n_owner;
+  a.stealc = stealc.p;
+  a.steal_min = env_int("RTCLJ_STEAL_MIN", 256, 1);
+  // claims of up to 1024 samples in the record's longest-first order (the
+  // heavy tiles start first: fewer claims, 6.03 -> 6.00 ms on C1); in plain
+  // order up to 1/48 of the tile's pool (0: the kernel's per-pool rule; C1's
+  // 6,400: 128 -- helpers then need small claims to balance the tail;
+  // C4's 64,000: 1024)
+  a.batch_max = env_int("RTCLJ_BATCH_MAX", (a.tile_order && !first_order) ? 1024 : 0, 0);
+  return RT_OK;
+}
+
+// Path export for split launches (KArgs xq; RTCLJ_EXPORT=1, A/B): a wave
+// whose batches are spent and which holds at most RTCLJ_EXPORT_LIM paths
+// (default 64: as soon as its batches are spent) writes them out and
+// leaves, so a unit's workgroup frees its slot without draining; the sweep
+// launch runs the records.  At most one record per thread of a unit.
+int Schedule::bind_export(KArgs& a, FillSet& fills, size_t records) {
+  HIP_TRY(xq.reserve(records * 4, stream));
+  if (!xq_n) HIP_TRY(xq_n.alloc(2));
+  fills.add(xq_n.p, 0, 2 * sizeof(unsigned));
+  a.xq = xq.p;
+  a.xq_n = xq_n.p;
+  a.compact = std::min(64, env_int("RTCLJ_EXPORT_LIM", 64, 1));
+  ++xq_launches;
+  return RT_OK;
+}
+
+// Behind a launch that recorded its tiles' costs: this record's sort, at the
+// next launch of the shape on the stream (RTCLJ_SORT_EAGER=1, A/B: right
+// behind this launch, as before round 6; within noise on every bench.py leg,
+// profiles/r06/sort_ab/).  plan_units_next: the units of a wholly split
+// launch, for which RTCLJ_SPLIT_PLAN=1 plans the next one (-1: none).
+int Schedule::record(int n_tiles, int spp, int plan_units_next) {
+  sort_pending = true;
+  ready = false;
+  sort_plan = -1;
+  if (plan_units_next >= 0 && env_int("RTCLJ_SPLIT_PLAN", 0, 0) != 0) {
+    HIP_TRY(units.reserve(plan_units_next, stream));
+    sort_plan = plan_units_next;
+  }
+  if (env_int("RTCLJ_SORT_EAGER", 0, 0) != 0) return sort_record(n_tiles, spp);
+  return RT_OK;
+}
 
 // rt_launch, and rt_launch_accum's pass (acc_sums: the accumulator's
 // [rows][width][3] sums; d_out NULL).  A pass is the launch with no whole
@@ -1111,11 +1332,11 @@ static int launch_impl(const rt_dscene* ds, const rt_camera* c, const rt_params*
                        uint64_t* d_counters, void* hip_stream, unsigned long long* acc_sums,
                        const char* who = "rt_launch", const int* active = nullptr, int n_active = 0) {
   if (!ds || !c || !p || (!d_out && !acc_sums)) return set_error(RT_E_ARG, std::string(who) + ": NULL argument");
-  if (p->width <= 0 || p->height <= 0 || p->spp < 0 || p->spp > RT_MAX_SPP ||
-      (p->flags & ~(RT_FLAG_REALM | RT_FLAG_STREAMED | RT_FLAG_REJECTION_SAMPLERS)) != 0)
-    return set_error(RT_E_ARG, std::string(who) + ": bad width/height/spp/flags");
+  if (const int rc = check_frame_args(who, *p)) return rc;
   const int rows = rows_out(*p);
   if (rows < 0) return set_error(RT_E_ARG, std::string(who) + ": bad row selection");
+  if (rows == 0) return RT_OK;
+  HIP_TRY(hipSetDevice(ds->device));
   KArgs a{};
   a.geo = ds->geo;
   a.geo2 = reinterpret_cast<const Pair*>(ds->geo2);
@@ -1124,240 +1345,52 @@ static int launch_impl(const rt_dscene* ds, const rt_camera* c, const rt_params*
   a.kind = ds->kind;
   a.out = d_out;
   a.counters = reinterpret_cast<unsigned long long*>(d_counters);
-  std::memcpy(a.cam + 0, c->center, 12);
-  std::memcpy(a.cam + 3, c->p00, 12);
-  std::memcpy(a.cam + 6, c->du, 12);
-  std::memcpy(a.cam + 9, c->dv, 12);
-  std::memcpy(a.cam + 12, c->disk_u, 12);
-  std::memcpy(a.cam + 15, c->disk_v, 12);
-  a.defocus = c->defocus ? 1 : 0;
+  pack_frame(a, *c, *p, rows);
   a.n = ds->n;
   a.n_pad = ds->n_pad;
-  a.width = p->width;
-  a.rows_out = rows;
-  a.row_begin = p->row_begin;
-  a.row_tile = p->row_tile > 0 ? p->row_tile : 8;
-  a.tile_first = p->tile_first;
-  a.tile_step = p->tile_step;
-  a.spp = p->spp;
-  a.sample_begin = p->sample_begin;
   a.max_depth = p->max_depth;
   a.realm = (p->flags & RT_FLAG_REALM) ? 1 : 0;
-  // the loop-free samplers unless the caller asks for the reference's rejection loops
-  a.sampler = (p->flags & RT_FLAG_REJECTION_SAMPLERS) ? 0 : (RT_SAMPLER_SPHERE | RT_SAMPLER_DISK);
-  a.key = seed_key(p->seed);
-  if (rows == 0) return RT_OK;
-  HIP_TRY(hipSetDevice(ds->device));
-  int vsel = launch_variant(*ds, *p);
-  if (variant_table(vsel).scan == SCAN_BVHS && p->max_depth > 1023) vsel = 16;   // (a path's depth left: 10 bits in the exchange)
-  const Variant& v = variant_table(vsel);
-  if (!v.fn) return set_error(RT_E_ARG, std::string(who) + ": no kernel for variant " + std::to_string(vsel));
-  const DTree& tr = ds->tree[variant_tree(vsel)];
-  a.bvh_blob = tr.blob;
-  a.bvh_blob_f4 = tr.blob_f4;
-  a.bvh_off_pairs = tr.off_pairs;
-  a.bvh_off_pidx = tr.off_pidx;
-  a.big_pair0 = tr.big_pair0;
-  a.n_big_leaves = tr.n_big_leaves;
-  // entries per lane: the ordered traversal (trees 1, 2) holds at most depth
-  // (a node on level L has L - 1 ancestors; the dead far-child write goes one
-  // above them); tree 0 also serves the while-while variants (depth + 2)
-  a.bvh_stack = compact_variant(vsel) ? stack_entries_compact(tr) : stack_entries(tr, variant_tree(vsel));
-  for (int k = 0; k < 3; ++k) a.bvh_c[k] = tr.c[k];
-  a.bvh_r = tr.r;
-  a.bvh_c0 = tr.c0;
-  // drain compaction: a post holds as many paths as a wave's stack slice has
-  // room for (RTCLJ_COMPACT: post at or below that many paths; 0 off)
-  {
-    const int words = a.bvh_stack * 16 * (v.scan == SCAN_BVHO || v.scan == SCAN_BVHQ7 ? 1 : 2);   // a wave's stack slice
-    a.mb_paths = std::min(32, words / kMbFields);
-    a.compact = is_bvh_scan(v.scan) ? std::min(a.mb_paths, env_int("RTCLJ_COMPACT", a.mb_paths, 0)) : 0;
-  }
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const int th = variant_rows(v);   // the variant's tile rows
+  Kernel v;
+  if (const int rc = bind_variant(who, *ds, *p, a, &v)) return rc;
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const int th = policy::variant_rows(v.t);   // the variant's tile rows
   const int gx = (p->width + kTile - 1) / kTile, gy = (rows + th - 1) / th;
-  const dim3 block(v.threads);
   if (active && (th != kTile || n_active <= 0 || n_active > gx * gy))
-    return set_error(RT_E_ARG, std::string(who) + ": variant " + std::to_string(vsel) + " has no 8 x 8 tiles");
+    return set_error(RT_E_ARG, std::string(who) + ": variant " + std::to_string(v.vsel) + " has no 8 x 8 tiles");
   const int n_tiles = active ? n_active : gx * gy;
   a.tiles_x = gx;
-  if (v.stats) {
-    const int rc = dbg_buffers(ds->device, &a.dbg, &a.dbgw);
-    if (rc != RT_OK) return rc;
-  }
-#ifdef RTCLJ_DIAG
-  else if (g_timeline) {   // wave timeline only (rt_debug_waves), no counters
-    unsigned long long* unused = nullptr;
-    const int rc = dbg_buffers(ds->device, &unused, &a.dbgw);
-    if (rc != RT_OK) return rc;
-  }
-#endif
-#ifdef RTCLJ_DIAG
-  // (diagnostic: RTCLJ_LDS_PAD bytes of dynamic LDS added to the launch, to
-  // measure the kernel at fewer workgroups per CU)
-  const size_t lds = launch_lds(*ds, vsel) + static_cast<size_t>(env_int("RTCLJ_LDS_PAD", 0, 0));
-#else
-  const size_t lds = launch_lds(*ds, vsel);
-#endif
-  if (lds > 64 * 1024) {
-    HIP_TRY(hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    if (v.sweep) HIP_TRY(hipFuncSetAttribute(v.sweep, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-  }
+  if (const int rc = bind_debug(ds->device, v, a)) return rc;
+  size_t lds = 0;
+  if (const int rc = bind_lds(*ds, v, &lds)) return rc;
   // the stream's entry: adaptive schedule and split partial sums
   Schedule* sch = nullptr;
   std::unique_lock<std::mutex> sched_lock;
   if (!active) {
-    ScheduleSet& set = ds->sched;
-    sched_lock = std::unique_lock<std::mutex>(set.mu);
-    for (int k = 0; k < set.used && !sch; ++k)
-      if (set.s[k].stream == stream) sch = &set.s[k];
-    if (!sch && set.used < kSchedStreams) {
-      sch = &set.s[set.used++];
-      sch->stream = stream;
-    }
+    sched_lock = std::unique_lock<std::mutex>(ds->sched.mu);
+    sch = ds->sched.entry(stream);
   }
-  // Sample split: a frame of fewer tiles than
-  // kSplitRounds x the workgroups the GPU holds at once (a shard of a
-  // multi-GPU frame, a small image) runs every tile as `split` workgroups,
-  // one contiguous sample range each, so that the launch does not end on a
-  // few whole tiles running alone (its length would be the longest tile's).
-  // The integer pixel sums add up to the same bits in any grouping.
-  // (The kernel also takes a whole-tile prefix of the order, n_whole; the
-  // split tiles' partial sums go through finalize_kernel.)
-  // (Tile sharing, below, takes the launches that are not split: a split
-  // launch has about one unit per workgroup slot, all of which end together,
-  // and on C1's 8-GPU shard the split is faster -- 1.05 vs 1.09-1.18 ms --
-  // while sharing balances the tail of a long launch in plain order, C1
-  // 6.78 -> 6.47 ms, and in the record's longest-first order costs nothing
-  // (profiles/r03/share_ab.txt).  RTCLJ_STEAL=0: never share.)
-  int split = 1, n_whole = n_tiles;
-  const bool steal = sch && env_int("RTCLJ_STEAL", 1, 0) != 0 && !v.stats && v.scan != SCAN_BVHS;
-  if ((sch || acc_sums) && p->spp > 1) {
-    if (const char* e = std::getenv("RTCLJ_SPLIT")) {
-      split = std::max(1, std::atoi(e));
-    } else {
-      const int slots = launch_slots(ds->device, v.fn, lds, v.threads);
-      // (28: its pools are the split's answer already; they split only when
-      // fewer than RTCLJ_TH4_SPLIT_ROUNDS (1) rounds of them fill the device)
-      const int rounds = vsel == 28 ? env_int("RTCLJ_TH4_SPLIT_ROUNDS", 1, 1) : split_rounds();
-      const int64_t want = static_cast<int64_t>(rounds) * slots;
-      if (slots > 0 && n_tiles < want) {
-        split = static_cast<int>((want + n_tiles - 1) / n_tiles);
-        // frames in flight: the next frame fills this launch's tail, so two
-        // rounds of workgroups suffice (at least 2 splits: an unsplit heavy
-        // tile would outlive two frames).  C1's 8-GPU shard, 2 streams:
-        // 0.817 ms per frame at split 2 vs 0.87 at 3 (profiles/r03/shard_matrix_*.txt)
-        if (p->flags & RT_FLAG_STREAMED)
-          split = std::max(2, static_cast<int>((2 * static_cast<int64_t>(slots) + n_tiles - 1) / n_tiles));
-      }
-    }
-    split = std::min(split, std::min(p->spp, kSplitMax));
-    if (split > 1) n_whole = 0;
-  }
-  if (acc_sums) n_whole = 0;   // an accumulating pass: every unit's sums go to part[]
+  const bool steal = sch && env_int("RTCLJ_STEAL", 1, 0) != 0 && !v.t.stats && v.t.walk != policy::WALK_SORTED;
+  const int split = ((sch || acc_sums) && p->spp > 1) ? launch_split(*ds, v, lds, n_tiles, *p) : 1;
+  // (an accumulating pass: every unit's sums go to part[])
+  const int n_whole = (split > 1 || acc_sums) ? 0 : n_tiles;
   a.split = split;
   a.n_whole = n_whole;
   a.rt_magic = magic64(a.row_tile);
   const int64_t n_units64 = n_whole + static_cast<int64_t>(n_tiles - n_whole) * split;
   if (n_units64 > INT_MAX) return set_error(RT_E_ARG, std::string(who) + ": frame too large");
   const int n_units = static_cast<int>(n_units64);
-  const size_t n_elems = static_cast<size_t>(rows) * p->width * 3;
-  if (acc_sums) {
-    a.part = acc_sums;
-  } else if (split > 1) {
-    // the split tiles' integer sums: one u64 per channel, added to by the
-    // splits, converted and zeroed by finalize_kernel
-    const size_t need = n_elems;
-    if (sch->part_cap < need) {   // grow: this stream's kernels may still read the old buffer
-      HIP_TRY(hipStreamSynchronize(stream));
-      if (sch->part) (void)hipFree(sch->part);
-      sch->part = nullptr;
-      sch->part_cap = 0;
-      HIP_TRY(hipMalloc(&sch->part, need * sizeof(unsigned long long)));
-      HIP_TRY(static_cast<hipError_t>(fill_async(sch->part, 0, need * sizeof(unsigned long long), stream)));
-      sch->part_cap = need;
-      sch->part_dirty = false;
-    }
-    if (sch->part_dirty) {   // an earlier launch failed between its trace and finalize kernels
-      HIP_TRY(static_cast<hipError_t>(fill_async(sch->part, 0, sch->part_cap * sizeof(unsigned long long), stream)));
-      sch->part_dirty = false;
-    }
-    a.part = sch->part;
-  }
-  // adaptive schedule: dispatch tiles longest first, by the durations the
-  // previous launches of this launch shape on this scene and stream measured
-  // (each launch's added to half the record before it)
-  bool new_shape = false;
-  if (sch) {
-    ScheduleKey key{};
-    key.width = a.width;
-    key.rows = a.rows_out;
-    key.row_begin = a.row_begin;
-    key.row_tile = a.row_tile;
-    key.tile_first = a.tile_first;
-    key.tile_step = a.tile_step;
-    key.gx = gx;
-    key.gy = gy;
-    if (std::memcmp(&sch->key, &key, sizeof key) != 0) {
-      sch->ready = false;
-      sch->sort_pending = false;   // (that record was another shape's)
-      sch->key = key;
-      new_shape = true;
-    }
-  }
-  // the fills this launch needs before its trace kernel, as one launch
+  const bool finalize = split > 1 && !acc_sums;   // the split tiles' sums go through the stream's part buffer
+  if (acc_sums) a.part = acc_sums;
+  else if (finalize)
+    if (const int rc = sch->bind_part(a, static_cast<size_t>(rows) * p->width * 3)) return rc;
+  const bool new_shape =
+      sch && sch->rekey(ScheduleKey{a.width, a.rows_out, a.row_begin, a.row_tile, a.tile_first, a.tile_step, gx, gy});
   FillSet fills;
-  bool first_order = false;   // a shape's first launch in a heuristic order
-  if (sch && g_schedule.load() == 0) {
-    if (sch->cap < n_tiles) {   // grow: this stream's kernels may still read the old buffers
-      HIP_TRY(hipStreamSynchronize(stream));
-      if (sch->cost) (void)hipFree(sch->cost);
-      if (sch->order) (void)hipFree(sch->order);
-      sch->cost = nullptr;
-      sch->order = nullptr;
-      sch->cap = 0;
-      sch->ready = false;
-      sch->sort_pending = false;
-      HIP_TRY(hipMalloc(&sch->cost, n_tiles * sizeof(unsigned)));
-      HIP_TRY(hipMalloc(&sch->order, n_tiles * sizeof(int)));
-      sch->cap = n_tiles;
-    }
-    // the previous launch's record, sorted now (stream-ordered after it)
-    if (sch->sort_pending) HIP_TRY(static_cast<hipError_t>(sort_record(sch, n_tiles, p->spp, stream)));
-    if (sch->ready) {
-      a.tile_order = sch->order;
-    } else if (env_int("RTCLJ_FIRST_ORDER", 1, 0) == 1) {
-      // No record yet: the tiles bottom-up.  The reference's scenes (and
-      // C1-C4) put the ground and its bodies below the sky: the expensive
-      // tiles start first and the launch ends on sky tiles, where row-major
-      // order ended on the ground's.  C1's first frame of a shape 5.13-5.19
-      // ms against 5.25 row-major (tools/first_frame.py, 9 pairs, two
-      // rounds; profiles/r06/first_order/); RTCLJ_FIRST_ORDER=0: row-major.
-      // Tile sharing still balances the tail, as in plain order.
-      int* order = sch->order;
-      int n = n_tiles;
-      void* oargs[] = {&order, &n};
-      HIP_TRY(hipLaunchKernel(reinterpret_cast<const void*>(&iota_rev_kernel), dim3(static_cast<unsigned>((n + 255) / 256)),
-                              dim3(256), oargs, 0, stream));
-      a.tile_order = sch->order;
-      first_order = true;
-    }
-    a.tile_cost = sch->cost;
-    // a split launch in the recorded order: with RTCLJ_SPLIT_PLAN=1, the
-    // cost-balanced units the previous launch of the shape planned (when it
-    // planned this many).  Off by default: C1's 8-GPU shard 1.10-1.15 ms
-    // against 0.99-1.02 with uniform splits, the 4-GPU one 1.93 vs 1.69
-    // (profiles/r04/split_plan/; round 2's cost-sized splits lost the same
-    // way): a heavy tile's many short pools each end with idle lanes.
-    if (split > 1 && sch->ready && sch->plan_units == n_units - n_whole && env_int("RTCLJ_SPLIT_PLAN", 0, 0) != 0)
-      a.unit_tab = sch->units;
-    // the costs decay (order_kernel halves them after sorting): zeroed only
-    // when this launch shape starts a new history
-    if (!sch->ready) fills.add(sch->cost, 0, n_tiles * sizeof(unsigned));
-  }
+  bool first_order = false;
+  if (sch && g_schedule.load() == 0)
+    if (const int rc = sch->bind_order(a, fills, n_tiles, p->spp, split > 1 ? n_units - n_whole : -1, &first_order))
+      return rc;
   if (active) a.tile_order = active;
-  // the grid: the units, then (stealing) the thieves, dispatched last, i.e.
-  // as the units' slots free up in the launch's tail
   int64_t grid = n_units;
   // Sharing balances a launch whose tiles have no cost record (plain order:
   // a process's or a shape's first frame).  In the recorded longest-first
@@ -1366,83 +1399,8 @@ static int launch_impl(const rt_dscene* ds, const rt_camera* c, const rt_params*
   // (C1: 31 vs 11 MB per launch; profiles/r04/share_rounds/): off there
   // unless RTCLJ_SHARE_RECORDED=1.
   if (steal && split == 1 && !acc_sums && (!a.tile_order || first_order || env_int("RTCLJ_SHARE_RECORDED", 0, 0) != 0)) {
-    const int slots = std::max(1, launch_slots(ds->device, v.fn, lds, v.threads));
-    const int n_owner = 2 * slots;   // owner entries: twice the resident workgroups
-    // (at most 32 per slot: a tile's helper count stays below 2^16)
-    grid += static_cast<int64_t>(std::min(32, env_int("RTCLJ_THIEVES", 4, 0))) * slots;
-    if (grid > INT_MAX) grid = n_units;
-    if (!sch->stealc) {
-      HIP_TRY(hipMalloc(&sch->stealc, 2 * sizeof(unsigned long long)));
-      HIP_TRY(static_cast<hipError_t>(fill_async(sch->stealc, 0, 2 * sizeof(unsigned long long), stream)));
-    }
-    if (sch->steal_cap < n_tiles) {   // grow: this stream's kernels may still use the old buffers
-      HIP_TRY(hipStreamSynchronize(stream));
-      if (sch->word) (void)hipFree(sch->word);
-      if (sch->done) (void)hipFree(sch->done);
-      if (sch->sum) (void)hipFree(sch->sum);
-      sch->word = nullptr;
-      sch->done = nullptr;
-      sch->sum = nullptr;
-      sch->steal_cap = 0;
-      const size_t nsum = static_cast<size_t>(n_tiles) * kPoolPx * 3;
-      HIP_TRY(hipMalloc(&sch->word, n_tiles * sizeof(unsigned long long)));
-      HIP_TRY(hipMalloc(&sch->done, n_tiles * sizeof(unsigned)));
-      HIP_TRY(hipMalloc(&sch->sum, nsum * sizeof(unsigned long long)));
-      // words 0: lo = hi, nothing to steal until an owner publishes; sums
-      // and done counts 0 (the kernel keeps them so between uses)
-      HIP_TRY(static_cast<hipError_t>(fill_async(sch->word, 0, n_tiles * sizeof(unsigned long long), stream)));
-      HIP_TRY(static_cast<hipError_t>(fill_async(sch->done, 0, n_tiles * sizeof(unsigned), stream)));
-      HIP_TRY(static_cast<hipError_t>(fill_async(sch->sum, 0, nsum * sizeof(unsigned long long), stream)));
-      sch->steal_cap = n_tiles;
-      new_shape = true;
-    }
-    if (sch->owner_cap != n_owner) {
-      HIP_TRY(hipStreamSynchronize(stream));
-      if (sch->owner) (void)hipFree(sch->owner);
-      sch->owner = nullptr;
-      sch->owner_cap = 0;
-      HIP_TRY(hipMalloc(&sch->owner, n_owner * sizeof(int)));
-      sch->owner_cap = n_owner;
-      new_shape = true;
-    }
-    if (!sch->epoch_started) {   // (RTCLJ_EPOCH_START: tests start a stream near the wrap)
-      sch->epoch = static_cast<unsigned>(std::min(0xffff, env_int("RTCLJ_EPOCH_START", 1, 1)) - 1);
-      sch->epoch_started = true;
-    }
-    sch->epoch = (sch->epoch + 1) & 0xffffu;
-    if (sch->epoch == 0) {   // wrapped: no word or owner entry may carry the epoch's last use
-      sch->epoch = 1;
-      new_shape = true;
-    }
-    a.epoch = sch->epoch;
-    // a new shape (or a wrap): no tile is being run, and no word holds this
-    // launch's epoch.  (Old owner entries would only name words of other
-    // epochs, but tile indices of another shape may exceed this one's; a word
-    // last published 65,535 launches ago carries the epoch a wrap reuses.)
-    if (new_shape) {
-      fills.add(sch->owner, 0xff, n_owner * sizeof(int));
-      fills.add(sch->word, 0, n_tiles * sizeof(unsigned long long));
-    }
-    // owners publish only in the launch's last RTCLJ_SHARE_ROUNDS rounds of
-    // units (default 2; a round = the workgroups the device holds at once.
-    // C4 plain order: WRITE_SIZE 2.90 GB per launch at every round, 0.44 at
-    // 2, 0.60 at 3; C1's timing the same at 1, 2, 3 or every round:
-    // profiles/r04/share_rounds/)
-    a.share_from = static_cast<int>(std::max<int64_t>(
-        0, n_units - static_cast<int64_t>(env_int("RTCLJ_SHARE_ROUNDS", 2, 0)) * slots));
-    a.word = sch->word;
-    a.done = sch->done;
-    a.sum = sch->sum;
-    a.owner = sch->owner;
-    a.n_owner = n_owner;
-    a.stealc = sch->stealc;
-    a.steal_min = env_int("RTCLJ_STEAL_MIN", 256, 1);
-    // claims of up to 1024 samples in the record's longest-first order (the
-    // heavy tiles start first: fewer claims, 6.03 -> 6.00 ms on C1); in plain
-    // order up to 1/48 of the tile's pool (0: the kernel's per-pool rule; C1's
-    // 6,400: 128 -- helpers then need small claims to balance the tail;
-    // C4's 64,000: 1024)
-    a.batch_max = env_int("RTCLJ_BATCH_MAX", (a.tile_order && !first_order) ? 1024 : 0, 0);
+    const int slots = std::max(1, launch_slots(ds->device, v.fn, lds, v.t.threads));
+    if (const int rc = sch->bind_sharing(a, fills, n_tiles, n_units, slots, new_shape, first_order, &grid)) return rc;
   }
   a.n_units = n_units;
   // a wave's claims on an unshared pool: guided (an eighth of what is left
@@ -1450,40 +1408,14 @@ static int launch_impl(const rt_dscene* ds, const rt_camera* c, const rt_params*
   // batches were round 3's: C1 5.960 -> 5.916 ms, C2 287.9 -> 286.1 ms,
   // profiles/r04/lds_batch/)
   a.lds_batch_max = std::max(64, env_int("RTCLJ_LDS_BATCH", 256, 64));
-  // Path export for split launches (KArgs xq; RTCLJ_EXPORT=1, A/B): a wave
-  // whose batches are spent and which holds at most RTCLJ_EXPORT_LIM paths
-  // (default 64: as soon as its batches are spent) writes them out and
-  // leaves, so a unit's workgroup frees its slot without draining; the sweep
-  // launch runs the records.  At most one record per thread of a unit.
   const bool xport = sch && split > 1 && v.sweep && env_int("RTCLJ_EXPORT", 0, 0) != 0;
-  if (xport) {
-    const size_t need = static_cast<size_t>(n_units) * v.threads;
-    if (sch->xq_cap < need) {   // grow: this stream's kernels may still read the old records
-      HIP_TRY(hipStreamSynchronize(stream));
-      if (sch->xq) (void)hipFree(sch->xq);
-      sch->xq = nullptr;
-      sch->xq_cap = 0;
-      HIP_TRY(hipMalloc(&sch->xq, need * 4 * sizeof(uint4)));
-      sch->xq_cap = need;
-    }
-    if (!sch->xq_n) HIP_TRY(hipMalloc(&sch->xq_n, 2 * sizeof(unsigned)));
-    fills.add(sch->xq_n, 0, 2 * sizeof(unsigned));
-    a.xq = sch->xq;
-    a.xq_n = sch->xq_n;
-    a.compact = std::min(64, env_int("RTCLJ_EXPORT_LIM", 64, 1));
-    ++sch->xq_launches;
-  }
-  if (fills.count) {
-    size_t most = 0;
-    for (int k = 0; k < fills.count; ++k) most = std::max(most, fills.n[k]);
-    const size_t blocks = std::max<size_t>(1, std::min<size_t>((most + 255) / 256, 2048));
-    void* fa[] = {&fills};
-    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void*>(&fill_set_kernel), dim3(static_cast<unsigned>(blocks)),
-                            dim3(256), fa, 0, stream));
-  }
-  void* args[] = {&a};
-  if (split > 1 && !acc_sums) sch->part_dirty = true;   // (cleared once finalize_kernel is enqueued)
-  HIP_TRY(hipLaunchKernel(v.fn, dim3(static_cast<unsigned>(grid)), block, args, lds, stream));
+  if (xport)
+    if (const int rc = sch->bind_export(a, fills, static_cast<size_t>(n_units) * v.t.threads)) return rc;
+
+  if (fills.count) HIP_TRY(enqueue_fills(fills, stream));
+  const dim3 block(v.t.threads);
+  if (finalize) sch->part_dirty = true;   // (cleared once finalize_kernel is enqueued)
+  HIP_TRY(enqueue(v.fn, dim3(static_cast<unsigned>(grid)), block, lds, stream, a));
   if (xport) {
     // the sweep: one workgroup per slot the device holds, each starting on
     // its own 256 records and claiming more; a workgroup past the records
@@ -1493,42 +1425,17 @@ static int launch_impl(const rt_dscene* ds, const rt_camera* c, const rt_params*
     b.tile_cost = nullptr;
     b.tile_order = nullptr;
     b.unit_tab = nullptr;
-    b.compact = is_bvh_scan(v.scan) ? std::min(b.mb_paths, env_int("RTCLJ_COMPACT", b.mb_paths, 0)) : 0;
-    const int sw = std::max(1, launch_slots(ds->device, v.sweep, lds, v.threads));
-    void* bargs[] = {&b};
-    HIP_TRY(hipLaunchKernel(v.sweep, dim3(static_cast<unsigned>(sw)), block, bargs, lds, stream));
+    b.compact = is_bvh_scan(v.t.scan) ? std::min(b.mb_paths, env_int("RTCLJ_COMPACT", b.mb_paths, 0)) : 0;
+    const int sw = std::max(1, launch_slots(ds->device, v.sweep, lds, v.t.threads));
+    HIP_TRY(enqueue(v.sweep, dim3(static_cast<unsigned>(sw)), block, lds, stream, b));
   }
-  if (split > 1 && !acc_sums) {
-    unsigned long long* part = a.part;
-    const int* order = a.tile_order;
-    int nw = n_whole, tx = gx, tht = th, w = p->width, nr = rows, spp = p->spp, realm = a.realm;
-    float* out = d_out;
-    void* fargs[] = {&part, &order, &nw, &tx, &tht, &w, &nr, &out, &spp, &realm};
-    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void*>(&finalize_kernel), dim3(n_tiles - n_whole), dim3(kTile * 3 * th),
-                            fargs, 0, stream));
+  if (finalize) {
+    HIP_TRY(enqueue(finalize_kernel, dim3(n_tiles - n_whole), dim3(kTile * 3 * th), 0, stream, a.part, a.tile_order,
+                    n_whole, gx, th, p->width, rows, d_out, p->spp, a.realm));
     sch->part_dirty = false;
   }
-  if (a.tile_cost) {
-    // this record's sort, at the next launch of the shape on the stream
-    // (RTCLJ_SORT_EAGER=1, A/B: right behind this launch, as before round 6;
-    // within noise on every bench.py leg, profiles/r06/sort_ab/)
-    sch->sort_pending = true;
-    sch->ready = false;
-    sch->sort_plan = -1;
-    if (split > 1 && n_whole == 0 && env_int("RTCLJ_SPLIT_PLAN", 0, 0) != 0) {
-      const int U = n_units;
-      if (sch->units_cap < U) {   // grow: this stream's kernels may still read the old plan
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (sch->units) (void)hipFree(sch->units);
-        sch->units = nullptr;
-        sch->units_cap = 0;
-        HIP_TRY(hipMalloc(&sch->units, U * sizeof(int2)));
-        sch->units_cap = U;
-      }
-      sch->sort_plan = U;
-    }
-    if (env_int("RTCLJ_SORT_EAGER", 0, 0) != 0) HIP_TRY(static_cast<hipError_t>(sort_record(sch, n_tiles, p->spp, stream)));
-  }
+  if (a.tile_cost)
+    if (const int rc = sch->record(n_tiles, p->spp, (split > 1 && n_whole == 0) ? n_units : -1)) return rc;
   HIP_TRY(hipGetLastError());
   return RT_OK;
 }
@@ -1540,17 +1447,13 @@ extern "C" int rt_launch(const rt_dscene* ds, const rt_camera* c, const rt_param
   return launch_impl(ds, c, p, d_out, d_counters, hip_stream, nullptr);
 }
 
-// ---- progressive rendering: the accumulator (rt.h) ------------------------
-// The frame's integer sums outlive the launches: rows x width x 3 u64 on the
-// scene's device, and the samples per pixel they hold (host side; a pass
-// counts when it is enqueued).  mu orders the count's updates and the one
-// staging buffer of rt_accum_add.
-struct rt_accum {
+// ---- frame buffers that outlive the launches (rt.h): what rt_accum, rt_adapt
+// and rt_feat share.  Each is on its scene's device and holds a frame shape
+// and the samples it has taken (host side; a pass counts when it is
+// enqueued).  mu orders the count's updates and the entries' host state.
+struct FrameBuf {
   int device = 0;
   rt_params shape{};   // width, height and the row selection (row_tile resolved)
-  size_t n = 0;        // sums: rows_out x width x 3
-  unsigned long long* sums = nullptr;
-  unsigned long long* stage = nullptr;   // rt_accum_add's copy of the caller's sums (n, on first use)
   mutable std::mutex mu;
   int64_t samples = 0;
 };
@@ -1571,70 +1474,121 @@ static bool same_shape(const rt_params& a, const rt_params& b) {
   return a.width == b.width && a.height == b.height && a.row_begin == b.row_begin && a.row_end == b.row_end &&
          a.row_tile == b.row_tile && a.tile_first == b.tile_first && a.tile_step == b.tile_step;
 }
+// a create's shape: *rows = its output rows (> 0)
+static int frame_rows(const char* who, const rt_params& shape, int* rows) {
+  *rows = rows_out(shape);
+  if (shape.width <= 0 || shape.height <= 0 || *rows <= 0)
+    return set_error(RT_E_ARG, std::string(who) + ": bad width/height/row selection");
+  return RT_OK;
+}
+// a pass of p on ds into b (`noun`): the same device, the same shape
+static int check_match(const char* who, const char* noun, const FrameBuf& b, const rt_dscene& ds, const rt_params& p) {
+  if (ds.device != b.device)
+    return set_error(RT_E_ARG, std::string(who) + ": the scene is on device " + std::to_string(ds.device) + ", " + noun +
+                                   " on device " + std::to_string(b.device));
+  if (!same_shape(accum_shape(p), b.shape)) {
+    const std::string n(noun);
+    return set_error(RT_E_ARG, std::string(who) + ": width/height/row selection differ from " + n +
+                                   (n.back() == 's' ? "'" : "'s"));
+  }
+  return RT_OK;
+}
+// ... and room for its samples (the caller holds b.mu)
+static int check_pass(const char* who, const char* noun, const FrameBuf& b, const rt_dscene& ds, const rt_params& p) {
+  if (const int rc = check_match(who, noun, b, ds, p)) return rc;
+  if (p.spp > 0 && b.samples + p.spp > kAccumMaxSamples)
+    return set_error(RT_E_ARG, std::string(who) + ": more than 2^32 - 1 samples per pixel");
+  return RT_OK;
+}
+// sums of `samples` samples per pixel added from the host (the caller holds b.mu)
+static int check_add(const char* who, const FrameBuf& b, int64_t samples) {
+  if (samples < 0 || samples > kAccumMaxSamples || b.samples + samples > kAccumMaxSamples)
+    return set_error(RT_E_ARG, std::string(who) + ": samples negative, or more than 2^32 - 1 per pixel in all");
+  return RT_OK;
+}
+static int64_t frame_samples(const FrameBuf* b) {
+  if (!b) return 0;
+  std::lock_guard<std::mutex> lk(b->mu);
+  return b->samples;
+}
+// a create's new buffer object for `shape` on ds's device, which is made current
+template <class B>
+static int frame_new(const rt_dscene& ds, const rt_params& shape, B** b) {
+  HIP_TRY(hipSetDevice(ds.device));
+  *b = new B;
+  (*b)->device = ds.device;
+  (*b)->shape = accum_shape(shape);
+  return RT_OK;
+}
+// ... handed out once its allocations and first fills (e) are done: the first
+// pass may come on any stream
+template <class B>
+static int frame_created(const char* who, B* b, hipError_t e, B** out) {
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess) {
+    delete b;
+    return hip_fail(e, who);
+  }
+  *out = b;
+  return RT_OK;
+}
+template <class B>
+static int frame_free(B* b) {
+  if (!b) return RT_OK;
+  (void)hipSetDevice(b->device);
+  delete b;
+  return RT_OK;
+}
+static int check_resolve_flags(const char* who, int flags) {
+  if ((flags & ~(RT_FLAG_REALM | RT_FLAG_STREAMED | RT_FLAG_REJECTION_SAMPLERS)) != 0)
+    return set_error(RT_E_ARG, std::string(who) + ": bad flags");
+  return RT_OK;
+}
+
+// ---- progressive rendering: the accumulator (rt.h) ------------------------
+// The frame's integer sums outlive the launches: rows x width x 3 u64 on the
+// scene's device.  mu also orders the one staging buffer of rt_accum_add.
+struct rt_accum : FrameBuf {
+  size_t n = 0;   // sums: rows_out x width x 3
+  DevBuf<unsigned long long> sums;
+  DevBuf<unsigned long long> stage;   // rt_accum_add's copy of the caller's sums (n, on first use)
+};
 
 extern "C" int rt_accum_create(const rt_dscene* ds, const rt_params* shape, rt_accum** out) {
   clear_error();
   if (!ds || !shape || !out) return set_error(RT_E_ARG, "rt_accum_create: NULL argument");
   *out = nullptr;
-  const int rows = rows_out(*shape);
-  if (shape->width <= 0 || shape->height <= 0 || rows <= 0)
-    return set_error(RT_E_ARG, "rt_accum_create: bad width/height/row selection");
-  HIP_TRY(hipSetDevice(ds->device));
-  rt_accum* acc = new rt_accum;
-  acc->device = ds->device;
-  acc->shape = accum_shape(*shape);
+  int rows = 0;
+  if (const int rc = frame_rows("rt_accum_create", *shape, &rows)) return rc;
+  rt_accum* acc = nullptr;
+  if (const int rc = frame_new(*ds, *shape, &acc)) return rc;
   acc->n = static_cast<size_t>(rows) * shape->width * 3;
-  // zeroed before the call returns: the first pass may come on any stream
-  hipError_t e = hipMalloc(&acc->sums, acc->n * sizeof(unsigned long long));
-  if (e == hipSuccess) e = static_cast<hipError_t>(fill_async(acc->sums, 0, acc->n * sizeof(unsigned long long), nullptr));
-  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  if (e != hipSuccess) {
-    if (acc->sums) (void)hipFree(acc->sums);
-    delete acc;
-    return hip_fail(e, "rt_accum_create");
-  }
-  *out = acc;
-  return RT_OK;
+  hipError_t e = acc->sums.alloc(acc->n);
+  if (e == hipSuccess) e = fill_zero(acc->sums, acc->n, nullptr);
+  return frame_created("rt_accum_create", acc, e, out);
 }
 
-extern "C" int rt_accum_free(rt_accum* acc) {
-  if (!acc) return RT_OK;
-  (void)hipSetDevice(acc->device);
-  if (acc->sums) (void)hipFree(acc->sums);
-  if (acc->stage) (void)hipFree(acc->stage);
-  delete acc;
-  return RT_OK;
-}
+extern "C" int rt_accum_free(rt_accum* acc) { return frame_free(acc); }
 
 extern "C" int rt_accum_clear(rt_accum* acc, void* hip_stream) {
   clear_error();
   if (!acc) return set_error(RT_E_ARG, "rt_accum_clear: NULL argument");
   std::lock_guard<std::mutex> lk(acc->mu);
   HIP_TRY(hipSetDevice(acc->device));
-  HIP_TRY(static_cast<hipError_t>(fill_async(acc->sums, 0, acc->n * sizeof(unsigned long long), hip_stream)));
+  HIP_TRY(fill_zero(acc->sums, acc->n, static_cast<hipStream_t>(hip_stream)));
   acc->samples = 0;
   return RT_OK;
 }
 
-extern "C" int64_t rt_accum_samples(const rt_accum* acc) {
-  if (!acc) return 0;
-  std::lock_guard<std::mutex> lk(acc->mu);
-  return acc->samples;
-}
+extern "C" int64_t rt_accum_samples(const rt_accum* acc) { return frame_samples(acc); }
 
 extern "C" int rt_launch_accum(const rt_dscene* ds, const rt_camera* c, const rt_params* p, rt_accum* acc,
                                uint64_t* d_counters, void* hip_stream) {
   clear_error();
   if (!ds || !c || !p || !acc) return set_error(RT_E_ARG, "rt_launch_accum: NULL argument");
-  if (ds->device != acc->device)
-    return set_error(RT_E_ARG, "rt_launch_accum: the scene is on device " + std::to_string(ds->device) +
-                                   ", the accumulator on device " + std::to_string(acc->device));
-  if (!same_shape(accum_shape(*p), acc->shape))
-    return set_error(RT_E_ARG, "rt_launch_accum: width/height/row selection differ from the accumulator's");
   std::lock_guard<std::mutex> lk(acc->mu);
-  if (p->spp > 0 && acc->samples + p->spp > kAccumMaxSamples)
-    return set_error(RT_E_ARG, "rt_launch_accum: more than 2^32 - 1 samples per pixel");
-  const int rc = launch_impl(ds, c, p, nullptr, d_counters, hip_stream, acc->sums, "rt_launch_accum");
+  if (const int rc = check_pass("rt_launch_accum", "the accumulator", *acc, *ds, *p)) return rc;
+  const int rc = launch_impl(ds, c, p, nullptr, d_counters, hip_stream, acc->sums.p, "rt_launch_accum");
   if (rc == RT_OK) acc->samples += p->spp;
   return rc;
 }
@@ -1643,28 +1597,13 @@ static int accum_resolve(const rt_accum* acc, int flags, float* d_f, uint8_t* d_
                          const char* who) {
   clear_error();
   if (!acc || (!d_f && !d_u8)) return set_error(RT_E_ARG, std::string(who) + ": NULL argument");
-  if ((flags & ~(RT_FLAG_REALM | RT_FLAG_STREAMED | RT_FLAG_REJECTION_SAMPLERS)) != 0)
-    return set_error(RT_E_ARG, std::string(who) + ": bad flags");
-  static const QThr thr = [] {
-    QThr t;
-    std::memcpy(t.t, quantize_thresholds(), sizeof t.t);
-    return t;
-  }();
-  int64_t count;
-  {
-    std::lock_guard<std::mutex> lk(acc->mu);
-    count = acc->samples;
-  }
+  if (const int rc = check_resolve_flags(who, flags)) return rc;
+  const int64_t count = frame_samples(acc);
   HIP_TRY(hipSetDevice(acc->device));
-  const unsigned long long* sums = acc->sums;
-  size_t n = acc->n;
-  float nf = static_cast<float>(count > 0 ? count : 1);   // RN(float(n))
-  int realm = (flags & RT_FLAG_REALM) ? 1 : 0;
-  QThr q = thr;
-  const size_t blocks = std::max<size_t>(1, std::min<size_t>((n / 2 + 255) / 256, 4096));
-  void* args[] = {&sums, &n, &nf, &realm, &d_f, &d_u8, &q};
-  HIP_TRY(hipLaunchKernel(reinterpret_cast<const void*>(&resolve_kernel), dim3(static_cast<unsigned>(blocks)), dim3(256),
-                          args, 0, static_cast<hipStream_t>(hip_stream)));
+  const float nf = static_cast<float>(count > 0 ? count : 1);   // RN(float(n))
+  const size_t blocks = std::max<size_t>(1, std::min<size_t>((acc->n / 2 + 255) / 256, 4096));
+  HIP_TRY(enqueue(resolve_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, static_cast<hipStream_t>(hip_stream),
+                  acc->sums.p, acc->n, nf, (flags & RT_FLAG_REALM) ? 1 : 0, d_f, d_u8, quantize_table()));
   return RT_OK;
 }
 
@@ -1681,7 +1620,7 @@ extern "C" int rt_accum_read(const rt_accum* acc, uint64_t* host_sums, void* hip
   if (!acc || !host_sums) return set_error(RT_E_ARG, "rt_accum_read: NULL argument");
   HIP_TRY(hipSetDevice(acc->device));
   const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  HIP_TRY(hipMemcpyAsync(host_sums, acc->sums, acc->n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(host_sums, acc->sums.p, acc->n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   return RT_OK;
 }
@@ -1690,19 +1629,14 @@ extern "C" int rt_accum_add(rt_accum* acc, const uint64_t* host_sums, int64_t sa
   clear_error();
   if (!acc || !host_sums) return set_error(RT_E_ARG, "rt_accum_add: NULL argument");
   std::lock_guard<std::mutex> lk(acc->mu);
-  if (samples < 0 || samples > kAccumMaxSamples || acc->samples + samples > kAccumMaxSamples)
-    return set_error(RT_E_ARG, "rt_accum_add: samples negative, or more than 2^32 - 1 per pixel in all");
+  if (const int rc = check_add("rt_accum_add", *acc, samples)) return rc;
   HIP_TRY(hipSetDevice(acc->device));
   const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  if (!acc->stage) HIP_TRY(hipMalloc(&acc->stage, acc->n * sizeof(unsigned long long)));
-  HIP_TRY(hipMemcpyAsync(acc->stage, host_sums, acc->n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-  unsigned long long* sums = acc->sums;
-  const unsigned long long* add = acc->stage;
-  size_t n = acc->n;
-  const size_t blocks = std::min<size_t>((n + 255) / 256, 4096);
-  void* args[] = {&sums, &add, &n};
-  HIP_TRY(hipLaunchKernel(reinterpret_cast<const void*>(&accum_add_kernel), dim3(static_cast<unsigned>(blocks)), dim3(256),
-                          args, 0, stream));
+  if (!acc->stage) HIP_TRY(acc->stage.alloc(acc->n));
+  HIP_TRY(hipMemcpyAsync(acc->stage.p, host_sums, acc->n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+  const size_t blocks = std::min<size_t>((acc->n + 255) / 256, 4096);
+  HIP_TRY(enqueue(accum_add_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, acc->sums.p, acc->stage.p,
+                  acc->n));
   // the caller's array and the staging copy are free again when this returns
   HIP_TRY(hipStreamSynchronize(stream));
   acc->samples += samples;
@@ -1718,24 +1652,25 @@ extern "C" int rt_accum_add(rt_accum* acc, const uint64_t* host_sums, int64_t sa
 // that pair is copied to `pinned` behind it, and the next step waits for `ev`
 // and takes the two numbers from there: the grid of its launch depends on
 // them.  The pairs alternate so that a kernel zeroes the one the evaluation
-// after it counts in.  mu orders the entries' host state.
-struct rt_adapt {
-  int device = 0;
-  rt_params shape{};
+// after it counts in.  (samples: over all pixels, not per pixel.)
+struct rt_adapt : FrameBuf {
   rt_adapt_opts opts{};
   int rows = 0, gx = 0, gy = 0, n_tiles = 0;
   size_t n = 0;   // sums per half: rows x width x 3
-  unsigned long long* h[2] = {nullptr, nullptr};
-  uint32_t* counts = nullptr;
-  int* list[2] = {nullptr, nullptr};
-  unsigned* state = nullptr;    // device u32[4]
+  DevBuf<unsigned long long> h[2];
+  DevBuf<uint32_t> counts;
+  DevBuf<int> list[2];
+  DevBuf<unsigned> state;       // device u32[4]
   unsigned* pinned = nullptr;   // host u32[2]
   hipEvent_t ev = nullptr;
-  mutable std::mutex mu;
   int step = 0, cur = 0, gen = 0;
   bool pending = false;   // an evaluation's read-back is in flight
   int n_active = 0;
-  int64_t px_active = 0, samples = 0;
+  int64_t px_active = 0;
+  ~rt_adapt() {
+    if (pinned) (void)hipHostFree(pinned);
+    if (ev) (void)hipEventDestroy(ev);
+  }
 };
 
 static const char* adapt_opts_error(const rt_adapt_opts& o) {
@@ -1749,32 +1684,13 @@ static const char* adapt_opts_error(const rt_adapt_opts& o) {
   return nullptr;
 }
 
-static void adapt_release(rt_adapt* ad) {
-  (void)hipSetDevice(ad->device);
-  for (int k = 0; k < 2; ++k) {
-    if (ad->h[k]) (void)hipFree(ad->h[k]);
-    if (ad->list[k]) (void)hipFree(ad->list[k]);
-  }
-  if (ad->counts) (void)hipFree(ad->counts);
-  if (ad->state) (void)hipFree(ad->state);
-  if (ad->pinned) (void)hipHostFree(ad->pinned);
-  if (ad->ev) (void)hipEventDestroy(ad->ev);
-  delete ad;
-}
-
 // step 0, every tile active, sums and counts zero: enqueued on stream
 static hipError_t adapt_reset(rt_adapt* ad, hipStream_t stream) {
   hipError_t e = hipSuccess;
-  for (int k = 0; k < 2 && e == hipSuccess; ++k)
-    e = static_cast<hipError_t>(fill_async(ad->h[k], 0, ad->n * sizeof(unsigned long long), stream));
+  for (int k = 0; k < 2 && e == hipSuccess; ++k) e = fill_zero(ad->h[k], ad->n, stream);
   if (e != hipSuccess) return e;
-  int* list = ad->list[0];
-  uint32_t* counts = ad->counts;
-  unsigned* state = ad->state;
-  int n = ad->n_tiles;
-  void* args[] = {&list, &counts, &state, &n};
-  e = hipLaunchKernel(reinterpret_cast<const void*>(&adapt_reset_kernel), dim3(static_cast<unsigned>((n + 255) / 256)),
-                      dim3(256), args, 0, stream);
+  e = enqueue(adapt_reset_kernel, dim3(static_cast<unsigned>((ad->n_tiles + 255) / 256)), dim3(256), 0, stream,
+              ad->list[0].p, ad->counts.p, ad->state.p, ad->n_tiles);
   ad->step = ad->cur = ad->gen = 0;
   ad->pending = false;
   ad->n_active = ad->n_tiles;
@@ -1790,17 +1706,14 @@ extern "C" int rt_adapt_create(const rt_dscene* ds, const rt_params* shape, cons
   if (!shape || !opts || !out) return set_error(RT_E_ARG, "rt_adapt_create: NULL argument");
   if (const char* why = adapt_opts_error(*opts)) return set_error(RT_E_ARG, std::string("rt_adapt_create: ") + why);
   if (!ds) return set_error(RT_E_ARG, "rt_adapt_create: NULL argument");
-  const int rows = rows_out(*shape);
-  if (shape->width <= 0 || shape->height <= 0 || rows <= 0)
-    return set_error(RT_E_ARG, "rt_adapt_create: bad width/height/row selection");
+  int rows = 0;
+  if (const int rc = frame_rows("rt_adapt_create", *shape, &rows)) return rc;
   const int64_t tiles = static_cast<int64_t>((shape->width + kTile - 1) / kTile) * ((rows + kTile - 1) / kTile);
   // (the resolve's grid has a block row per frame row; the pixel count is a u32)
-  if (rows > 65535 || tiles > INT_MAX / kSplitMax || static_cast<int64_t>(rows) * shape->width > 0xffffffffll)
+  if (rows > 65535 || tiles > INT_MAX / policy::kSplitMax || static_cast<int64_t>(rows) * shape->width > 0xffffffffll)
     return set_error(RT_E_ARG, "rt_adapt_create: frame too large (more than 65535 rows)");
-  HIP_TRY(hipSetDevice(ds->device));
-  rt_adapt* ad = new rt_adapt;
-  ad->device = ds->device;
-  ad->shape = accum_shape(*shape);
+  rt_adapt* ad = nullptr;
+  if (const int rc = frame_new(*ds, *shape, &ad)) return rc;
   ad->opts = *opts;
   ad->rows = rows;
   ad->gx = (shape->width + kTile - 1) / kTile;
@@ -1809,29 +1722,20 @@ extern "C" int rt_adapt_create(const rt_dscene* ds, const rt_params* shape, cons
   ad->n = static_cast<size_t>(rows) * shape->width * 3;
   hipError_t e = hipSuccess;
   for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-    e = hipMalloc(&ad->h[k], ad->n * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc(&ad->list[k], ad->n_tiles * sizeof(int));
+    e = ad->h[k].alloc(ad->n);
+    if (e == hipSuccess) e = ad->list[k].alloc(ad->n_tiles);
   }
-  if (e == hipSuccess) e = hipMalloc(&ad->counts, ad->n_tiles * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(&ad->state, 4 * sizeof(unsigned));
+  if (e == hipSuccess) e = ad->counts.alloc(ad->n_tiles);
+  if (e == hipSuccess) e = ad->state.alloc(4);
   if (e == hipSuccess) e = hipHostMalloc(&ad->pinned, 2 * sizeof(unsigned));
   if (e == hipSuccess) e = hipEventCreateWithFlags(&ad->ev, hipEventDisableTiming);
-  // ready before the call returns: the first step may come on any stream
   if (e == hipSuccess) e = adapt_reset(ad, nullptr);
-  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  if (e != hipSuccess) {
-    adapt_release(ad);
-    return hip_fail(e, "rt_adapt_create");
-  }
-  *out = ad;
-  return RT_OK;
+  return frame_created("rt_adapt_create", ad, e, out);
 }
 
 extern "C" int rt_adapt_free(rt_adapt* ad) {
-  if (!ad) return RT_OK;
-  if (ad->pending) (void)hipEventSynchronize(ad->ev);   // (the copy into `pinned`)
-  adapt_release(ad);
-  return RT_OK;
+  if (ad && ad->pending) (void)hipEventSynchronize(ad->ev);   // (the copy into `pinned`)
+  return frame_free(ad);
 }
 
 extern "C" int rt_adapt_clear(rt_adapt* ad, void* hip_stream) {
@@ -1858,11 +1762,7 @@ extern "C" int rt_adapt_step(const rt_dscene* ds, const rt_camera* c, const rt_p
                              uint64_t* d_counters, void* hip_stream) {
   clear_error();
   if (!ds || !c || !p || !ad) return set_error(RT_E_ARG, "rt_adapt_step: NULL argument");
-  if (ds->device != ad->device)
-    return set_error(RT_E_ARG, "rt_adapt_step: the scene is on device " + std::to_string(ds->device) +
-                                   ", the adaptive frame on device " + std::to_string(ad->device));
-  if (!same_shape(accum_shape(*p), ad->shape))
-    return set_error(RT_E_ARG, "rt_adapt_step: width/height/row selection differ from the adaptive frame's");
+  if (const int rc = check_match("rt_adapt_step", "the adaptive frame", *ad, *ds, *p)) return rc;
   std::lock_guard<std::mutex> lk(ad->mu);
   const rt_adapt_opts& o = ad->opts;
   if (p->sample_begin < 0 || static_cast<int64_t>(p->sample_begin) + o.max_spp > INT_MAX)
@@ -1875,30 +1775,23 @@ extern "C" int rt_adapt_step(const rt_dscene* ds, const rt_camera* c, const rt_p
   q.spp = o.step_spp;
   q.sample_begin = p->sample_begin + ad->step * o.step_spp;
   const int traced = ad->n_active;
-  const int rc = launch_impl(ds, c, &q, nullptr, d_counters, hip_stream, ad->h[ad->step & 1], "rt_adapt_step",
-                             ad->list[ad->cur], traced);
+  const int rc = launch_impl(ds, c, &q, nullptr, d_counters, hip_stream, ad->h[ad->step & 1].p, "rt_adapt_step",
+                             ad->list[ad->cur].p, traced);
   if (rc != RT_OK) return rc;
   ad->samples += ad->px_active * o.step_spp;
   ++ad->step;
   // behind the trace: the tiles' new count, and after an odd step that
   // reached min_spp the rule (at max_spp every tile leaves untested)
-  uint32_t count = static_cast<uint32_t>(ad->step) * static_cast<uint32_t>(o.step_spp);
+  const uint32_t count = static_cast<uint32_t>(ad->step) * static_cast<uint32_t>(o.step_spp);
   const bool even_halves = (ad->step & 1) == 0;
   const bool at_cap = even_halves && count >= static_cast<uint32_t>(o.max_spp);
-  int decide = even_halves && !at_cap && count >= static_cast<uint32_t>(o.min_spp);
-  const unsigned long long *h0 = ad->h[0], *h1 = ad->h[1];
-  int width = ad->shape.width, rows = ad->rows, tiles_x = ad->gx, n_active = traced;
-  const int* active = ad->list[ad->cur];
-  int* next = ad->list[ad->cur ^ 1];
-  unsigned* state = ad->state + 2 * (ad->gen & 1);
-  unsigned* state_next = decide ? ad->state + 2 * ((ad->gen + 1) & 1) : nullptr;
-  uint32_t* counts = ad->counts;
-  uint32_t tol = o.tol_q16;
-  void* args[] = {&h0, &h1, &width, &rows, &tiles_x, &active, &n_active, &next, &state, &state_next, &counts,
-                  &count, &tol, &decide};
-  HIP_TRY(hipLaunchKernel(reinterpret_cast<const void*>(&adapt_eval_kernel),
-                          dim3(static_cast<unsigned>((n_active + kEvalWaves - 1) / kEvalWaves)), dim3(64 * kEvalWaves),
-                          args, 0, stream));
+  const bool decide = even_halves && !at_cap && count >= static_cast<uint32_t>(o.min_spp);
+  unsigned* state = ad->state.p + 2 * (ad->gen & 1);
+  unsigned* state_next = decide ? ad->state.p + 2 * ((ad->gen + 1) & 1) : nullptr;
+  HIP_TRY(enqueue(adapt_eval_kernel, dim3(static_cast<unsigned>((traced + kEvalWaves - 1) / kEvalWaves)),
+                  dim3(64 * kEvalWaves), 0, stream, ad->h[0].p, ad->h[1].p, ad->shape.width, ad->rows, ad->gx,
+                  ad->list[ad->cur].p, traced, ad->list[ad->cur ^ 1].p, state, state_next, ad->counts.p, count,
+                  o.tol_q16, decide ? 1 : 0));
   if (decide) {
     HIP_TRY(hipMemcpyAsync(ad->pinned, state, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipEventRecord(ad->ev, stream));
@@ -1918,34 +1811,20 @@ extern "C" int rt_adapt_active(const rt_adapt* ad) {
   return ad->n_active;
 }
 
-extern "C" int64_t rt_adapt_samples(const rt_adapt* ad) {
-  if (!ad) return 0;
-  std::lock_guard<std::mutex> lk(ad->mu);
-  return ad->samples;
-}
+extern "C" int64_t rt_adapt_samples(const rt_adapt* ad) { return frame_samples(ad); }
 
 static int adapt_resolve(const rt_adapt* ad, int flags, float* d_f, uint8_t* d_u8, void* hip_stream,
                          const char* who) {
   clear_error();
   if (!ad || (!d_f && !d_u8)) return set_error(RT_E_ARG, std::string(who) + ": NULL argument");
-  if ((flags & ~(RT_FLAG_REALM | RT_FLAG_STREAMED | RT_FLAG_REJECTION_SAMPLERS)) != 0)
-    return set_error(RT_E_ARG, std::string(who) + ": bad flags");
-  static const QThr thr = [] {
-    QThr t;
-    std::memcpy(t.t, quantize_thresholds(), sizeof t.t);
-    return t;
-  }();
+  if (const int rc = check_resolve_flags(who, flags)) return rc;
   HIP_TRY(hipSetDevice(ad->device));
-  const unsigned long long *h0 = ad->h[0], *h1 = ad->h[1];
-  const uint32_t* counts = ad->counts;
-  int width = ad->shape.width, tiles_x = ad->gx, realm = (flags & RT_FLAG_REALM) ? 1 : 0;
-  QThr q = thr;
+  const int width = ad->shape.width;
   const unsigned bx = static_cast<unsigned>(std::max(1, std::min((width * 3 / 2 + 255) / 256, 64)));
-  void* args[] = {&h0, &h1, &counts, &width, &tiles_x, &realm, &d_f, &d_u8, &q};
   // (the rows are the grid's y: rt_adapt_create admits at most 65535)
-  HIP_TRY(hipLaunchKernel(reinterpret_cast<const void*>(&adapt_resolve_kernel),
-                          dim3(bx, static_cast<unsigned>(ad->rows)), dim3(256), args, 0,
-                          static_cast<hipStream_t>(hip_stream)));
+  HIP_TRY(enqueue(adapt_resolve_kernel, dim3(bx, static_cast<unsigned>(ad->rows)), dim3(256), 0,
+                  static_cast<hipStream_t>(hip_stream), ad->h[0].p, ad->h[1].p, ad->counts.p, width, ad->gx,
+                  (flags & RT_FLAG_REALM) ? 1 : 0, d_f, d_u8, quantize_table()));
   return RT_OK;
 }
 
@@ -1962,7 +1841,7 @@ extern "C" int rt_adapt_counts(const rt_adapt* ad, uint32_t* host_counts, void* 
   if (!ad || !host_counts) return set_error(RT_E_ARG, "rt_adapt_counts: NULL argument");
   HIP_TRY(hipSetDevice(ad->device));
   const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  HIP_TRY(hipMemcpyAsync(host_counts, ad->counts, ad->n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(host_counts, ad->counts.p, ad->n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   return RT_OK;
 }
@@ -1972,8 +1851,8 @@ extern "C" int rt_adapt_read(const rt_adapt* ad, uint64_t* host_sums0, uint64_t*
   if (!ad || !host_sums0 || !host_sums1) return set_error(RT_E_ARG, "rt_adapt_read: NULL argument");
   HIP_TRY(hipSetDevice(ad->device));
   const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  HIP_TRY(hipMemcpyAsync(host_sums0, ad->h[0], ad->n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(host_sums1, ad->h[1], ad->n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(host_sums0, ad->h[0].p, ad->n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(host_sums1, ad->h[1].p, ad->n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   return RT_OK;
 }
@@ -1982,58 +1861,24 @@ extern "C" int rt_adapt_read(const rt_adapt* ad, uint64_t* host_sums0, uint64_t*
 // Per pixel six 64-bit sums (albedo rgb, normal xyz, 2^-24 units), a u32 hit
 // count and the nearest hit distance as float bits, on the scene's device; the
 // samples per pixel they hold on the host side, as rt_accum keeps them.
-struct rt_feat {
-  int device = 0;
-  rt_params shape{};   // width, height and the row selection (row_tile resolved)
-  size_t n_px = 0;     // rows_out x width
-  unsigned long long* sums = nullptr;   // n_px x 6
-  unsigned* hits = nullptr;             // n_px
-  unsigned* depth = nullptr;            // n_px, float bits (+inf: no hit yet)
-  mutable std::mutex mu;
-  int64_t samples = 0;
+struct rt_feat : FrameBuf {
+  size_t n_px = 0;                   // rows_out x width
+  DevBuf<unsigned long long> sums;   // n_px x 6
+  DevBuf<unsigned> hits;             // n_px
+  DevBuf<unsigned> depth;            // n_px, float bits (+inf: no hit yet)
 };
 
-// Where a feature launch on ds takes its bodies from, classed as
-// resolve_variant classes the path kernel's variants: the selector's scan
-// variants (5, the diagnostic 1-10) and a tree too deep for the stack give the
-// linear scan; 12, or a tree image beyond the LDS budget, the tree in global
-// memory; everything else the tree in LDS.  The tree is the 4-body-leaf one
-// (tree[1]): half the nodes of the 2-body tree, and int body indices (the
-// 8-body tree's are u16).  Budget: blob + stack rows within 160 KB / 5 less
-// the kernel's 3.6 KB of static LDS, five workgroups per CU.
-constexpr size_t kFeatLdsBudget = 160 * 1024 / 5 - 4096;
-static int feat_stack_rows(const DTree& t) { return t.depth + 1; }
-static size_t feat_stack_bytes(const DTree& t) { return static_cast<size_t>(feat_stack_rows(t)) * kFeatThreads * 2; }
-static int feat_source(const rt_dscene& ds, int vsel) {
-  const int v = resolve_variant(ds, vsel);
-  const DTree& t = ds.tree[1];
-  if (v < 11 || t.depth + 2 > kBvhStack) return FEAT_SCAN;
-  if (v == 12 || static_cast<size_t>(t.blob_f4) * 16 + feat_stack_bytes(t) > kFeatLdsBudget) return FEAT_GLOBAL;
-  return FEAT_LDS;
-}
+// the feature kernel for a source of bodies (policy::feat_source)
 static const void* feat_fn(int src) {
   return src == FEAT_LDS      ? reinterpret_cast<const void*>(&feat_kernel<FEAT_LDS>)
          : src == FEAT_GLOBAL ? reinterpret_cast<const void*>(&feat_kernel<FEAT_GLOBAL>)
                               : reinterpret_cast<const void*>(&feat_kernel<FEAT_SCAN>);
 }
-static size_t feat_lds(const rt_dscene& ds, int src) {
-  const DTree& t = ds.tree[1];
-  return src == FEAT_SCAN ? 0 : feat_stack_bytes(t) + (src == FEAT_LDS ? static_cast<size_t>(t.blob_f4) * 16 : 0);
-}
 
-// words of a feature buffer set to v (fill_kernel takes any word: +inf's bits)
-static hipError_t feat_fill(void* p, uint32_t v, size_t words, hipStream_t stream) {
-  uint32_t* w = static_cast<uint32_t*>(p);
-  size_t n = words;
-  const size_t blocks = std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 2048));
-  void* args[] = {&w, &v, &n};
-  return hipLaunchKernel(reinterpret_cast<const void*>(&fill_kernel), dim3(static_cast<unsigned>(blocks)), dim3(256),
-                         args, 0, stream);
-}
 static hipError_t feat_reset(rt_feat* f, hipStream_t stream) {
-  hipError_t e = feat_fill(f->sums, 0u, f->n_px * 12, stream);
-  if (e == hipSuccess) e = feat_fill(f->hits, 0u, f->n_px, stream);
-  if (e == hipSuccess) e = feat_fill(f->depth, 0x7f800000u, f->n_px, stream);
+  hipError_t e = fill_zero(f->sums, f->n_px * 6, stream);
+  if (e == hipSuccess) e = fill_zero(f->hits, f->n_px, stream);
+  if (e == hipSuccess) e = fill_words(f->depth.p, 0x7f800000u, f->n_px, stream);
   return e;
 }
 
@@ -2041,37 +1886,19 @@ extern "C" int rt_feat_create(const rt_dscene* ds, const rt_params* shape, rt_fe
   clear_error();
   if (!ds || !shape || !out) return set_error(RT_E_ARG, "rt_feat_create: NULL argument");
   *out = nullptr;
-  const int rows = rows_out(*shape);
-  if (shape->width <= 0 || shape->height <= 0 || rows <= 0)
-    return set_error(RT_E_ARG, "rt_feat_create: bad width/height/row selection");
-  HIP_TRY(hipSetDevice(ds->device));
-  rt_feat* f = new rt_feat;
-  f->device = ds->device;
-  f->shape = accum_shape(*shape);
+  int rows = 0;
+  if (const int rc = frame_rows("rt_feat_create", *shape, &rows)) return rc;
+  rt_feat* f = nullptr;
+  if (const int rc = frame_new(*ds, *shape, &f)) return rc;
   f->n_px = static_cast<size_t>(rows) * shape->width;
-  // cleared before the call returns: the first pass may come on any stream
-  hipError_t e = hipMalloc(&f->sums, f->n_px * 6 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc(&f->hits, f->n_px * sizeof(unsigned));
-  if (e == hipSuccess) e = hipMalloc(&f->depth, f->n_px * sizeof(unsigned));
+  hipError_t e = f->sums.alloc(f->n_px * 6);
+  if (e == hipSuccess) e = f->hits.alloc(f->n_px);
+  if (e == hipSuccess) e = f->depth.alloc(f->n_px);
   if (e == hipSuccess) e = feat_reset(f, nullptr);
-  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  if (e != hipSuccess) {
-    rt_feat_free(f);
-    return hip_fail(e, "rt_feat_create");
-  }
-  *out = f;
-  return RT_OK;
+  return frame_created("rt_feat_create", f, e, out);
 }
 
-extern "C" int rt_feat_free(rt_feat* f) {
-  if (!f) return RT_OK;
-  (void)hipSetDevice(f->device);
-  if (f->sums) (void)hipFree(f->sums);
-  if (f->hits) (void)hipFree(f->hits);
-  if (f->depth) (void)hipFree(f->depth);
-  delete f;
-  return RT_OK;
-}
+extern "C" int rt_feat_free(rt_feat* f) { return frame_free(f); }
 
 extern "C" int rt_feat_clear(rt_feat* f, void* hip_stream) {
   clear_error();
@@ -2083,31 +1910,20 @@ extern "C" int rt_feat_clear(rt_feat* f, void* hip_stream) {
   return RT_OK;
 }
 
-extern "C" int64_t rt_feat_samples(const rt_feat* f) {
-  if (!f) return 0;
-  std::lock_guard<std::mutex> lk(f->mu);
-  return f->samples;
-}
+extern "C" int64_t rt_feat_samples(const rt_feat* f) { return frame_samples(f); }
 
 extern "C" int rt_launch_feat(const rt_dscene* ds, const rt_camera* c, const rt_params* p, rt_feat* f,
                               uint64_t* d_counters, void* hip_stream) {
   clear_error();
   if (!ds || !c || !p || !f) return set_error(RT_E_ARG, "rt_launch_feat: NULL argument");
-  if (p->width <= 0 || p->height <= 0 || p->spp < 0 || p->spp > RT_MAX_SPP ||
-      (p->flags & ~(RT_FLAG_REALM | RT_FLAG_STREAMED | RT_FLAG_REJECTION_SAMPLERS)) != 0)
-    return set_error(RT_E_ARG, "rt_launch_feat: bad width/height/spp/flags");
-  if (ds->device != f->device)
-    return set_error(RT_E_ARG, "rt_launch_feat: the scene is on device " + std::to_string(ds->device) +
-                                   ", the feature buffers on device " + std::to_string(f->device));
-  if (!same_shape(accum_shape(*p), f->shape))
-    return set_error(RT_E_ARG, "rt_launch_feat: width/height/row selection differ from the feature buffers'");
+  if (const int rc = check_frame_args("rt_launch_feat", *p)) return rc;
   std::lock_guard<std::mutex> lk(f->mu);
-  if (p->spp > 0 && f->samples + p->spp > kAccumMaxSamples)
-    return set_error(RT_E_ARG, "rt_launch_feat: more than 2^32 - 1 samples per pixel");
+  if (const int rc = check_pass("rt_launch_feat", "the feature buffers", *f, *ds, *p)) return rc;
   if (p->spp == 0) return RT_OK;
   const int rows = rows_out(*p);
   HIP_TRY(hipSetDevice(ds->device));
-  const int src = feat_source(*ds, g_variant.load());
+  const policy::Scene si = scene_info(*ds);
+  const int src = policy::feat_source(si, g_variant.load(), kDiag);
   const DTree& tr = ds->tree[1];
   FeatArgs a{};
   a.geo = ds->geo;
@@ -2125,33 +1941,16 @@ extern "C" int rt_launch_feat(const rt_dscene* ds, const rt_camera* c, const rt_
   for (int k = 0; k < 3; ++k) a.bvh_c[k] = tr.c[k];
   a.bvh_r = tr.r;
   a.bvh_c0 = tr.c0;
-  std::memcpy(a.cam + 0, c->center, 12);
-  std::memcpy(a.cam + 3, c->p00, 12);
-  std::memcpy(a.cam + 6, c->du, 12);
-  std::memcpy(a.cam + 9, c->dv, 12);
-  std::memcpy(a.cam + 12, c->disk_u, 12);
-  std::memcpy(a.cam + 15, c->disk_v, 12);
-  a.defocus = c->defocus ? 1 : 0;
-  a.sampler = (p->flags & RT_FLAG_REJECTION_SAMPLERS) ? 0 : (RT_SAMPLER_SPHERE | RT_SAMPLER_DISK);
+  pack_frame(a, *c, *p, rows);
   a.n = ds->n;
-  a.width = p->width;
-  a.rows_out = rows;
-  a.row_begin = p->row_begin;
-  a.row_tile = p->row_tile > 0 ? p->row_tile : 8;
-  a.tile_first = p->tile_first;
-  a.tile_step = p->tile_step;
   a.tiles_x = (p->width + kTile - 1) / kTile;
-  a.spp = p->spp;
-  a.sample_begin = p->sample_begin;
-  a.key = seed_key(p->seed);
-  a.sums = f->sums;
-  a.hits = f->hits;
-  a.depth = f->depth;
+  a.sums = f->sums.p;
+  a.hits = f->hits.p;
+  a.depth = f->depth.p;
   a.counters = reinterpret_cast<unsigned long long*>(d_counters);
   const int gy = (rows + kTile - 1) / kTile;
-  void* args[] = {&a};
-  HIP_TRY(hipLaunchKernel(feat_fn(src), dim3(static_cast<unsigned>(a.tiles_x * gy)), dim3(kFeatThreads), args,
-                          feat_lds(*ds, src), static_cast<hipStream_t>(hip_stream)));
+  HIP_TRY(enqueue(feat_fn(src), dim3(static_cast<unsigned>(a.tiles_x * gy)), dim3(kFeatThreads), policy::feat_lds(si, src),
+                  static_cast<hipStream_t>(hip_stream), a));
   f->samples += p->spp;
   return RT_OK;
 }
@@ -2159,20 +1958,12 @@ extern "C" int rt_launch_feat(const rt_dscene* ds, const rt_camera* c, const rt_
 extern "C" int rt_feat_resolve(const rt_feat* f, float* d_out, void* hip_stream) {
   clear_error();
   if (!f || !d_out) return set_error(RT_E_ARG, "rt_feat_resolve: NULL argument");
-  int64_t count;
-  {
-    std::lock_guard<std::mutex> lk(f->mu);
-    count = f->samples;
-  }
+  const int64_t count = frame_samples(f);
   HIP_TRY(hipSetDevice(f->device));
-  const unsigned long long* sums = f->sums;
-  const unsigned *hits = f->hits, *depth = f->depth;
-  size_t n_px = f->n_px;
-  float nf = static_cast<float>(count > 0 ? count : 1);   // RN(float(n))
-  const size_t blocks = std::max<size_t>(1, std::min<size_t>((n_px + 255) / 256, 4096));
-  void* args[] = {&sums, &hits, &depth, &n_px, &nf, &d_out};
-  HIP_TRY(hipLaunchKernel(reinterpret_cast<const void*>(&feat_resolve_kernel), dim3(static_cast<unsigned>(blocks)),
-                          dim3(256), args, 0, static_cast<hipStream_t>(hip_stream)));
+  const float nf = static_cast<float>(count > 0 ? count : 1);   // RN(float(n))
+  const size_t blocks = std::max<size_t>(1, std::min<size_t>((f->n_px + 255) / 256, 4096));
+  HIP_TRY(enqueue(feat_resolve_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, static_cast<hipStream_t>(hip_stream),
+                  f->sums.p, f->hits.p, f->depth.p, f->n_px, nf, d_out));
   return RT_OK;
 }
 
@@ -2182,9 +1973,9 @@ extern "C" int rt_feat_read(const rt_feat* f, int64_t* host_sums, uint32_t* host
   if (!f || !host_sums || !host_hits || !host_depth) return set_error(RT_E_ARG, "rt_feat_read: NULL argument");
   HIP_TRY(hipSetDevice(f->device));
   const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  HIP_TRY(hipMemcpyAsync(host_sums, f->sums, f->n_px * 6 * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(host_hits, f->hits, f->n_px * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(host_depth, f->depth, f->n_px * sizeof(float), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(host_sums, f->sums.p, f->n_px * 6 * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(host_hits, f->hits.p, f->n_px * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(host_depth, f->depth.p, f->n_px * sizeof(float), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   return RT_OK;
 }
@@ -2194,33 +1985,26 @@ extern "C" int rt_feat_add(rt_feat* f, const int64_t* host_sums, const uint32_t*
   clear_error();
   if (!f || !host_sums || !host_hits || !host_depth) return set_error(RT_E_ARG, "rt_feat_add: NULL argument");
   std::lock_guard<std::mutex> lk(f->mu);
-  if (samples < 0 || samples > kAccumMaxSamples || f->samples + samples > kAccumMaxSamples)
-    return set_error(RT_E_ARG, "rt_feat_add: samples negative, or more than 2^32 - 1 per pixel in all");
+  if (const int rc = check_add("rt_feat_add", *f, samples)) return rc;
   for (size_t i = 0; i < f->n_px; ++i)   // (a depth is a positive distance or +inf: the minimum runs on the bits)
     if (!(host_depth[i] > 0.0f)) return set_error(RT_E_ARG, "rt_feat_add: a depth is not a positive distance or +inf");
   HIP_TRY(hipSetDevice(f->device));
   const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   // one staging block: sums | hits | depth (freed when the call returns)
   const size_t sb = f->n_px * 6 * sizeof(uint64_t), wb = f->n_px * sizeof(uint32_t);
-  char* stage = nullptr;
-  HIP_TRY(hipMalloc(&stage, sb + 2 * wb));
-  hipError_t e = hipMemcpyAsync(stage, host_sums, sb, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(stage + sb, host_hits, wb, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(stage + sb + wb, host_depth, wb, hipMemcpyHostToDevice, stream);
+  DevBuf<char> stage;
+  HIP_TRY(stage.alloc(sb + 2 * wb));
+  hipError_t e = hipMemcpyAsync(stage.p, host_sums, sb, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(stage.p + sb, host_hits, wb, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(stage.p + sb + wb, host_depth, wb, hipMemcpyHostToDevice, stream);
   if (e == hipSuccess) {
-    unsigned long long* sums = f->sums;
-    unsigned *hits = f->hits, *depth = f->depth;
-    const unsigned long long* as = reinterpret_cast<const unsigned long long*>(stage);
-    const unsigned* ah = reinterpret_cast<const unsigned*>(stage + sb);
-    const unsigned* ad = reinterpret_cast<const unsigned*>(stage + sb + wb);
-    size_t n_px = f->n_px;
-    const size_t blocks = std::max<size_t>(1, std::min<size_t>((n_px + 255) / 256, 4096));
-    void* args[] = {&sums, &hits, &depth, &as, &ah, &ad, &n_px};
-    e = hipLaunchKernel(reinterpret_cast<const void*>(&feat_add_kernel), dim3(static_cast<unsigned>(blocks)), dim3(256),
-                        args, 0, stream);
+    const size_t blocks = std::max<size_t>(1, std::min<size_t>((f->n_px + 255) / 256, 4096));
+    e = enqueue(feat_add_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, f->sums.p, f->hits.p,
+                f->depth.p, reinterpret_cast<const unsigned long long*>(stage.p),
+                reinterpret_cast<const unsigned*>(stage.p + sb), reinterpret_cast<const unsigned*>(stage.p + sb + wb),
+                f->n_px);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  (void)hipFree(stage);
   if (e != hipSuccess) return hip_fail(e, "rt_feat_add");
   f->samples += samples;
   return RT_OK;
@@ -2234,15 +2018,9 @@ extern "C" int rt_feat_occupancy(const rt_dscene* ds, int* out4) {
   clear_error();
   if (!ds || !out4) return set_error(RT_E_ARG, "rt_feat_occupancy: NULL argument");
   HIP_TRY(hipSetDevice(ds->device));
-  const int src = feat_source(*ds, g_variant.load());
-  const size_t lds = feat_lds(*ds, src);
-  int blocks = 0;
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, feat_fn(src), kFeatThreads, lds));
-  hipFuncAttributes fa{};
-  HIP_TRY(hipFuncGetAttributes(&fa, feat_fn(src)));
-  out4[0] = blocks;
-  out4[1] = fa.numRegs;
-  out4[2] = static_cast<int>(lds + fa.sharedSizeBytes);
+  const policy::Scene si = scene_info(*ds);
+  const int src = policy::feat_source(si, g_variant.load(), kDiag);
+  if (const int rc = occupancy_report(feat_fn(src), kFeatThreads, policy::feat_lds(si, src), out4)) return rc;
   out4[3] = src;
   return RT_OK;
 }
@@ -2265,18 +2043,17 @@ extern "C" int rt_prepare(int device, double* out_ms4) {
   HIP_TRY(hipFree(nullptr));
   const auto t1 = Clk::now();
   hipFuncAttributes fa{};
-  HIP_TRY(hipFuncGetAttributes(&fa, variant_table(16).fn));
+  HIP_TRY(hipFuncGetAttributes(&fa, variant_fn(policy::kFull4)));
   const auto t2 = Clk::now();
   constexpr size_t kProbe = 64 * 1024;
-  void* d = nullptr;
-  HIP_TRY(hipMalloc(&d, kProbe));
-  hipError_t e = static_cast<hipError_t>(fill_async(d, 0, kProbe, nullptr));
+  DevBuf<uint32_t> d;
+  HIP_TRY(d.alloc(kProbe / 4));
+  hipError_t e = fill_zero(d, kProbe / 4, nullptr);
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   const auto t3 = Clk::now();
   std::vector<unsigned char> host(kProbe);
-  if (e == hipSuccess) e = hipMemcpy(host.data(), d, kProbe, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(host.data(), d.p, kProbe, hipMemcpyDeviceToHost);
   const auto t4 = Clk::now();
-  (void)hipFree(d);
   if (e != hipSuccess) return hip_fail(e, "rt_prepare");
   if (out_ms4) {
     out_ms4[0] = ms(t0, t1);
@@ -2314,14 +2091,12 @@ extern "C" int rt_steal_stats(const rt_dscene* ds, void* hip_stream, uint64_t* o
   out2[0] = out2[1] = 0;
   const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   std::lock_guard<std::mutex> lk(ds->sched.mu);
-  for (int k = 0; k < ds->sched.used; ++k) {
-    const Schedule& e = ds->sched.s[k];
-    if (e.stream != stream || !e.stealc) continue;
-    HIP_TRY(hipSetDevice(ds->device));
-    HIP_TRY(hipStreamSynchronize(stream));
-    HIP_TRY(hipMemcpy(out2, e.stealc, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(e.stealc, 0, 2 * sizeof(uint64_t)));
-  }
+  const Schedule* e = ds->sched.find(stream);
+  if (!e || !e->stealc) return RT_OK;
+  HIP_TRY(hipSetDevice(ds->device));
+  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipMemcpy(out2, e->stealc.p, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemset(e->stealc.p, 0, 2 * sizeof(uint64_t)));
   return RT_OK;
 }
 
@@ -2334,17 +2109,15 @@ extern "C" int rt_export_stats(const rt_dscene* ds, void* hip_stream, uint64_t* 
   out2[0] = out2[1] = 0;
   const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   std::lock_guard<std::mutex> lk(ds->sched.mu);
-  for (int k = 0; k < ds->sched.used; ++k) {
-    Schedule& e = ds->sched.s[k];
-    if (e.stream != stream || !e.xq_n) continue;
-    HIP_TRY(hipSetDevice(ds->device));
-    HIP_TRY(hipStreamSynchronize(stream));
-    unsigned n[2] = {0, 0};
-    HIP_TRY(hipMemcpy(n, e.xq_n, sizeof n, hipMemcpyDeviceToHost));
-    out2[0] = e.xq_launches;
-    out2[1] = n[0];
-    e.xq_launches = 0;
-  }
+  Schedule* e = ds->sched.find(stream);
+  if (!e || !e->xq_n) return RT_OK;
+  HIP_TRY(hipSetDevice(ds->device));
+  HIP_TRY(hipStreamSynchronize(stream));
+  unsigned n[2] = {0, 0};
+  HIP_TRY(hipMemcpy(n, e->xq_n.p, sizeof n, hipMemcpyDeviceToHost));
+  out2[0] = e->xq_launches;
+  out2[1] = n[0];
+  e->xq_launches = 0;
   return RT_OK;
 }
 
@@ -2363,3 +2136,4 @@ extern "C" int rt_debug_waves(int device, uint64_t* out, size_t n_waves) {
   HIP_TRY(hipMemset(g_dbgw[device], 0, 4 * kDbgWaves * sizeof(uint64_t)));
   return static_cast<int>(n_waves);
 }
+

@@ -570,37 +570,30 @@ __global__ __launch_bounds__(kSortThreads, 6) void sorted_kernel(const KArgs a) 
 }
 
 
-// the diagnostic variants (trace.hip's variant_table asks here for all but
-// 0, 5, 12, 16, 18 and 22)
-const Variant* diag_variant(int v) {
-  static const Variant t[] = {
-      {nullptr, false, false, 0},                                          // 0 (product)
-      {RT_K(SRC_LDS, SCAN_SIMPLE, false), true, false, SCAN_SIMPLE},       // 1
-      {RT_K(SRC_SCALAR, SCAN_SIMPLE, false), false, false, SCAN_SIMPLE},   // 2
-      {RT_K(SRC_LDS, SCAN_SIMPLE, true), true, true, SCAN_SIMPLE},         // 3
-      {RT_K(SRC_LDS, SCAN_GROUP4, false), true, false, SCAN_GROUP4},       // 4
-      {nullptr, false, false, 0},                                          // 5 (product)
-      {RT_K(SRC_LDS, SCAN_GROUP4, true), true, true, SCAN_GROUP4},         // 6
-      {RT_K(SRC_SCALAR, SCAN_GROUP4, true), false, true, SCAN_GROUP4},     // 7
-      {RT_K(SRC_LDS, SCAN_PK4, false), true, false, SCAN_PK4},             // 8
-      {RT_K(SRC_SCALAR, SCAN_PK4, false), false, false, SCAN_PK4},         // 9
-      {RT_K(SRC_SCALAR, SCAN_PK4, true), false, true, SCAN_PK4},           // 10
-      {RT_K(SRC_LDS, SCAN_BVH, false), true, false, SCAN_BVH},             // 11
-      {nullptr, false, false, 0},                                          // 12 (product)
-      {RT_K(SRC_LDS, SCAN_BVH, true), true, true, SCAN_BVH},               // 13
-      {nullptr, false, false, 0},                                          // 14 (dropped: while-while traversal)
-      {nullptr, false, false, 0},                                          // 15 (dropped: its stats build)
-      {nullptr, false, false, 0},                                          // 16 (product)
-      {RT_K(SRC_LDS, SCAN_BVHQ, true), true, true, SCAN_BVHQ},             // 17
-      {nullptr, false, false, 0},                                          // 18 (product)
-      {RT_KW(SRC_LDS, SCAN_BVHO, true, 8), true, true, SCAN_BVHO, 512},    // 19
-      // direction-coherent waves (A/B, measured slower: profiles/r04/sorted_waves/):
-      // octant-sorted, and lock-step packing only
-      {reinterpret_cast<const void*>(&sorted_kernel<true>), true, false, SCAN_BVHS, kSortThreads},    // 20
-      {reinterpret_cast<const void*>(&sorted_kernel<false>), true, false, SCAN_BVHS, kSortThreads},   // 21
-  };
-  constexpr int nt = static_cast<int>(sizeof t / sizeof t[0]);
-  return (v > 0 && v < nt && t[v].fn) ? &t[v] : nullptr;
+// the diagnostic variants' kernels (trace.hip's variant_fn asks here for what
+// the product library lacks: variant_policy.h's BUILD_DIAG rows, whose scan,
+// staging and statistics columns these template arguments repeat)
+const void* diag_kernel(int v) {
+  switch (v) {
+    case 1: return RT_K(SRC_LDS, SCAN_SIMPLE, false);
+    case 2: return RT_K(SRC_SCALAR, SCAN_SIMPLE, false);
+    case 3: return RT_K(SRC_LDS, SCAN_SIMPLE, true);
+    case 4: return RT_K(SRC_LDS, SCAN_GROUP4, false);
+    case 6: return RT_K(SRC_LDS, SCAN_GROUP4, true);
+    case 7: return RT_K(SRC_SCALAR, SCAN_GROUP4, true);
+    case 8: return RT_K(SRC_LDS, SCAN_PK4, false);
+    case 9: return RT_K(SRC_SCALAR, SCAN_PK4, false);
+    case 10: return RT_K(SRC_SCALAR, SCAN_PK4, true);
+    case 11: return RT_K(SRC_LDS, SCAN_BVH, false);
+    case 13: return RT_K(SRC_LDS, SCAN_BVH, true);
+    case 17: return RT_K(SRC_LDS, SCAN_BVHQ, true);
+    case 19: return RT_KW(SRC_LDS, SCAN_BVHO, true, 8);
+    // direction-coherent waves (A/B, measured slower: profiles/r04/sorted_waves/):
+    // octant-sorted, and lock-step packing only
+    case 20: return reinterpret_cast<const void*>(&sorted_kernel<true>);
+    case 21: return reinterpret_cast<const void*>(&sorted_kernel<false>);
+  }
+  return nullptr;   // (14, 15 dropped: the while-while traversal and its stats build)
 }
 
 }  // namespace rtclj

@@ -394,6 +394,14 @@ constexpr bool is_bvh_scan(int scan) { return (scan >= SCAN_BVH && scan <= SCAN_
 constexpr bool is_q(int scan) { return scan == SCAN_BVHQ || scan == SCAN_BVHQ7; }
 // body pairs per leaf of the tree a traversal variant walks
 constexpr int leaf_pairs(int scan) { return scan == SCAN_BVHO ? 4 : is_q(scan) ? 2 : 1; }
+// What the host sizes a launch by (variant_policy.h's table holds these per
+// variant; trace.hip asserts the two agree).  The tree a scan walks: 0 =
+// 2-body leaves, 1 = 4, 2 = 8
+constexpr int scan_tree(int scan) { return scan == SCAN_BVHO ? 2 : (is_q(scan) || scan == SCAN_BVHS) ? 1 : 0; }
+// the compact image: u8 node-index stack, u32 pixel sums
+constexpr bool is_compact_scan(int scan) { return scan == SCAN_BVHQ7; }
+// bytes of a traversal stack entry: u8 node indices, else u16 addresses
+constexpr int stack_entry_bytes(int scan) { return (scan == SCAN_BVHO || scan == SCAN_BVHQ7) ? 1 : 2; }
 
 // two bodies side by side for packed fp32 math (v_pk_*_f32: one IEEE op per half)
 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -1929,23 +1937,14 @@ constexpr int kXWaveWords = kXFields * 64;        // a wave's slots (u32)
 constexpr size_t kXBytes = static_cast<size_t>(kSortWaves) * kXWaveWords * 4;   // 22,528
 
 
-// A kernel variant (rt_set_variant; trace.hip's table, trace_diag.hip's
-// diagnostic entries)
-struct Variant {
-  const void* fn;
-  bool lds;
-  bool stats;
-  int scan;   // SCAN_* (the tile shape: tile_rows, unless th)
-  int threads = 256;   // workgroup size
-  int th = 0;          // the pool's tile rows (0: tile_rows(scan))
-  const void* sweep = nullptr;   // the variant's sweep kernel (path export, KArgs::xq), or NULL
-};
-inline int variant_rows(const Variant& v) { return v.th ? v.th : tile_rows(v.scan); }
+// A kernel variant's (rt_set_variant) kernel: trace.hip's variant_fn,
+// trace_diag.hip's diag_kernel.  Its traits -- scan, workgroup size, tile
+// rows, LDS staging, statistics -- are a row of variant_policy.h's table.
 #define RT_K(SRC, SCAN, ST) reinterpret_cast<const void*>(&trace_kernel<SRC, SCAN, ST>)
 #define RT_KW(SRC, SCAN, ST, NW) reinterpret_cast<const void*>(&trace_kernel<SRC, SCAN, ST, NW>)
 #define RT_KWT(SRC, SCAN, ST, NW, TH) reinterpret_cast<const void*>(&trace_kernel<SRC, SCAN, ST, NW, TH>)
 #define RT_KSW(SRC, SCAN, NW, TH) reinterpret_cast<const void*>(&trace_kernel<SRC, SCAN, false, NW, TH, true>)
-// The diagnostic library's variants (trace_diag.hip): v's entry, or NULL.
-const Variant* diag_variant(int v);
+// The diagnostic library's variants (trace_diag.hip): v's kernel, or NULL.
+const void* diag_kernel(int v);
 
 }  // namespace rtclj

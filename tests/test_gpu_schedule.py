@@ -27,13 +27,13 @@ def env(gpu_lib):
 
 
 def _launch(env, cam, w, h, spp, stream=None, seed=1, rows=None, row_tile=0, tile_first=0, tile_step=0,
-            sample_begin=0, dll=None, ds=None):
+            sample_begin=0, dll=None, ds=None, max_depth=50):
     sc, ds0, torch = env
     from rtclj._lib import check, lib, rt_params
     ds = ds if ds is not None else ds0
     dll = dll if dll is not None else lib
     r0, r1 = rows or (0, h)
-    p = rt_params(width=w, height=h, row_begin=r0, row_end=r1, spp=spp, max_depth=50, seed=seed,
+    p = rt_params(width=w, height=h, row_begin=r0, row_end=r1, spp=spp, max_depth=max_depth, seed=seed,
                   sample_begin=sample_begin, row_tile=row_tile, tile_first=tile_first, tile_step=tile_step)
     n = check(lib.rt_rows_out(C.byref(p)))
     s = stream or torch.cuda.current_stream()
@@ -296,3 +296,54 @@ def test_cost_balanced_splits_are_bit_exact(env, split_env, monkeypatch):
             got = _launch(env, cam, w, h, spp)
             assert np.array_equal(got, want[spp]), (plan, spp)
     monkeypatch.delenv("RTCLJ_SPLIT_PLAN")
+
+
+@pytest.mark.parametrize("knobs", [
+    dict(RTCLJ_SPLIT="1"),                          # whole tiles in a first order: cost / order, word / done / sum
+    dict(RTCLJ_SPLIT="2"),                          # the split tiles' sums: part
+    dict(RTCLJ_SPLIT="2", RTCLJ_SPLIT_PLAN="1"),    # the planned units
+    dict(RTCLJ_SPLIT="2", RTCLJ_EXPORT="1"),        # the exported paths' records: xq
+    dict(RTCLJ_SPLIT="1", small_variant="16"),      # another kernel's resident workgroups: owner
+], ids=lambda k: "-".join(f"{n[6:].lower()}{v}" for n, v in k.items()))
+def test_buffers_regrow_from_a_smaller_shape(env, monkeypatch, knobs):
+    """A stream's per-shape buffers grow when a larger frame follows a smaller
+    one on the same stream of the same scene (the old buffers freed behind a
+    stream synchronisation, the new ones filled as a first launch's): the
+    reference five-body scene at 16 x 8, then twice at 64 x 40 (the second in
+    the recorded order, with the plan where one is made), each equal to the
+    frame a freshly uploaded scene gives under the same knobs.  The owner
+    table is sized by the kernel's resident workgroups, not the frame: its
+    case runs the small frame on variant 16, the large ones on the default."""
+    from rtclj import raytracing as R
+    from rtclj._lib import check, lib
+    torch = env[2]
+    for k in ("RTCLJ_SPLIT", "RTCLJ_SPLIT_PLAN", "RTCLJ_EXPORT"):
+        monkeypatch.delenv(k, raising=False)
+    knobs = dict(knobs)
+    small_variant = int(knobs.pop("small_variant", 0))
+    for k, v in knobs.items():
+        monkeypatch.setenv(k, v)
+    sc = R.Scene.from_bodies(R.hittables)
+    scenes_ = [C.c_void_p(), C.c_void_p()]
+    for ds in scenes_:
+        check(lib.rt_scene_upload(0, C.byref(sc.c), C.byref(ds)))
+    try:
+        grown, fresh = scenes_
+        stream, other = torch.cuda.Stream(), torch.cuda.Stream()
+        shot = dict(spp=4, max_depth=8)
+        cam_s, cam_l = R.camera(16, 8, **R.REFERENCE_CAMERA), R.camera(64, 40, **R.REFERENCE_CAMERA)
+        old = lib.rt_set_variant(small_variant)
+        try:
+            small = _launch(env, cam_s, 16, 8, stream=stream, ds=grown, **shot)
+        finally:
+            lib.rt_set_variant(old)
+        assert not np.isnan(small).any()
+        want = [_launch(env, cam_l, 64, 40, stream=other, ds=fresh, **shot) for _ in range(2)]
+        assert not np.isnan(want[0]).any() and np.array_equal(want[0], want[1])
+        for k in range(2):
+            got = _launch(env, cam_l, 64, 40, stream=stream, ds=grown, **shot)
+            assert np.array_equal(got, want[k]), k
+        assert np.array_equal(_launch(env, cam_s, 16, 8, stream=stream, ds=grown, **shot), small)
+    finally:
+        for ds in scenes_:
+            lib.rt_scene_free(ds)
