@@ -475,6 +475,15 @@ int rt_adapt_resolve(const rt_adapt* ad, int flags, float* d_out, void* hip_stre
  * table (raytracing.clj:141-155, :19-26): the bytes rt_quantize gives for
  * rt_adapt_resolve's floats. */
 int rt_adapt_resolve_u8(const rt_adapt* ad, int flags, uint8_t* d_out, void* hip_stream);
+/* One half of the frame as a frame of its own (raytracing.clj:141-155, :155),
+ * so that an adaptive frame's two estimates feed rt_denoise without a trip
+ * through the host.  Asynchronous, non-destructive: d_out (device,
+ * rt_rows_out x width x 3 floats) = per channel RN(float(H[half])) * 2^-24 /
+ * RN(float(max(count[tile] / 2, 1))), or * (1 / that) with RT_FLAG_REALM in
+ * flags (the only flag read) -- what rt_adapt_resolve_host gives for
+ * (H[half], zeros, counts / 2).  After an even number of steps each half
+ * holds count / 2 samples.  RT_E_ARG for a half outside {0, 1}. */
+int rt_adapt_resolve_half(const rt_adapt* ad, int half, int flags, float* d_out, void* hip_stream);
 /* raytracing.clj:141-155: the gy x gx samples per pixel of the tiles, the
  * frame's sample heat map, copied to host_counts behind hip_stream's work;
  * returns when they are there. */
@@ -583,6 +592,104 @@ int rt_feat_resolve_host(const int64_t* sums, const uint32_t* hits, const float*
  * per CU, VGPRs per lane, LDS bytes per workgroup, the bodies' source: 0 = BVH
  * in LDS, 1 = BVH in global memory, 2 = linear scan}. */
 int rt_feat_occupancy(const rt_dscene* ds, int* out4);
+
+/* ---- feature-guided denoiser: an a-trous filter over rt_feat's guides --------
+ * What a low-sample frame of compute-pixel's loop (raytracing.clj:141-155)
+ * looks like after an edge-avoiding a-trous wavelet filter (Dammertz et al.
+ * 2010) guided by rt_feat_resolve's eight channels, run on albedo-demodulated
+ * colour, its colour edge-stop scaled by the variance two half-frames give (the
+ * SVGF manner).  The result is a function of the inputs and options alone: a
+ * fixed sequence of single fp32 operations, each rounded once in the order
+ * written (no fma; / and sqrt IEEE), which the device kernels, rt_denoise_host
+ * and a NumPy restatement (tests/test_denoise_host.py) give bit for bit,
+ * whatever the workgroup shape.
+ *
+ * Inputs, for a contiguous rows x width image (neighbours in the arrays must
+ * be neighbours in the picture: a compacted interleaved shard, tile_step > 0,
+ * is gathered first):
+ *   half0, half1  rows x width x 3 floats each: two estimates of the frame from
+ *                 disjoint, equally large sample sets (two rt_accum over sample
+ *                 ranges [0, n) and [n, 2 n); rt_adapt_resolve_half's two);
+ *   feat          rows x width x 8 floats in rt_feat_resolve's layout: albedo
+ *                 rgb, normal xyz, depth (+inf where nothing was hit), coverage.
+ * Options (NULL: the defaults; outside the ranges: RT_E_ARG):
+ *   levels       5     1..8      a-trous levels, step 2^i at level i
+ *   normal_pow2  5     0..8      the normal weight is squared this many times
+ *   sigma_c      4.0   finite > 0  colour edge-stop, in standard deviations
+ *   sigma_z      0.05  finite > 0  depth edge-stop, relative depth per pixel
+ *
+ * Prep, per pixel p:
+ *   alb_c = max(feat_c, 2^-10), c = r, g, b
+ *   ia = half0 / alb, ib = half1 / alb, m = 0.5 * (ia + ib)
+ *   lum(x) = (x_r * 0.2126f + x_g * 0.7152f) + x_b * 0.0722f
+ *   d = lum(ia) - lum(ib), var = (0.25f * d) * d
+ *   texel (m_r, m_g, m_b, var); guides n = feat[3..5], z = feat[6],
+ *   cov = feat[7], the same at every level.
+ * Level i = 0 .. levels - 1, step s = 2^i, from the previous texels to new ones:
+ *   1. vbar_p = the 3 x 3 binomial mean of var at step 1: weights
+ *      k = g[dy] * g[dx], g = {1/4, 1/2, 1/4} (exact), taps row-major (dy outer)
+ *      over -1..1, taps outside the image skipped, num += k * var_q and
+ *      den += k from 0 in that order, vbar = num / den.
+ *   2. sd = sqrt(vbar) * sigma_c + 1e-6f.
+ *   3. Taps (dy, dx), each -2..2, row-major (dy outer), at q = p + s * (dx, dy),
+ *      those outside the image skipped; k = h[dy] * h[dx],
+ *      h = {1/16, 1/4, 3/8, 1/4, 1/16} (exact).  The centre tap has w = k.
+ *      Every other tap:
+ *        dn = min(1, max(0, ((n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z)
+ *                           + (1 - cov_p) * (1 - cov_q)))
+ *             (sky agrees with sky; a surface never agrees with sky)
+ *        wn = dn, squared normal_pow2 times
+ *        wz = 1 where z_p and z_q are both +inf, 0 where exactly one is, else
+ *             r = |z_p - z_q| / ((sigma_z * float(s * max(|dx|, |dy|))) * min(z_p, z_q)),
+ *             wz = 1 / (1 + r * r)
+ *        rc = |lum(m_p) - lum(m_q)| / sd, wc = 1 / (1 + rc * rc)
+ *        w = ((k * wn) * wz) * wc
+ *      and in tap order, from 0:  acc_c += w * m_q.c,  accv += (w * w) * var_q,
+ *      wsum += w.
+ *   4. m' = acc / wsum, var' = accv / (wsum * wsum)  (wsum >= 9/64: the centre).
+ * Output: out_c = m_c * alb_c after the last level.
+ *
+ * To know: the filter biases (it trades noise for blur: the more samples a
+ * frame holds the less it gains); glass and mirrors are guided
+ * by their first hit only, so what they show is filtered as one surface; the
+ * depth term is relative depth per pixel of tap distance, not distance from a
+ * plane, so ground seen at a grazing angle is filtered less.
+ *
+ * The inputs are never written.  out may not overlap an input (RT_E_ARG).
+ * Inputs are expected as the library produces them (finite colours, features
+ * as rt_feat_resolve writes them); other values -- NaN, a depth <= 0 -- give
+ * unspecified numbers, never an out-of-bounds access, a fault or a hang. */
+typedef struct rt_denoise_opts {
+  int levels, normal_pow2;
+  float sigma_c, sigma_z;
+} rt_denoise_opts;
+typedef struct rt_denoiser rt_denoiser;
+/* raytracing.clj:141-155's frame, filtered: a denoiser for rows x width images
+ * on `device`.  It owns the two ping-pong texel buffers and the packed guides
+ * (16 + 16 + 16 + 4 = 52 bytes per pixel) and nothing else.
+ * RT_E_ARG on width or rows <= 0 or more than 2^31 - 1 pixels, RT_E_NODEV on
+ * a device that is not there. */
+int rt_denoiser_create(int device, int width, int rows, rt_denoiser** out);
+int rt_denoiser_free(rt_denoiser* dn);   /* NULL: 0 */
+/* Asynchronous: enqueue the filter on hip_stream (NULL: the default stream) of
+ * the denoiser's device: the prep, then one kernel per level, the last of
+ * which writes d_out (device, rows x width x 3 floats).  d_half0, d_half1 and
+ * d_feat are device pointers, aligned as floats.  Calls on one denoiser share
+ * its scratch: they go on one stream, or are ordered by the caller.  RT_E_ARG
+ * on a NULL argument, bad options, d_out overlapping an input, or a stream of
+ * another device. */
+int rt_denoise(rt_denoiser* dn, const rt_denoise_opts* o, const float* d_half0, const float* d_half1,
+               const float* d_feat, float* d_out, void* hip_stream);
+/* rt_denoise with a HIP event behind every kernel (diagnostic; synchronous,
+ * raytracing.clj:141-155's frame as above): waits for the filter, then out_ms
+ * (levels + 2 floats) = the milliseconds of the prep, of each level in order,
+ * and of the whole from the first event to the last. */
+int rt_denoise_profile(rt_denoiser* dn, const rt_denoise_opts* o, const float* d_half0, const float* d_half1,
+                       const float* d_feat, float* d_out, void* hip_stream, float* out_ms);
+/* The same on the host, in plain C++ (no device; raytracing.clj:141-155): the
+ * yardstick of the kernels, and a filter for frames that are on the host. */
+int rt_denoise_host(const rt_denoise_opts* o, const float* half0, const float* half1, const float* feat,
+                    int width, int rows, float* out);
 
 /* Asynchronous: enqueue rt_quantize on hip_stream's device for n channels
  * already in HBM (d_lin: n floats, d_out: n bytes, device pointers): the same

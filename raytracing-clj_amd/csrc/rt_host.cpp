@@ -30,6 +30,7 @@
 #include <thread>
 #include <vector>
 
+#include "denoise.h"
 #include "first_hit.h"
 #include "rt_internal.h"
 
@@ -259,6 +260,42 @@ extern "C" int rt_feat_resolve_host(const int64_t* sums, const uint32_t* hits, c
     for (int c = 0; c < 6; ++c) s[c] = sums[i * 6 + c];
     rtclj::fh_resolve(s, hits[i], depth[i], nf, out + i * RT_FEAT_CHANNELS);
   }
+  return RT_OK;
+}
+
+// rt_denoise on the host (denoise.h's dn_prep / dn_level_pixel / dn_finish,
+// the text the kernels run): the prep, `levels` passes between two texel
+// arrays, the colour times the albedo again
+static bool dn_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+extern "C" int rt_denoise_host(const rt_denoise_opts* o, const float* half0, const float* half1, const float* feat,
+                               int width, int rows, float* out) {
+  clear_error();
+  if (!half0 || !half1 || !feat || !out) return set_error(RT_E_ARG, "rt_denoise_host: NULL argument");
+  if (width <= 0 || rows <= 0 || static_cast<int64_t>(width) * rows > 0x7fffffffll)
+    return set_error(RT_E_ARG, "rt_denoise_host: bad width/rows");
+  const rt_denoise_opts opt = o ? *o : dn_default_opts();
+  if (const char* why = dn_opts_error(opt)) return set_error(RT_E_ARG, std::string("rt_denoise_host: ") + why);
+  const size_t n_px = static_cast<size_t>(width) * rows, fb = sizeof(float);
+  if (dn_overlap(out, n_px * 3 * fb, half0, n_px * 3 * fb) || dn_overlap(out, n_px * 3 * fb, half1, n_px * 3 * fb) ||
+      dn_overlap(out, n_px * 3 * fb, feat, n_px * RT_FEAT_CHANNELS * fb))
+    return set_error(RT_E_ARG, "rt_denoise_host: out overlaps an input");
+  std::vector<DnTexel> tex[2] = {std::vector<DnTexel>(n_px), std::vector<DnTexel>(n_px)};
+  std::vector<DnGuide> guide(n_px);
+  std::vector<float> omc(n_px);
+  for (size_t i = 0; i < n_px; ++i)
+    dn_prep(half0 + 3 * i, half1 + 3 * i, feat + RT_FEAT_CHANNELS * i, &tex[0][i], &guide[i], &omc[i]);
+  for (int lv = 0; lv < opt.levels; ++lv) {
+    const DnArrays a{tex[lv & 1].data(), guide.data(), omc.data(), width};
+    std::vector<DnTexel>& dst = tex[(lv & 1) ^ 1];
+    for (int y = 0; y < rows; ++y)
+      for (int x = 0; x < width; ++x)
+        dst[a.at(x, y)] = dn_level_pixel(a, x, y, width, rows, 1 << lv, opt.normal_pow2, opt.sigma_c, opt.sigma_z);
+  }
+  const std::vector<DnTexel>& last = tex[opt.levels & 1];
+  for (size_t i = 0; i < n_px; ++i) dn_finish(last[i], feat + RT_FEAT_CHANNELS * i, out + 3 * i);
   return RT_OK;
 }
 

@@ -16,7 +16,7 @@
 //           [--seed S] [--gpus N] [--out PATH] [--png PATH] [--no-png] [--json]
 //           [--host-quantize] [--rejection-samplers] [--passes K]
 //           [--adaptive TOLQ16 [--step S] [--min-spp A] [--max-spp B]]
-//           [--features STEM]
+//           [--features STEM] [--denoise STEM]
 // Defaults follow the reference: spp 100, depth 50, width 400, 16:9.
 // --passes K: the spp in K near-equal accumulating passes on device 0
 // (rt_launch_accum into an rt_accum, the sums read back, rt_resolve_sums and
@@ -33,6 +33,12 @@
 // normal xyz, depth = the nearest hit, coverage; row-major, as the host
 // stores them), STEM.albedo.png the albedo through rt_quantize,
 // STEM.normal.png the bytes floor(255 * clamp(0.5 n + 0.5, 0, 1) + 0.5), linear.
+// --denoise STEM: after the render, the frame once more on device 0 as two
+// accumulators of spp / 2 samples each (sample indices [0, spp / 2) and
+// [spp / 2, spp): the frame's own rays, at its seed) and the first-hit features
+// of all spp, resolved on the device and filtered by rt_denoise with its
+// default options (include/rt.h): STEM.denoised.ppm and STEM.denoised.png hold
+// rt_quantize of the result.  An odd spp is an error (exit status 2).
 // --json: one more line, a JSON object of where this one-frame process's time
 // went (the device start-up -- the HIP runtime's first rt_device_count, then
 // rt_prepare's context / code object / queue / pageable staging -- on a thread
@@ -50,6 +56,8 @@
 #include <utility>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>   // (--denoise's device frame: hipMalloc, hipMemcpy)
+
 #include "../../include/rt.h"
 
 int main(int argc, char** argv) {
@@ -59,7 +67,7 @@ int main(int argc, char** argv) {
   long long ad_samples = 0;
   int ad_tiles = 0, ad_cap_tiles = 0, ad_steps = 0;
   unsigned long long seed = 1;
-  std::string scene = "reference", out, png, features;
+  std::string scene = "reference", out, png, features, denoise;
   bool realm = false, json = false, host_quantize = false, no_png = false, rejection = false;
   int pos = 0;
   const auto t_start = std::chrono::steady_clock::now();
@@ -76,7 +84,7 @@ int main(int argc, char** argv) {
   // (a missing option value ends the process before the start-up thread
   // exists: no exit while that thread may be inside the HIP runtime)
   static const char* const kValued[] = {"--scene", "--width", "--seed", "--gpus", "--grid", "--out", "--png", "--passes",
-                                        "--adaptive", "--step", "--min-spp", "--max-spp", "--features"};
+                                        "--adaptive", "--step", "--min-spp", "--max-spp", "--features", "--denoise"};
   for (int i = 1; i < argc; ++i) {
     const bool valued = std::any_of(std::begin(kValued), std::end(kValued),
                                     [&](const char* f) { return std::strcmp(argv[i], f) == 0; });
@@ -116,6 +124,7 @@ int main(int argc, char** argv) {
     else if (a == "--min-spp") ad_min = std::atoi(val());
     else if (a == "--max-spp") ad_max = std::atoi(val());
     else if (a == "--features") features = val();
+    else if (a == "--denoise") denoise = val();
     else if (a == "--realm") realm = true;
     else if (a == "--rejection-samplers") rejection = true;   // RT_FLAG_REJECTION_SAMPLERS
     else if (a == "--json") json = true;
@@ -166,6 +175,10 @@ int main(int argc, char** argv) {
   const double scene_ms = ms_since(t_start);
   prep.join();   // (the device start-up ran beside the argument parsing and the scene)
   const double prep_wait_ms = ms_since(t_start) - scene_ms;
+  if (!denoise.empty() && (spp <= 0 || spp % 2 != 0)) {
+    std::fprintf(stderr, "--denoise needs an even spp (two halves of spp / 2 samples), got %d\n", spp);
+    return 2;
+  }
   rt_params p{};
   p.width = width;
   p.height = height;
@@ -318,6 +331,57 @@ int main(int argc, char** argv) {
       if (!ok) std::fprintf(stderr, "%s\n", rt_last_error());
     }
     rt_feat_free(ft);
+    rt_scene_free(ds);
+    if (!ok) return 1;
+  }
+  if (!denoise.empty()) {
+    // the frame's rays as two halves and their features (raytracing.clj:141-155,
+    // :144-151, :33-43), resolved and filtered on device 0
+    const size_t npx = static_cast<size_t>(width) * height;
+    rt_dscene* ds = nullptr;
+    rt_accum* acc[2] = {nullptr, nullptr};
+    rt_feat* ft = nullptr;
+    rt_denoiser* dn = nullptr;
+    float* d_buf = nullptr;   // half0 | half1 | out (3 floats a pixel each) | feat (8)
+    std::vector<float> lin(npx * 3);
+    std::vector<uint8_t> b8(npx * 3);
+    rt_params hp = p;
+    hp.n_devices = 0;
+    hp.spp = spp / 2;
+    bool ok = rt_scene_upload(0, &s, &ds) == RT_OK && rt_feat_create(ds, &p, &ft) == RT_OK &&
+              rt_denoiser_create(0, width, height, &dn) == RT_OK;
+    for (int k = 0; ok && k < 2; ++k) {
+      hp.sample_begin = k * (spp / 2);
+      ok = rt_accum_create(ds, &hp, &acc[k]) == RT_OK && rt_launch_accum(ds, &cam, &hp, acc[k], nullptr, nullptr) == RT_OK;
+    }
+    ok = ok && rt_launch_feat(ds, &cam, &p, ft, nullptr, nullptr) == RT_OK;
+    if (!ok) std::fprintf(stderr, "--denoise failed: %s\n", rt_last_error());
+    if (ok && hipMalloc(reinterpret_cast<void**>(&d_buf), npx * (9 + RT_FEAT_CHANNELS) * sizeof(float)) != hipSuccess) {
+      std::fprintf(stderr, "--denoise failed: no device memory for the frame\n");
+      ok = false;
+    }
+    if (ok) {
+      float *d_h0 = d_buf, *d_h1 = d_buf + npx * 3, *d_out = d_buf + npx * 6, *d_feat = d_buf + npx * 9;
+      ok = rt_accum_resolve(acc[0], p.flags, d_h0, nullptr) == RT_OK &&
+           rt_accum_resolve(acc[1], p.flags, d_h1, nullptr) == RT_OK && rt_feat_resolve(ft, d_feat, nullptr) == RT_OK &&
+           rt_denoise(dn, nullptr, d_h0, d_h1, d_feat, d_out, nullptr) == RT_OK;
+      if (!ok) std::fprintf(stderr, "--denoise failed: %s\n", rt_last_error());
+      if (ok && hipMemcpy(lin.data(), d_out, lin.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+        std::fprintf(stderr, "--denoise failed: the copy back\n");
+        ok = false;
+      }
+    }
+    if (ok) {
+      ok = rt_quantize(lin.data(), b8.data(), b8.size()) == RT_OK &&
+           rt_write_ppm((denoise + ".denoised.ppm").c_str(), b8.data(), width, height) == RT_OK &&
+           rt_write_png((denoise + ".denoised.png").c_str(), b8.data(), width, height) == RT_OK;
+      if (!ok) std::fprintf(stderr, "%s\n", rt_last_error());
+    }
+    if (d_buf) (void)hipFree(d_buf);
+    rt_denoiser_free(dn);
+    rt_feat_free(ft);
+    rt_accum_free(acc[0]);
+    rt_accum_free(acc[1]);
     rt_scene_free(ds);
     if (!ok) return 1;
   }

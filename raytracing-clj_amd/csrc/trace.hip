@@ -9,10 +9,13 @@
 // (first_hit.h: feat_kernel, feat_resolve_kernel) and the rt_feat entries are
 // here too.  Which variant a launch runs and the LDS it needs
 // is variant_policy.h's (pure functions, checked on the CPU); the device
-// buffers the host side owns are dev_buf.h's DevBuf.
+// buffers the host side owns are dev_buf.h's DevBuf.  The denoiser's kernels
+// (denoise.h) and the rt_denoiser entries close the file.
 #include "trace_kernel.h"
 #define RT_FIRST_HIT_KERNEL
 #include "first_hit.h"
+#define RT_DENOISE_KERNEL
+#include "denoise.h"
 #include "variant_policy.h"
 #include "dev_buf.h"
 
@@ -338,6 +341,22 @@ __global__ __launch_bounds__(256) void adapt_resolve_kernel(const unsigned long 
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     if (head) put(0, h0[e0] + h1[e0]);
     if ((w3 - head) & 1) put(w3 - 1, h0[e0 + w3 - 1] + h1[e0 + w3 - 1]);
+  }
+}
+
+// rt_adapt_resolve_half: one half's sums as a frame, resolve_kernel's
+// conversion with half the count of the element's tile (each half holds half
+// the tile's samples).  A thread per element, grid-stride.
+__global__ __launch_bounds__(256) void adapt_half_kernel(const unsigned long long* __restrict__ h,
+                                                          const uint32_t* __restrict__ counts, int width,
+                                                          int tiles_x, size_t n, int realm, float* __restrict__ out) {
+  const size_t stride = static_cast<size_t>(gridDim.x) * 256;
+  for (size_t e = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; e < n; e += stride) {
+    const size_t px = e / 3, y = px / static_cast<size_t>(width), x = px - y * static_cast<size_t>(width);
+    const uint32_t c = counts[(y / kTile) * tiles_x + x / kTile] / 2u;
+    const float nf = static_cast<float>(c > 0u ? c : 1u);   // RN(float(count / 2))
+    const float tot = static_cast<float>(h[e]) * 0x1p-24f;
+    out[e] = realm ? tot * (1.0f / nf) : tot / nf;
   }
 }
 
@@ -1836,6 +1855,19 @@ extern "C" int rt_adapt_resolve_u8(const rt_adapt* ad, int flags, uint8_t* d_out
   return adapt_resolve(ad, flags, nullptr, d_out, hip_stream, "rt_adapt_resolve_u8");
 }
 
+extern "C" int rt_adapt_resolve_half(const rt_adapt* ad, int half, int flags, float* d_out, void* hip_stream) {
+  clear_error();
+  if (!ad || !d_out) return set_error(RT_E_ARG, "rt_adapt_resolve_half: NULL argument");
+  if (half != 0 && half != 1) return set_error(RT_E_ARG, "rt_adapt_resolve_half: half is neither 0 nor 1");
+  if (const int rc = check_resolve_flags("rt_adapt_resolve_half", flags)) return rc;
+  HIP_TRY(hipSetDevice(ad->device));
+  const size_t blocks = std::max<size_t>(1, std::min<size_t>((ad->n + 255) / 256, 4096));
+  HIP_TRY(enqueue(adapt_half_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
+                  static_cast<hipStream_t>(hip_stream), ad->h[half].p, ad->counts.p, ad->shape.width, ad->gx, ad->n,
+                  (flags & RT_FLAG_REALM) ? 1 : 0, d_out));
+  return RT_OK;
+}
+
 extern "C" int rt_adapt_counts(const rt_adapt* ad, uint32_t* host_counts, void* hip_stream) {
   clear_error();
   if (!ad || !host_counts) return set_error(RT_E_ARG, "rt_adapt_counts: NULL argument");
@@ -2023,6 +2055,144 @@ extern "C" int rt_feat_occupancy(const rt_dscene* ds, int* out4) {
   if (const int rc = occupancy_report(feat_fn(src), kFeatThreads, policy::feat_lds(si, src), out4)) return rc;
   out4[3] = src;
   return RT_OK;
+}
+
+// ---- the denoiser (rt.h, denoise.h) -----------------------------------------
+// Its scratch on the device: the two texel arrays the levels ping-pong between
+// and the guides the prep packs, for one image size.  mu orders the calls'
+// enqueues (the scratch itself is ordered by the caller's stream).
+struct rt_denoiser {
+  int device = 0, width = 0, rows = 0;
+  size_t n_px = 0;
+  std::mutex mu;
+  DevBuf<DnTexel> tex[2];
+  DevBuf<DnGuide> guide;
+  DevBuf<float> omc;
+};
+
+extern "C" int rt_denoiser_create(int device, int width, int rows, rt_denoiser** out) {
+  clear_error();
+  if (!out) return set_error(RT_E_ARG, "rt_denoiser_create: NULL argument");
+  *out = nullptr;
+  // (the level kernel's grid has a block row per kDnBy frame rows)
+  if (width <= 0 || rows <= 0 || static_cast<int64_t>(width) * rows > 0x7fffffffll ||
+      (rows + kDnBy - 1) / kDnBy > 65535)
+    return set_error(RT_E_ARG, "rt_denoiser_create: bad width/rows");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return set_error(RT_E_NODEV, "rt_denoiser_create: device " + std::to_string(device) + " not available");
+  HIP_TRY(hipSetDevice(device));
+  rt_denoiser* dn = new rt_denoiser;
+  dn->device = device;
+  dn->width = width;
+  dn->rows = rows;
+  dn->n_px = static_cast<size_t>(width) * rows;
+  hipError_t e = dn->tex[0].alloc(dn->n_px);
+  if (e == hipSuccess) e = dn->tex[1].alloc(dn->n_px);
+  if (e == hipSuccess) e = dn->guide.alloc(dn->n_px);
+  if (e == hipSuccess) e = dn->omc.alloc(dn->n_px);
+  if (e != hipSuccess) {
+    delete dn;
+    return hip_fail(e, "rt_denoiser_create");
+  }
+  *out = dn;
+  return RT_OK;
+}
+
+extern "C" int rt_denoiser_free(rt_denoiser* dn) {
+  if (!dn) return RT_OK;
+  (void)hipSetDevice(dn->device);
+  delete dn;
+  return RT_OK;
+}
+
+static bool dn_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+
+// rt_denoise / rt_denoise_profile: the checks, then the prep and the levels
+// enqueued on the stream.  ev (rt_denoise_profile): 2 + levels events, one
+// recorded before the prep and one behind every kernel.
+static int denoise_enqueue(const char* who, rt_denoiser* dn, const rt_denoise_opts* o, const float* d_half0,
+                           const float* d_half1, const float* d_feat, float* d_out, void* hip_stream,
+                           hipEvent_t* ev, int* levels_out) {
+  const std::string me(who);
+  if (!dn || !d_half0 || !d_half1 || !d_feat || !d_out) return set_error(RT_E_ARG, me + ": NULL argument");
+  const rt_denoise_opts opt = o ? *o : dn_default_opts();
+  if (const char* why = dn_opts_error(opt)) return set_error(RT_E_ARG, me + ": " + why);
+  const size_t cb = dn->n_px * 3 * sizeof(float);
+  if (dn_overlap(d_out, cb, d_half0, cb) || dn_overlap(d_out, cb, d_half1, cb) ||
+      dn_overlap(d_out, cb, d_feat, dn->n_px * RT_FEAT_CHANNELS * sizeof(float)))
+    return set_error(RT_E_ARG, me + ": d_out overlaps an input");
+  std::lock_guard<std::mutex> lk(dn->mu);
+  HIP_TRY(hipSetDevice(dn->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (stream) {
+    hipDevice_t sdev = 0;
+    if (hipStreamGetDevice(stream, &sdev) == hipSuccess && static_cast<int>(sdev) != dn->device)
+      return set_error(RT_E_ARG, me + ": the stream is on device " + std::to_string(static_cast<int>(sdev)) +
+                                     ", the denoiser on device " + std::to_string(dn->device));
+  }
+  if (levels_out) *levels_out = opt.levels;
+  if (ev) HIP_TRY(hipEventRecord(ev[0], stream));
+  const size_t pblocks = std::max<size_t>(1, std::min<size_t>((dn->n_px + 255) / 256, 4096));
+  HIP_TRY(enqueue(denoise_prep_kernel, dim3(static_cast<unsigned>(pblocks)), dim3(256), 0, stream, d_half0, d_half1,
+                  d_feat, dn->n_px, dn->tex[0].p, dn->guide.p, dn->omc.p));
+  if (ev) HIP_TRY(hipEventRecord(ev[1], stream));
+  const dim3 grid(static_cast<unsigned>((dn->width + kDnBx - 1) / kDnBx),
+                  static_cast<unsigned>((dn->rows + kDnBy - 1) / kDnBy)),
+      block(kDnBx, kDnBy);
+  for (int lv = 0; lv < opt.levels; ++lv) {
+    const DnTexel* src = dn->tex[lv & 1].p;
+    DnTexel* dst = dn->tex[(lv & 1) ^ 1].p;
+    const bool last = lv + 1 == opt.levels;
+    if (lv < 2) {   // step 1 and 2: the LDS tile
+      const auto fn = lv == 0 ? (last ? denoise_level_lds_kernel<1, true> : denoise_level_lds_kernel<1, false>)
+                              : (last ? denoise_level_lds_kernel<2, true> : denoise_level_lds_kernel<2, false>);
+      HIP_TRY(enqueue(fn, grid, block, 0, stream, src, dn->guide.p, dn->omc.p, dn->width, dn->rows, opt.normal_pow2,
+                      opt.sigma_c, opt.sigma_z, dst, d_feat, d_out));
+      if (ev) HIP_TRY(hipEventRecord(ev[2 + lv], stream));
+      continue;
+    }
+    HIP_TRY(enqueue(last ? denoise_level_kernel<true> : denoise_level_kernel<false>, grid, block, 0, stream, src,
+                    dn->guide.p, dn->omc.p, dn->width, dn->rows, 1 << lv, opt.normal_pow2, opt.sigma_c, opt.sigma_z,
+                    dst, d_feat, d_out));
+    if (ev) HIP_TRY(hipEventRecord(ev[2 + lv], stream));
+  }
+  return RT_OK;
+}
+
+extern "C" int rt_denoise(rt_denoiser* dn, const rt_denoise_opts* o, const float* d_half0, const float* d_half1,
+                          const float* d_feat, float* d_out, void* hip_stream) {
+  clear_error();
+  return denoise_enqueue("rt_denoise", dn, o, d_half0, d_half1, d_feat, d_out, hip_stream, nullptr, nullptr);
+}
+
+// rt_denoise with an event behind every kernel (diagnostic, tools/denoise_time.py):
+// waits, then out_ms = {prep, level 0 .., the whole}.
+extern "C" int rt_denoise_profile(rt_denoiser* dn, const rt_denoise_opts* o, const float* d_half0,
+                                  const float* d_half1, const float* d_feat, float* d_out, void* hip_stream,
+                                  float* out_ms) {
+  clear_error();
+  if (!out_ms) return set_error(RT_E_ARG, "rt_denoise_profile: NULL argument");
+  if (dn) HIP_TRY(hipSetDevice(dn->device));
+  hipEvent_t ev[2 + kDnMaxLevels] = {};
+  hipError_t e = hipSuccess;
+  for (int k = 0; dn && k < 2 + kDnMaxLevels && e == hipSuccess; ++k) e = hipEventCreate(&ev[k]);
+  int levels = 0;
+  int rc = e == hipSuccess ? denoise_enqueue("rt_denoise_profile", dn, o, d_half0, d_half1, d_feat, d_out, hip_stream,
+                                             ev, &levels)
+                           : hip_fail(e, "rt_denoise_profile");
+  if (rc == RT_OK) {
+    e = hipEventSynchronize(ev[1 + levels]);
+    for (int k = 0; k <= levels && e == hipSuccess; ++k) e = hipEventElapsedTime(&out_ms[k], ev[k], ev[k + 1]);
+    if (e == hipSuccess) e = hipEventElapsedTime(&out_ms[levels + 1], ev[0], ev[1 + levels]);
+    if (e != hipSuccess) rc = hip_fail(e, "rt_denoise_profile");
+  }
+  for (hipEvent_t v : ev)
+    if (v) (void)hipEventDestroy(v);
+  return rc;
 }
 
 // A device's start-up ahead of the first render (rt.h): the context, the

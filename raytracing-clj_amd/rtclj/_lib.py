@@ -74,6 +74,14 @@ class rt_adapt_opts(C.Structure):
     _fields_ = [("step_spp", C.c_int), ("min_spp", C.c_int), ("max_spp", C.c_int), ("tol_q16", C.c_uint32)]
 
 
+class rt_denoise_opts(C.Structure):
+    _fields_ = [("levels", C.c_int), ("normal_pow2", C.c_int), ("sigma_c", C.c_float), ("sigma_z", C.c_float)]
+
+
+# rt_denoise's defaults (include/rt.h)
+DENOISE_DEFAULTS = dict(levels=5, normal_pow2=5, sigma_c=4.0, sigma_z=0.05)
+
+
 # symbol -> (restype, argtypes); every function include/rt.h declares
 SIGNATURES = {
     "rt_camera_setup": (C.c_int, [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -141,6 +149,15 @@ SIGNATURES = {
     "rt_feat_resolve_host": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_size_t,
                                        C.c_int64, C.POINTER(C.c_float)]),
     "rt_feat_occupancy": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rt_adapt_resolve_half": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_denoiser_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "rt_denoiser_free": (C.c_int, [C.c_void_p]),
+    "rt_denoise": (C.c_int, [C.c_void_p, C.POINTER(rt_denoise_opts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_void_p]),
+    "rt_denoise_profile": (C.c_int, [C.c_void_p, C.POINTER(rt_denoise_opts), C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
+    "rt_denoise_host": (C.c_int, [C.POINTER(rt_denoise_opts), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                  C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "rt_quantize_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rt_set_variant": (C.c_int, [C.c_int]),
     "rt_resolve_variant": (C.c_int, [C.c_void_p]),
@@ -165,7 +182,9 @@ ADDITIVE = {"rt_prepare", "rt_render_u8", "rt_quantize_device", "rt_render_submi
             "rt_adapt_active", "rt_adapt_samples", "rt_adapt_resolve", "rt_adapt_resolve_u8", "rt_adapt_counts",
             "rt_adapt_read", "rt_adapt_eval_host", "rt_adapt_resolve_host", "rt_feat_create", "rt_feat_free",
             "rt_feat_clear", "rt_feat_samples", "rt_launch_feat", "rt_feat_resolve", "rt_feat_read",
-            "rt_feat_add", "rt_feat_resolve_host", "rt_feat_occupancy"}
+            "rt_feat_add", "rt_feat_resolve_host", "rt_feat_occupancy", "rt_adapt_resolve_half",
+            "rt_denoiser_create", "rt_denoiser_free", "rt_denoise", "rt_denoise_profile",
+            "rt_denoise_host"}
 
 RT_FEAT_CHANNELS = 8   # rt_feat_resolve's floats per pixel: albedo rgb, normal xyz, depth, coverage
 

@@ -24,8 +24,9 @@ from fractions import Fraction
 import numpy as np
 
 from . import hittable, material
-from ._lib import (RT_DIELECTRIC, RT_FEAT_CHANNELS, RT_LAMBERTIAN, RT_METAL, RT_NONE, RTError, check, dptr, fptr,
-                   i64ptr, iptr, lib, rt_adapt_opts, rt_camera, rt_params, rt_scene, rt_stats, u8ptr, u32ptr, u64ptr)
+from ._lib import (DENOISE_DEFAULTS, RT_DIELECTRIC, RT_FEAT_CHANNELS, RT_LAMBERTIAN, RT_METAL, RT_NONE, RTError, check,
+                   dptr, fptr, i64ptr, iptr, lib, rt_adapt_opts, rt_camera, rt_denoise_opts, rt_params, rt_scene,
+                   rt_stats, u8ptr, u32ptr, u64ptr)
 
 # ---- scene (raytracing.clj:63-78) --------------------------------------------
 hittables = [
@@ -348,6 +349,13 @@ class Adaptive:
         fn = self._dll.rt_adapt_resolve_u8 if u8 else self._dll.rt_adapt_resolve
         self._check(fn(self._ad, self._p.flags, C.c_void_p(d_out), self._stream))
 
+    def resolve_half_into(self, d_out: int, half: int) -> None:
+        """Enqueue one half (0 or 1) as a frame of its own into a device
+        buffer the caller owns (rt_adapt_resolve_half): the two estimates
+        Denoiser.run takes, with no trip through the host."""
+        self._check(self._dll.rt_adapt_resolve_half(self._ad, int(half), self._p.flags, C.c_void_p(d_out),
+                                                    self._stream))
+
     def clear(self) -> None:
         """Back to step 0 with every tile active (rt_adapt_clear)."""
         self._check(self._dll.rt_adapt_clear(self._ad, self._stream))
@@ -488,6 +496,125 @@ class Features:
 
     def __del__(self):
         self.close()
+
+
+def _denoise_opts(opts: dict) -> rt_denoise_opts:
+    unknown = set(opts) - set(DENOISE_DEFAULTS)
+    if unknown:
+        raise TypeError(f"denoise: unknown option(s) {sorted(unknown)}")
+    o = {**DENOISE_DEFAULTS, **opts}
+    return rt_denoise_opts(levels=int(o["levels"]), normal_pow2=int(o["normal_pow2"]), sigma_c=float(o["sigma_c"]),
+                           sigma_z=float(o["sigma_z"]))
+
+
+def denoise_host(half0, half1, feat, library=None, **opts) -> np.ndarray:
+    """rt_denoise_host (include/rt.h): the feature-guided a-trous filter on the
+    host, in plain C++ -- the bits Denoiser.run gives on the device.  half0,
+    half1: float32 (rows, width, 3), two estimates of the frame from disjoint,
+    equally large sample sets; feat: float32 (rows, width, 8) as Features.frame()
+    gives it.  Options: levels, normal_pow2, sigma_c, sigma_z.  Returns float32
+    (rows, width, 3)."""
+    dll = library if library is not None else lib
+    half0 = np.ascontiguousarray(half0, np.float32)
+    half1 = np.ascontiguousarray(half1, np.float32)
+    feat = np.ascontiguousarray(feat, np.float32)
+    if half0.ndim != 3 or half0.shape[2] != 3 or half1.shape != half0.shape or \
+            feat.shape != half0.shape[:2] + (RT_FEAT_CHANNELS,):
+        raise ValueError("denoise_host: half0, half1 must be (rows, width, 3) and feat (rows, width, 8)")
+    rows, width = half0.shape[:2]
+    out = np.empty(half0.shape, np.float32)
+    o = _denoise_opts(opts)
+    code = dll.rt_denoise_host(C.byref(o), fptr(half0), fptr(half1), fptr(feat), width, rows, fptr(out))
+    if code < 0:
+        raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+    return out
+
+
+class Denoiser:
+    """The feature-guided a-trous filter on device `device` for images of
+    rows x width (rt_denoiser, include/rt.h): it owns the filter's scratch.
+
+        with Denoiser(400, 225) as dn:
+            dn.run(d_half0, d_half1, d_feat, d_out)      # device addresses
+
+    run() is asynchronous, on `stream` (a HIP stream handle, int; default the
+    NULL stream); the inputs are two half-frames (rows, width, 3) and the
+    resolved features (rows, width, 8), all float32 on the device."""
+
+    def __init__(self, width: int, rows: int, device: int = 0, library=None):
+        self._dll = library if library is not None else lib
+        self.width, self.rows = int(width), int(rows)
+        self._dn = C.c_void_p()
+        self._check(self._dll.rt_denoiser_create(int(device), self.width, self.rows, C.byref(self._dn)))
+        self.shape = (self.rows, self.width, 3)
+
+    def _check(self, code):
+        if code < 0:
+            raise RTError(code, self._dll.rt_last_error().decode(errors="replace"))
+        return code
+
+    def run(self, d_half0: int, d_half1: int, d_feat: int, d_out: int, stream=None, **opts) -> None:
+        """Enqueue the filter (rt_denoise); options as denoise_host."""
+        o = _denoise_opts(opts)
+        self._check(self._dll.rt_denoise(self._dn, C.byref(o), C.c_void_p(d_half0), C.c_void_p(d_half1),
+                                         C.c_void_p(d_feat), C.c_void_p(d_out),
+                                         C.c_void_p(stream) if stream else None))
+
+    def close(self) -> None:
+        if getattr(self, "_dn", None):
+            self._dll.rt_denoiser_free(self._dn)
+            self._dn = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def render_denoised(scene, cam: rt_camera, width: int, height: int, spp: int = 8, max_depth: int = 50, seed: int = 1,
+                    flags: int = 0, library=None, **opts):
+    """A low-sample frame and its denoised version, on device 0: two
+    accumulators of spp / 2 samples each (sample indices [0, spp / 2) and
+    [spp / 2, spp): together the rays render() traces at spp), the first-hit
+    features of all spp samples, everything resolved on the device, then
+    Denoiser.run.  `spp` must be even.  Returns (denoised, mean, feat):
+    float32 (height, width, 3), the plain mean of the two halves likewise, and
+    the feature frame (height, width, 8).  The device buffers are torch's
+    (import torch before rtclj, as the GPU tests and bench.py do: both bring
+    a HIP runtime and the first one loaded serves the process)."""
+    if spp <= 0 or spp % 2:
+        raise ValueError("render_denoised: spp must be even and positive")
+    import torch
+    if not torch.cuda.is_available():
+        raise RTError(-5, "render_denoised: torch sees no GPU (import torch before rtclj)")
+    half = spp // 2
+    sc = scene if isinstance(scene, Scene) else Scene.from_bodies(scene)
+    dev = torch.device("cuda", 0)
+    n_px = width * height
+    d_h = [torch.empty(n_px * 3, dtype=torch.float32, device=dev) for _ in range(2)]
+    d_feat = torch.empty(n_px * RT_FEAT_CHANNELS, dtype=torch.float32, device=dev)
+    d_out = torch.empty(n_px * 3, dtype=torch.float32, device=dev)
+    torch.cuda.synchronize(dev)   # (the passes below run on the NULL stream)
+    with Progressive(sc, cam, width, height, max_depth, seed, flags=flags, library=library) as a0, \
+            Progressive(sc, cam, width, height, max_depth, seed, flags=flags, sample_begin=half, library=library) as a1, \
+            Features(sc, cam, width, height, seed=seed, flags=flags, library=library) as ft, \
+            Denoiser(width, height, library=library) as dn:
+        a0.add(half)
+        a1.add(half)
+        ft.add(spp)
+        a0.resolve_into(d_h[0].data_ptr())
+        a1.resolve_into(d_h[1].data_ptr())
+        ft.resolve_into(d_feat.data_ptr())
+        dn.run(d_h[0].data_ptr(), d_h[1].data_ptr(), d_feat.data_ptr(), d_out.data_ptr(), **opts)
+        torch.cuda.synchronize(dev)
+        h0, h1 = (d.cpu().numpy().reshape(height, width, 3) for d in d_h)
+        feat = d_feat.cpu().numpy().reshape(height, width, RT_FEAT_CHANNELS)
+        out = d_out.cpu().numpy().reshape(height, width, 3)
+    return out, np.float32(0.5) * (h0 + h1), feat
 
 
 def pass_sizes(spp: int, passes: int):
@@ -665,4 +792,4 @@ if __name__ == "__main__":  # python -m rtclj.raytracing [spp] [depth]
 
 
 __all__ = ["hittables", "REFERENCE_CAMERA", "image_height", "flatten", "flatten64", "Scene", "camera", "render", "Progressive", "Adaptive", "pass_sizes",
-           "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]
+           "Features", "denoise_host", "Denoiser", "render_denoised", "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]
