@@ -49,6 +49,10 @@ def _lib():
         d.oracle_render_cols.argtypes = [C.c_int, C.c_int, dp, ip, dp, dp, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64,
                                          C.c_int, fp, dp, u64p]
+        d.oracle_features.restype = C.c_int
+        d.oracle_features.argtypes = [C.c_int, C.c_int, dp, ip, dp, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_int64),
+                                      C.POINTER(C.c_uint32), fp, dp, C.POINTER(C.c_int32), dp, fp]
         d.oracle_sphere_hit.restype = C.c_int
         d.oracle_sphere_hit.argtypes = [dp, dp, dp, C.c_double, C.c_double, dp]
         d.oracle_reflect.argtypes = [dp, dp, dp]
@@ -107,6 +111,60 @@ def render(mode, sphere, kind, mat, cam, defocus, width, height, spp, max_depth,
     if rc != 0:
         raise ValueError(f"oracle_render rejected its arguments (rc={rc})")
     return out, out64, int(cnt[0]), int(cnt[1])
+
+
+def features(mode, sphere, kind, mat, cam, defocus, width, height, spp, seed=1, rows=None, sample_begin=0,
+             nthreads=0, row_step=1, want_body=False, want_t=False, want_rays=False):
+    """The first-hit feature pass (include/rt.h, rt_launch_feat) of rows r0,
+    r0+row_step, ... < r1 (default all), samples sample_begin ... + spp - 1 -> dict.
+    MODE_MIRROR32 (| DIRECT bits), what rt_feat_read returns bit for bit:
+      sums int64 (rows, W, 6), hits uint32 (rows, W), depth float32 (rows, W).
+    MODE_REF64D (MODE_REF64: the rejection disk), the same draws in double:
+      albedo, normal float64 (rows, W, 3) means over the samples (the sky on a
+      miss, normal 0), depth float64 (min t |d|, +inf: none), hits uint32.
+    want_body: body int32 (rows, W, spp), -1 a miss; want_t: t float64, the
+    same shape (+inf a miss); want_rays (mirror): rays float32 (..., spp, 6), (o, d)."""
+    r0, r1 = (0, height) if rows is None else rows
+    nrows = (r1 - r0 + row_step - 1) // row_step
+    sph, sp = _d(np.asarray(sphere, np.float64).reshape(-1, 4))
+    mt, mp = _d(np.asarray(mat, np.float64).reshape(-1, 4))
+    kd = np.ascontiguousarray(kind, np.int32).reshape(-1)
+    cm, cp = _d(np.asarray(cam, np.float64).reshape(18))
+    fp64 = (mode & 0xf) in (MODE_REF64, MODE_REF64D)
+    dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+    sums = hits = depth = mean = body = t = rays = None
+    if fp64:
+        mean = np.full((nrows, width, 8), np.nan, np.float64)
+    else:
+        sums = np.full((nrows, width, 6), -1, np.int64)
+        hits = np.full((nrows, width), 0xffffffff, np.uint32)
+        depth = np.full((nrows, width), np.nan, np.float32)
+    if want_body:
+        body = np.full((nrows, width, max(spp, 0)), -2, np.int32)
+    if want_t:
+        t = np.full((nrows, width, max(spp, 0)), np.nan, np.float64)
+    if want_rays:
+        rays = np.full((nrows, width, max(spp, 0), 6), np.nan, np.float32)
+
+    def ptr(a, ty):
+        return None if a is None else a.ctypes.data_as(ty)
+    rc = _lib().oracle_features(mode, len(kd), sp, kd.ctypes.data_as(C.POINTER(C.c_int)), mp, cp, int(defocus),
+                                width, height, r0, r1, row_step, spp, sample_begin, seed, nthreads,
+                                ptr(sums, C.POINTER(C.c_int64)), ptr(hits, C.POINTER(C.c_uint32)), ptr(depth, fp),
+                                ptr(mean, dp), ptr(body, C.POINTER(C.c_int32)), ptr(t, dp), ptr(rays, fp))
+    if rc != 0:
+        raise ValueError(f"oracle_features rejected its arguments (rc={rc})")
+    if fp64:
+        out = dict(albedo=mean[..., 0:3], normal=mean[..., 3:6], depth=mean[..., 6], hits=mean[..., 7].astype(np.uint32))
+    else:
+        out = dict(sums=sums, hits=hits, depth=depth)
+    if want_body:
+        out["body"] = body
+    if want_t:
+        out["t"] = t
+    if want_rays:
+        out["rays"] = rays
+    return out
 
 
 def sphere_hit(sphere4, o, d, tmin, tmax):

@@ -48,6 +48,12 @@
 //     (MODE_MIRROR32 | 0x30, MODE_REALM32 | 0x30): the paths coincide except
 //     where an fp32 decision flips.  They take no 0x10 / 0x20 bits.
 //
+// oracle_features — the first-hit feature pass (include/rt.h, rt_launch_feat)
+//   on the same camera rays: MODE_MIRROR32 (| 0x10, 0x20) restates the feature
+//   kernel's fp32 ops, and its integer sums, hit counts and depth bits are what
+//   rt_feat_read must return; MODE_REF64D (MODE_REF64) runs hit_anything64 on
+//   the same draws in double.
+//
 // The reference's RNG is clojure.core/rand (unseeded java.util.Random,
 // vec3a.clj:71-72), so no bitwise reference image exists.  Both modes draw
 // from the build's keyed stream instead: xorshift32 seeded per
@@ -431,16 +437,14 @@ void disk_direct32(Rng& s, float& x, float& y) {
 }
 enum { DIRECT_SPHERE = 1, DIRECT_DISK = 2 };   // the kernel's RT_SAMPLER_* bits (mode >> 4)
 
-// one sample of the stackless kernel loop; returns colour, adds segments
-void sample32(const Scene32& sc, const float* cam, bool defocus, bool realm, int direct, int px, int gy,
-              uint32_t st, int max_depth, float* col, uint64_t* segs) {
-  Rng rng{st};
+// the kernel's camera ray of one sample (trace_kernel.h block `camera`): the
+// jittered pixel, the defocus draw, d = s - o.  rng is left where the path goes on.
+void camera_ray32(const float* cam, bool defocus, int direct, int px, int gy, Rng& rng, float* o, float* d) {
   const float fx = static_cast<float>(px) + (rng.uf() - 0.5f);
   const float fy = static_cast<float>(gy) + (rng.uf() - 0.5f);
   const float sx = std::fmaf(cam[9], fy, std::fmaf(cam[6], fx, cam[3]));
   const float sy = std::fmaf(cam[10], fy, std::fmaf(cam[7], fx, cam[4]));
   const float sz = std::fmaf(cam[11], fy, std::fmaf(cam[8], fx, cam[5]));
-  float ox, oy, oz;
   if (defocus) {
     float qx, qy;
     if (direct & DIRECT_DISK) {
@@ -451,15 +455,27 @@ void sample32(const Scene32& sc, const float* cam, bool defocus, bool realm, int
         qy = 2.0f * rng.uf() - 1.0f;
       } while (!(std::fmaf(qy, qy, qx * qx) < 1.0f));
     }
-    ox = std::fmaf(cam[15], qy, std::fmaf(cam[12], qx, cam[0]));
-    oy = std::fmaf(cam[16], qy, std::fmaf(cam[13], qx, cam[1]));
-    oz = std::fmaf(cam[17], qy, std::fmaf(cam[14], qx, cam[2]));
+    o[0] = std::fmaf(cam[15], qy, std::fmaf(cam[12], qx, cam[0]));
+    o[1] = std::fmaf(cam[16], qy, std::fmaf(cam[13], qx, cam[1]));
+    o[2] = std::fmaf(cam[17], qy, std::fmaf(cam[14], qx, cam[2]));
   } else {
-    ox = cam[0];
-    oy = cam[1];
-    oz = cam[2];
+    o[0] = cam[0];
+    o[1] = cam[1];
+    o[2] = cam[2];
   }
-  float dx = sx - ox, dy = sy - oy, dz = sz - oz;
+  d[0] = sx - o[0];
+  d[1] = sy - o[1];
+  d[2] = sz - o[2];
+}
+
+// one sample of the stackless kernel loop; returns colour, adds segments
+void sample32(const Scene32& sc, const float* cam, bool defocus, bool realm, int direct, int px, int gy,
+              uint32_t st, int max_depth, float* col, uint64_t* segs) {
+  Rng rng{st};
+  float o0[3], d0[3];
+  camera_ray32(cam, defocus, direct, px, gy, rng, o0, d0);
+  float ox = o0[0], oy = o0[1], oz = o0[2];
+  float dx = d0[0], dy = d0[1], dz = d0[2];
   float tr = 1.0f, tg = 1.0f, tb = 1.0f;
   int last = -1;
   col[0] = col[1] = col[2] = 0.0f;
@@ -676,6 +692,233 @@ void render_row(const Job& J, int ro, int x0, int x1, uint64_t* segs) {
   }
 }
 
+// ------------------------------------------------ first-hit features -------
+// The feature pass (include/rt.h "first-hit features"; the kernel is
+// raytracing-clj_amd/csrc/first_hit.h's feat_kernel) for one camera sample,
+// from its definitions: what the sample adds to the pixel's integer sums.
+
+// n * 2^24 toward zero as int32 (the kernel's v_cvt_i32_f32: NaN gives 0, out
+// of range saturates)
+inline int32_t fix24s(float c) {
+  const float v = c * 0x1p24f;
+  if (v != v) return 0;
+  if (v >= 0x1p31f) return INT32_MAX;
+  if (v <= -0x1p31f) return INT32_MIN;
+  return static_cast<int32_t>(v);
+}
+
+struct FeatSample32 {
+  int body;          // -1: the sky
+  float t;           // the hit's distance (|d| units of the unit direction), +inf: none
+  uint32_t alb[3];   // fix24 of the albedo or of the sky
+  int32_t nrm[3];    // fix24s of the unit normal, 0 on a miss
+};
+
+FeatSample32 feat_sample32(const Scene32& sc, const float* o, const float* d) {
+  FeatSample32 f{};
+  // the ray as the search sees it (first_hit.h fh_ray): |d| and 1/|d|
+  // correctly rounded, u = d * (1/|d|), t-min = 1e-3 |d|
+  const float len = std::sqrt(std::fmaf(d[2], d[2], std::fmaf(d[1], d[1], d[0] * d[0])));
+  const float il = 1.0f / len;
+  const float ux = d[0] * il, uy = d[1] * il, uz = d[2] * il;
+  const float tmin = 1e-3f * len;
+  // hit-anything: the linear scan in array order, no self-hit guard; accepted
+  // iff t > t-min and (t, index) is strictly below the best; +inf never hits
+  float best_t = INFINITY;
+  int best = -1;
+  for (int s = 0; s < sc.n; ++s) {
+    const float* g = &sc.geo[4 * s];
+    const float ocx = g[0] - o[0], ocy = g[1] - o[1], ocz = g[2] - o[2];
+    const float h = std::fmaf(uz, ocz, std::fmaf(uy, ocy, ux * ocx));
+    const float c = std::fmaf(ocx, ocx, std::fmaf(ocz, ocz, std::fmaf(ocy, ocy, g[3])));
+    const float disc = std::fmaf(h, h, -c);
+    if (!(std::fmin(disc, std::fmax(h, -c)) >= 0.0f)) continue;   // no root above t-min
+    const float sq = std::sqrt(disc);
+    const float tn = h - sq;
+    const float t = tn > tmin ? tn : h + sq;
+    if (t > tmin && (t < best_t || (t == best_t && s < best))) {
+      best_t = t;
+      best = s;
+    }
+  }
+  f.body = best;
+  f.t = best_t;
+  if (best < 0) {  // the sky (raytracing.clj:55-58), the path's ops
+    const float sa = 0.5f * (uy + 1.0f);
+    const float om = 1.0f - sa;
+    f.alb[0] = fix24(std::fmaf(sa, 0.5f, om));
+    f.alb[1] = fix24(std::fmaf(sa, 0.7f, om));
+    f.alb[2] = fix24(std::fmaf(sa, 1.0f, om));
+    return f;
+  }
+  // the hit record: P = o + u t, n = (P - C) * RN(1/r), turned against d
+  const float* sp = &sc.sph[4 * best];
+  const float hx = std::fmaf(ux, best_t, o[0]);
+  const float hy = std::fmaf(uy, best_t, o[1]);
+  const float hz = std::fmaf(uz, best_t, o[2]);
+  const float ir = 1.0f / sp[3];
+  float nx = (hx - sp[0]) * ir, ny = (hy - sp[1]) * ir, nz = (hz - sp[2]) * ir;
+  if (!(std::fmaf(d[2], nz, std::fmaf(d[1], ny, d[0] * nx)) < 0.0f)) {
+    nx = -nx;
+    ny = -ny;
+    nz = -nz;
+  }
+  // ... scaled to unit length by one correctly rounded 1 / |n|
+  const float nil = 1.0f / std::sqrt(std::fmaf(nz, nz, std::fmaf(ny, ny, nx * nx)));
+  f.nrm[0] = fix24s(nx * nil);
+  f.nrm[1] = fix24s(ny * nil);
+  f.nrm[2] = fix24s(nz * nil);
+  // ::attenuation by kind (material.clj:13-46)
+  const int kind = sc.kind[best];
+  const float* m = &sc.mat[4 * best];
+  if (kind == LAMB || kind == METAL) {
+    for (int c = 0; c < 3; ++c) f.alb[c] = fix24(m[c]);
+  } else if (kind == DIEL) {
+    for (int c = 0; c < 3; ++c) f.alb[c] = 1u << 24;
+  }
+  return f;
+}
+
+inline uint32_t float_bits(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  return u;
+}
+
+struct FeatJob {
+  const Job* J;
+  bool fp64;
+  int rows;
+  // mirror outputs
+  int64_t* sums;     // rows x w x 6
+  uint32_t* hits;    // rows x w
+  float* depth;      // rows x w
+  // fp64 outputs
+  double* mean64;    // rows x w x 8: albedo rgb, unit normal xyz, min distance (+inf), hits
+  // either mode, nullable
+  int32_t* body;     // rows x w x spp
+  double* tsamp;     // rows x w x spp: the sample's distance (+inf: miss)
+  float* rays;       // rows x w x spp x 6 (o, d): mirror only
+};
+
+void feat_row(const FeatJob& F, int ro, int x0, int x1) {
+  const Job& J = *F.J;
+  const int gy = J.row_begin + ro * J.row_step;
+  t_direct64 = J.mode == MODE_REF64D;
+  for (int px = x0; px < x1; ++px) {
+    const uint32_t pixel = static_cast<uint32_t>(gy) * static_cast<uint32_t>(J.width) + static_cast<uint32_t>(px);
+    const size_t e = static_cast<size_t>(ro) * J.width + px;
+    if (!F.fp64) {
+      uint64_t alb[3] = {0, 0, 0};
+      int64_t nrm[3] = {0, 0, 0};
+      uint32_t nh = 0, dmin = 0x7f800000u;
+      const uint32_t pk = mix32(J.key ^ mix32(pixel));
+      for (int k = 0; k < J.spp; ++k) {
+        uint32_t st = mix32(pk + static_cast<uint32_t>(J.sample_begin + k) * 0x9e3779b9u);
+        if (st == 0) st = 0x6d2b79f5u;
+        Rng rng{st};
+        float o[3], d[3];
+        camera_ray32(J.cam32, J.defocus, J.direct, px, gy, rng, o, d);
+        const FeatSample32 f = feat_sample32(J.s32, o, d);
+        for (int c = 0; c < 3; ++c) {
+          alb[c] += f.alb[c];
+          nrm[c] += f.nrm[c];
+        }
+        if (f.body >= 0) {
+          ++nh;
+          dmin = std::min(dmin, float_bits(f.t));   // t > 0: the bits order as the floats
+        }
+        const size_t se = e * J.spp + k;
+        if (F.body) F.body[se] = f.body;
+        if (F.tsamp) F.tsamp[se] = static_cast<double>(f.t);
+        if (F.rays) {
+          for (int c = 0; c < 3; ++c) {
+            F.rays[se * 6 + c] = o[c];
+            F.rays[se * 6 + 3 + c] = d[c];
+          }
+        }
+      }
+      for (int c = 0; c < 3; ++c) {
+        F.sums[e * 6 + c] = static_cast<int64_t>(alb[c]);
+        F.sums[e * 6 + 3 + c] = nrm[c];
+      }
+      F.hits[e] = nh;
+      std::memcpy(&F.depth[e], &dmin, 4);
+    } else {
+      // compute-pixel's ray (raytracing.clj:141-151) and one hit-anything, in double
+      const double* c = J.cam64;
+      const V center{c[0], c[1], c[2]}, p00{c[3], c[4], c[5]}, du{c[6], c[7], c[8]}, dv{c[9], c[10], c[11]};
+      const V disk_u{c[12], c[13], c[14]}, disk_v{c[15], c[16], c[17]};
+      V alb{0, 0, 0}, nrm{0, 0, 0};
+      double dmin = INFINITY;
+      uint32_t nh = 0;
+      uint64_t tests = 0;
+      for (int k = 0; k < J.spp; ++k) {
+        Rng rng{sample_state(J.key, pixel, static_cast<uint32_t>(J.sample_begin + k))};
+        const double xi1 = rng.ud();
+        const V ps0 = vadd(p00, vmul(du, px + (xi1 - 0.5)));
+        const double xi2 = rng.ud();
+        const V ps = vadd(ps0, vmul(dv, gy + (xi2 - 0.5)));
+        V org = center;
+        if (J.defocus) {
+          const V p = in_unit_disk64(rng);
+          org = vadd(vadd(center, vmul(disk_u, p.x)), vmul(disk_v, p.y));
+        }
+        const V dir = vsub(ps, org);
+        Hit64 h;
+        const size_t se = e * J.spp + k;
+        if (hit_anything64(J.s64, org, dir, 1e-3, INFINITY, &h, &tests)) {
+          const double* m = J.s64.mat + 4 * h.what;
+          const int kind = J.s64.kind[h.what];
+          if (kind == LAMB || kind == METAL) alb = vadd(alb, V{m[0], m[1], m[2]});
+          else if (kind == DIEL) alb = vadd(alb, V{1.0, 1.0, 1.0});
+          nrm = vadd(nrm, h.n);
+          const double dist = h.t * std::sqrt(vlen2(dir));
+          dmin = std::min(dmin, dist);
+          ++nh;
+          if (F.body) F.body[se] = h.what;
+          if (F.tsamp) F.tsamp[se] = dist;
+        } else {
+          const double y = vunit(dir).y;
+          const double a = 0.5 * (y + 1.0);
+          alb = vadd(alb, vadd(vmul(V{1.0, 1.0, 1.0}, 1.0 - a), vmul(V{0.5, 0.7, 1.0}, a)));
+          if (F.body) F.body[se] = -1;
+          if (F.tsamp) F.tsamp[se] = INFINITY;
+        }
+      }
+      const double n = static_cast<double>(J.spp);
+      double* out = F.mean64 + e * 8;
+      out[0] = alb.x / n, out[1] = alb.y / n, out[2] = alb.z / n;
+      out[3] = nrm.x / n, out[4] = nrm.y / n, out[5] = nrm.z / n;
+      out[6] = dmin;
+      out[7] = static_cast<double>(nh);
+    }
+  }
+}
+
+void fill_scene32(Job& J, int n, const double* sphere, const int* kind, const double* mat, const double* cam) {
+  J.s64 = Scene64{n, sphere, kind, mat};
+  J.s32.n = n;
+  J.s32.kind = kind;
+  J.s32.geo.resize(4 * static_cast<size_t>(std::max(n, 1)));
+  J.s32.sph.resize(4 * static_cast<size_t>(std::max(n, 1)));
+  J.s32.mat.resize(4 * static_cast<size_t>(std::max(n, 1)));
+  for (int i = 0; i < n; ++i) {
+    const float r = static_cast<float>(sphere[4 * i + 3]);
+    for (int k = 0; k < 3; ++k) {
+      J.s32.geo[4 * i + k] = static_cast<float>(sphere[4 * i + k]);
+      J.s32.sph[4 * i + k] = static_cast<float>(sphere[4 * i + k]);
+    }
+    J.s32.geo[4 * i + 3] = -(r * r);
+    J.s32.sph[4 * i + 3] = r;
+    for (int k = 0; k < 4; ++k) J.s32.mat[4 * i + k] = static_cast<float>(mat[4 * i + k]);
+  }
+  for (int i = 0; i < 18; ++i) {
+    J.cam64[i] = cam[i];
+    J.cam32[i] = static_cast<float>(cam[i]);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -704,26 +947,7 @@ int oracle_render_cols(int mode, int n, const double* sphere, const int* kind, c
   J.mode = mode;
   J.direct = direct;
   J.zscale = g_zscale;
-  J.s64 = Scene64{n, sphere, kind, mat};
-  J.s32.n = n;
-  J.s32.kind = kind;
-  J.s32.geo.resize(4 * static_cast<size_t>(std::max(n, 1)));
-  J.s32.sph.resize(4 * static_cast<size_t>(std::max(n, 1)));
-  J.s32.mat.resize(4 * static_cast<size_t>(std::max(n, 1)));
-  for (int i = 0; i < n; ++i) {
-    const float r = static_cast<float>(sphere[4 * i + 3]);
-    for (int k = 0; k < 3; ++k) {
-      J.s32.geo[4 * i + k] = static_cast<float>(sphere[4 * i + k]);
-      J.s32.sph[4 * i + k] = static_cast<float>(sphere[4 * i + k]);
-    }
-    J.s32.geo[4 * i + 3] = -(r * r);
-    J.s32.sph[4 * i + 3] = r;
-    for (int k = 0; k < 4; ++k) J.s32.mat[4 * i + k] = static_cast<float>(mat[4 * i + k]);
-  }
-  for (int i = 0; i < 18; ++i) {
-    J.cam64[i] = cam[i];
-    J.cam32[i] = static_cast<float>(cam[i]);
-  }
+  fill_scene32(J, n, sphere, kind, mat, cam);
   J.defocus = defocus != 0;
   J.width = width;
   J.row_begin = row_begin;
@@ -782,6 +1006,73 @@ int oracle_render(int mode, int n, const double* sphere, const int* kind, const 
                   float* out, double* out64, uint64_t* counters) {
   return oracle_render_cols(mode, n, sphere, kind, mat, cam, defocus, width, height, row_begin, row_end, row_step,
                             0, width, spp, sample_begin, max_depth, seed, nthreads, out, out64, counters);
+}
+
+// The first-hit feature pass (include/rt.h, rt_launch_feat) for rows row_begin,
+// row_begin + row_step, ... < row_end, samples sample_begin ... + spp - 1 of
+// every pixel; scene, camera and selection as oracle_render.  Two modes:
+//   MODE_MIRROR32 (| DIRECT_* << 4): the kernel's fp32 ops, restated.  sums
+//     (rows x width x 6 int64: albedo rgb as unsigned, normal xyz signed, 2^-24
+//     units), hits (rows x width) and depth (rows x width, +inf: no hit) are
+//     what rt_feat_read returns after that pass, bit for bit.
+//   MODE_REF64D (MODE_REF64: the rejection disk): MODE_REF64D's camera ray and
+//     hit_anything64 in double.  mean64 (rows x width x 8): the mean albedo
+//     (unclamped; the sky on a miss), the mean unit normal, the minimum of
+//     t * |d| (+inf: no hit), the hit count.
+// Either mode, nullable: body (rows x width x spp int32, -1: miss), tsamp (the
+// same shape, each sample's distance, +inf: miss); the mirror alone: rays
+// (rows x width x spp x 6 floats, the sample's (o, d)).
+int oracle_features(int mode, int n, const double* sphere, const int* kind, const double* mat, const double* cam,
+                    int defocus, int width, int height, int row_begin, int row_end, int row_step, int spp,
+                    int sample_begin, uint64_t seed, int nthreads, int64_t* sums, uint32_t* hits, float* depth,
+                    double* mean64, int32_t* body, double* tsamp, float* rays) {
+  if (width <= 0 || height <= 0 || row_begin < 0 || row_end > height || row_end < row_begin || row_step <= 0 ||
+      spp < 0 || (n > 0 && (!sphere || !kind || !mat)) || !cam || (mode & ~0x3f) != 0)
+    return -1;
+  const int direct = (mode >> 4) & (DIRECT_SPHERE | DIRECT_DISK);
+  mode &= 0xf;
+  const bool fp64 = mode == MODE_REF64D || mode == MODE_REF64;
+  if ((!fp64 && mode != MODE_MIRROR32) || (fp64 && (direct || !mean64 || rays)) ||
+      (!fp64 && (!sums || !hits || !depth)))
+    return -1;
+  Job J{};
+  J.mode = mode;
+  J.direct = direct;
+  J.zscale = 1.0;
+  fill_scene32(J, n, sphere, kind, mat, cam);
+  J.defocus = defocus != 0;
+  J.width = width;
+  J.row_begin = row_begin;
+  J.row_step = row_step;
+  J.spp = spp;
+  J.sample_begin = sample_begin;
+  J.key = seed_key(seed);
+  FeatJob F{};
+  F.J = &J;
+  F.fp64 = fp64;
+  F.rows = (row_end - row_begin + row_step - 1) / row_step;
+  F.sums = sums, F.hits = hits, F.depth = depth, F.mean64 = mean64;
+  F.body = body, F.tsamp = tsamp, F.rays = rays;
+  constexpr int CH = 32;
+  const int per_row = (width + CH - 1) / CH;
+  const int items = F.rows * per_row;
+  int nt = nthreads > 0 ? nthreads : static_cast<int>(std::thread::hardware_concurrency());
+  nt = std::max(1, std::min(nt, std::max(items, 1)));
+  std::atomic<int> next{0};
+  auto work = [&]() {
+    for (int it; (it = next.fetch_add(1)) < items;) {
+      const int x0 = (it % per_row) * CH;
+      feat_row(F, it / per_row, x0, std::min(width, x0 + CH));
+    }
+  };
+  if (nt == 1) {
+    work();
+  } else {
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t) th.emplace_back(work);
+    for (auto& t : th) t.join();
+  }
+  return 0;
 }
 
 // ---- known-answer entry points (fp64 reference formulas) ----

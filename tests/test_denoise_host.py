@@ -149,6 +149,52 @@ def test_other_sigmas_and_defaults():
     assert np.array_equal(bits(out), bits(host(half0, half1, feat)))
 
 
+# ---- the edge scenes' pipelines -----------------------------------------------
+def _edge_cases():
+    import feat_oracle
+    return feat_oracle.DENOISE_CASES
+
+
+def edge_inputs_are_finite(half0, half1, feat):
+    """Per pixel: finite colours and guides as rt_feat_resolve writes them (the
+    depth a positive distance, or +inf where nothing was hit)."""
+    z = feat[..., 6]
+    return (np.isfinite(half0).all(-1) & np.isfinite(half1).all(-1) & np.isfinite(feat[..., :6]).all(-1) &
+            np.isfinite(feat[..., 7]) & (z > 0) & (np.isfinite(z) | (feat[..., 7] == 0)))
+
+
+@pytest.mark.parametrize("name", _edge_cases())
+def test_edge_pipelines(name):
+    """Halves and guides as the library makes them at the edges of its inputs
+    (the oracle's mirrors of rt_launch and rt_feat, 64 x 36): the albedo floor
+    on a channel of every ground pixel (albedo_negative), albedos of 40 under
+    colours of 256, depths near 2^-60 and 2^63, a frame that is all sky.  The host equals the definition
+    bit for bit, and the output is finite wherever the inputs are."""
+    import feat_oracle
+    half0, half1, feat = feat_oracle.denoise_inputs(name)
+    fin = edge_inputs_are_finite(half0, half1, feat)
+    print(f"{name}: colours up to {max(half0.max(), half1.max()):.4g}, albedo {feat[..., :3].min():.3g} .. "
+          f"{feat[..., :3].max():.3g}, depth {feat[..., 6].min():.3g} .. {feat[..., 6][np.isfinite(feat[..., 6])].max(initial=0):.3g}, "
+          f"coverage {feat[..., 7].mean():.3f}, finite inputs on {fin.mean():.2%}")
+    assert fin.all()       # the mirrors' sums are integers: every case's inputs are finite everywhere
+    for levels in (1, 5, 8):
+        got = host(half0, half1, feat, levels=levels)
+        want = denoise_np(half0, half1, feat, levels=levels)
+        assert np.array_equal(bits(got), bits(want)), (levels, int((bits(got) != bits(want)).sum()))
+        assert np.isfinite(got[fin]).all(), (levels, int((~np.isfinite(got)).any(-1).sum()))
+    # what the case is about reaches the filter
+    if name == "albedo_negative":
+        assert (feat[..., 1] < 2.0 ** -10).mean() > 0.3
+    if name == "albedo_saturating":
+        assert max(half0.max(), half1.max()) > 200 and feat[..., :3].max() == 40
+    if name == "scale_2^-62":
+        assert feat[..., 6].max() < 2.0 ** -58
+    if name == "scale_2^62":
+        assert feat[..., 6].min() > 2.0 ** 63
+    if name == "scale_2^63":
+        assert not feat[..., 7].any() and np.isinf(feat[..., 6]).all()
+
+
 # ---- exact edge stops -------------------------------------------------------
 # The variance pre-filter (step 1 of a level) is a plain 3 x 3 mean: it crosses
 # every edge by definition, so a change of a region's *variance* reaches its

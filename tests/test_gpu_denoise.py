@@ -192,6 +192,84 @@ def test_interleaved_shards(env, pipeline):
     assert np.array_equal(bits(got), bits(p.want))
 
 
+# ---- the edge scenes' pipelines -----------------------------------------------
+def _edge_cases():
+    import feat_oracle
+    return feat_oracle.DENOISE_CASES
+
+
+@pytest.mark.parametrize("name", _edge_cases())
+def test_edge_pipelines(env, name):
+    """tests/test_denoise_host.py's edge pipelines on the device: Progressive
+    x 2 and Features, resolved on the device, reproduce the oracle's inputs
+    bit for bit, and Denoiser.run equals the host on them at levels 1, 5, 8."""
+    import edge_scenes as E
+    import feat_oracle
+    R, torch = env.R, env.torch
+    sc, cam, meta = E.case(name)
+    p = E.params(meta)
+    half0, half1, feat = feat_oracle.denoise_inputs(name)
+    d_h = [nan_buf(env, E.W * E.H * 3) for _ in range(2)]
+    d_feat = nan_buf(env, E.W * E.H * 8)
+    kw = dict(seed=p["seed"])
+    with R.Progressive(sc, cam, E.W, E.H, max_depth=p["max_depth"], **kw) as a0, \
+            R.Progressive(sc, cam, E.W, E.H, max_depth=p["max_depth"], sample_begin=8, **kw) as a1, \
+            R.Features(sc, cam, E.W, E.H, **kw) as ft:
+        a0.add(8)
+        a1.add(8)
+        ft.add(16)
+        a0.resolve_into(d_h[0].data_ptr())
+        a1.resolve_into(d_h[1].data_ptr())
+        ft.resolve_into(d_feat.data_ptr())
+        torch.cuda.synchronize()
+    for d, a, what in ((d_h[0], half0, "half0"), (d_h[1], half1, "half1"), (d_feat, feat, "feat")):
+        assert np.array_equal(bits(d.cpu().numpy()), bits(a).reshape(-1)), (name, what)
+    with R.Denoiser(E.W, E.H) as dn:
+        for levels in (1, 5, 8):
+            out = nan_buf(env, E.W * E.H * 3)
+            dn.run(d_h[0].data_ptr(), d_h[1].data_ptr(), d_feat.data_ptr(), out.data_ptr(), levels=levels)
+            torch.cuda.synchronize()
+            got = out.cpu().numpy().reshape(E.H, E.W, 3)
+            want = R.denoise_host(half0, half1, feat, levels=levels)
+            assert np.isfinite(got).all(), (name, levels)
+            assert np.array_equal(bits(got), bits(want)), (name, levels, int((bits(got) != bits(want)).sum()))
+
+
+def test_unspecified_inputs_stay_local(env):
+    """40 x 33, 2 levels: a 4 x 4 corner block of NaN, +-inf, negative
+    colours, depth 0, negative depth, denormals and 3e38.  rt.h leaves the
+    numbers there unspecified; the call returns 0, and no pixel more than 8
+    pixels (Chebyshev) from the block differs from the host's bits: levels 0
+    and 1 reach 2 + 4 = 6 pixels.  The agreement inside that reach is printed."""
+    from rtclj._lib import lib, rt_denoise_opts
+    rows, width = 40, 33
+    half0, half1, feat = (a.copy() for a in random_inputs(rows, width, seed=77))
+    nan, inf, den = np.float32("nan"), np.float32("inf"), np.float32(1e-42)
+    half0[0, 0], half0[0, 1], half0[0, 2], half0[0, 3] = nan, inf, -inf, (-1.0, -2.0, -0.5)
+    half1[1, 0], half1[1, 1], half1[1, 2], half1[1, 3] = (3e38, 3e38, 3e38), den, (nan, 1.0, inf), -inf
+    half0[2, 0], half1[2, 0] = 3e38, 3e38
+    half0[2, 1], half1[2, 1] = den, den
+    feat[2, 2, 6], feat[2, 3, 6], feat[3, 0, 6], feat[3, 1, 6] = 0.0, -4.0, nan, den       # depths
+    feat[3, 2, 3:6], feat[3, 3, 3:6], feat[0, 0, 7], feat[1, 1, 7] = nan, (inf, -inf, 3e38), nan, -inf
+    feat[0, 2, 0:3], feat[1, 3, 0:3], feat[2, 0, 0:3] = (nan, -1.0, den), inf, 3e38
+    d0, d1, df = dev(env, half0), dev(env, half1), dev(env, feat)
+    out = nan_buf(env, rows * width * 3)
+    with env.R.Denoiser(width, rows) as dn:
+        o = rt_denoise_opts(levels=2, normal_pow2=5, sigma_c=4.0, sigma_z=0.05)
+        rc = lib.rt_denoise(dn._dn, C.byref(o), *(C.c_void_p(t.data_ptr()) for t in (d0, d1, df, out)), None)
+        assert rc == 0, lib.rt_last_error()
+        env.torch.cuda.synchronize()
+    got = out.cpu().numpy().reshape(rows, width, 3)
+    want = env.R.denoise_host(half0, half1, feat, levels=2)
+    y, x = np.mgrid[0:rows, 0:width]
+    far = np.maximum(y - 3, x - 3) > 8
+    assert far.sum() > rows * width // 2
+    assert np.isfinite(want[far]).all() and np.array_equal(bits(got[far]), bits(want[far]))
+    near = ~far
+    same = ((bits(got) == bits(want)) | (np.isnan(got) & np.isnan(want))).all(-1)
+    print(f"inside the block's reach: {same[near].mean():.2%} of {int(near.sum())} pixels agree with the host")
+
+
 # ---- rt_adapt_resolve_half --------------------------------------------------
 def test_adapt_halves(env):
     from rtclj._lib import RT_FLAG_REALM, fptr, lib, u32ptr, u64ptr

@@ -168,6 +168,68 @@ def test_sharded_render_with_a_high_bit_seed(gpu_lib):
     assert not np.array_equal(whole, E.mirror(name, seed=1)[0])
 
 
+ACCUM_CASES = ["albedo_gt1", "albedo_gt1_metal", "albedo_negative", "albedo_saturating", "eta_inf", "nonfinite_65",
+               "ties_big", "scale_2^-62", "scale_2^63", "seed_2^64-1", "sample_begin_2^32-8"]
+
+
+@pytest.mark.parametrize("name", ACCUM_CASES)
+def test_accumulated_passes_equal_mirror(gpu_lib, name):
+    """rt_launch_accum at the edges: the case's 16 samples in passes of 5 + 11
+    into one rt_accum -- on one stream, and again with the two passes on two
+    streams -- resolved into a NaN-filled buffer, equal the mirror's frame
+    (NaN == NaN), and the counters its segments and samples.  Where an albedo
+    leaves [-1, 1] the passes add through the u64 epilogue (global atomics)."""
+    import ctypes as C
+
+    import torch
+    from rtclj._lib import lib, rt_params
+    sc, cam, meta = E.case(name)
+    p = E.params(meta)
+    m, segs, smp = E.mirror(name)
+    ds = C.c_void_p()
+    assert lib.rt_scene_upload(0, C.byref(sc.c), C.byref(ds)) == 0, lib.rt_last_error()
+
+    def params(spp, begin):
+        return rt_params(width=E.W, height=E.H, row_begin=0, row_end=E.H, spp=spp, max_depth=p["max_depth"],
+                         seed=p["seed"], sample_begin=begin)
+    try:
+        for streams in (1, 2):
+            ss = [torch.cuda.Stream() for _ in range(streams)]
+            acc = C.c_void_p()
+            assert lib.rt_accum_create(ds, C.byref(params(16, p["sample_begin"])), C.byref(acc)) == 0, lib.rt_last_error()
+            try:
+                cnt = torch.zeros(2, dtype=torch.int64, device="cuda")
+                out = torch.full((E.H * E.W * 3 + 3,), float("nan"), dtype=torch.float32, device="cuda")
+                torch.cuda.synchronize()
+                begin = p["sample_begin"]
+                for i, n in enumerate((5, 11)):     # (both enqueued before either is waited for)
+                    rc = lib.rt_launch_accum(ds, C.byref(cam), C.byref(params(n, begin)), acc, C.c_void_p(cnt.data_ptr()),
+                                             C.c_void_p(ss[i % streams].cuda_stream))
+                    assert rc == 0, lib.rt_last_error()
+                    begin += n
+                torch.cuda.synchronize()
+                assert lib.rt_accum_samples(acc) == 16
+                rc = lib.rt_accum_resolve(acc, 0, C.c_void_p(out.data_ptr()), C.c_void_p(ss[0].cuda_stream))
+                assert rc == 0, lib.rt_last_error()
+                torch.cuda.synchronize()
+                f = out.cpu().numpy()
+                assert np.isnan(f[-3:]).all()               # the guard behind the frame
+                g = f[:-3].reshape(E.H, E.W, 3)
+                assert _same(g, m), (name, streams, _differing(g, m))
+                assert cnt.cpu().numpy().tolist() == [segs, smp], (name, streams)
+                if np.isfinite(m).all():
+                    assert np.isfinite(g).all()
+            finally:
+                lib.rt_accum_free(acc)
+    finally:
+        lib.rt_scene_free(ds)
+    # not vacuous
+    if name.startswith("albedo_gt1") or name == "albedo_saturating":
+        assert not meta["unit"] and m.max() > 1
+    if name == "scale_2^63":
+        assert segs == smp
+
+
 @pytest.mark.parametrize("name", ["albedo_saturating", "albedo_negative"])
 def test_render_u8_clamps_as_rt_quantize(gpu_lib, name):
     """rt_render_u8 on frames that leave [0, 1]: exactly rt_quantize's bytes

@@ -11,6 +11,14 @@
 // and of the reference camera (jittered pixels, defocus disk), and as many
 // rays with origins inside the tree's bounding sphere and isotropic
 // directions, every fourth with one or two components exactly zero.
+//
+//   first_hit_check --scene FILE --rays FILE
+// The same checks -- walk equals scan over the three trees, the stack within
+// depth - 1, and that it ends -- for a caller's inputs, raw little-endian
+// float32: bodies as n x (cx, cy, cz, r), rays as m x (o, d).  Non-finite
+// bodies and rays are inputs like any other (tests/test_first_hit_walk.py
+// feeds the edge scenes' bodies and the oracle's camera rays).  Another JSON
+// line; exit status 1 on a mismatch, 2 on unreadable input.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -146,9 +154,130 @@ uint32_t bits(float f) {
   return u;
 }
 
+// bvh_build's three trees (2, 4 and 8 bodies per leaf) as the walk reads them
+struct Trees {
+  BvhHost bvh[3];
+  std::vector<char> blob[3];
+  FhTree tree[3];
+  std::vector<float> geo;   // n x (cx, cy, cz, -r^2): the scan's
+  int max_depth = 0;
+};
+
+void build_trees(const std::vector<float>& sph, Trees* T) {
+  const int n = static_cast<int>(sph.size() / 4);
+  T->geo.resize(4 * static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) {
+    for (int k = 0; k < 3; ++k) T->geo[4 * i + k] = sph[4 * i + k];
+    T->geo[4 * i + 3] = -(sph[4 * i + 3] * sph[4 * i + 3]);
+  }
+  for (int k = 0; k < 3; ++k) {
+    bvh_build(sph.data(), n, &T->bvh[k], 2 << k, true);
+    const BvhHost& b = T->bvh[k];
+    const size_t nb = b.nodes.size() * sizeof(BvhNode), pb = b.pairs.size() * sizeof(float),
+                 ib = b.pidx.size() * sizeof(int);
+    T->blob[k].assign(nb + pb + ib, 0);
+    std::memcpy(T->blob[k].data(), b.nodes.data(), nb);
+    std::memcpy(T->blob[k].data() + nb, b.pairs.data(), pb);
+    std::memcpy(T->blob[k].data() + nb + pb, b.pidx.data(), ib);
+    FhTree& t = T->tree[k];
+    t.base = T->blob[k].data();
+    t.off_pairs = static_cast<int>(nb);
+    t.off_pidx = static_cast<int>(nb + pb);
+    t.leaf_pairs = 1 << k;
+    t.big_pair0 = b.big_pair0;
+    t.n_big_leaves = b.n_big_leaves;
+    t.ref_mul = static_cast<int>(sizeof(BvhNode));
+    for (int j = 0; j < 3; ++j) t.c[j] = b.center[j];
+    t.r = b.radius;
+    t.c0 = kPadRmax * b.r_max;
+    T->max_depth = b.depth > T->max_depth ? b.depth : T->max_depth;
+  }
+}
+
+struct Tally {
+  long long mismatches[3] = {0, 0, 0};
+  long long stack_over = 0;
+  int peak = 0;
+};
+
+// one ray: the scan's answer, and every tree's walk held to it
+FhBest check_ray(const Trees& T, const FhRay& r, Tally* tl) {
+  FhBest ref = fh_none();
+  fh_scan(r, T.geo.data(), static_cast<int>(T.geo.size() / 4), ref);
+  for (int k = 0; k < 3; ++k) {
+    HostStack st;
+    FhBest got = fh_none();
+    fh_walk(r, T.tree[k], st, got);
+    if (got.body != ref.body || bits(got.t) != bits(ref.t) || st.over) ++tl->mismatches[k];
+    // the device's stack holds depth + 1 rows: depth - 1 suffice
+    if (st.peak > T.bvh[k].depth - 1 && st.peak > 0) ++tl->stack_over;
+    tl->peak = st.peak > tl->peak ? st.peak : tl->peak;
+  }
+  return ref;
+}
+
+bool read_floats(const char* path, size_t per, std::vector<float>* out) {
+  std::FILE* f = std::fopen(path, "rb");
+  if (!f) return false;
+  std::fseek(f, 0, SEEK_END);
+  const long bytes = std::ftell(f);
+  std::fseek(f, 0, SEEK_SET);
+  bool ok = bytes >= 0 && static_cast<size_t>(bytes) % (per * sizeof(float)) == 0;
+  if (ok) {
+    out->resize(static_cast<size_t>(bytes) / sizeof(float));
+    ok = out->empty() || std::fread(out->data(), sizeof(float), out->size(), f) == out->size();
+  }
+  std::fclose(f);
+  return ok;
+}
+
+// --scene FILE --rays FILE: the same checks for a caller's bodies (n x (cx, cy,
+// cz, r)) and rays (m x (o, d)), raw little-endian float32
+int check_files(const char* scene_path, const char* rays_path) {
+  std::vector<float> sph, rays;
+  if (!read_floats(scene_path, 4, &sph) || !read_floats(rays_path, 6, &rays) || sph.size() / 4 > RT_MAX_SPHERES) {
+    std::fprintf(stderr, "first_hit_check: cannot read %s (n x 4 floats, n <= %d) or %s (m x 6 floats)\n", scene_path,
+                 RT_MAX_SPHERES, rays_path);
+    return 2;
+  }
+  Trees T;
+  build_trees(sph, &T);
+  Tally tl;
+  long long hits = 0, odd_rays = 0;
+  const size_t m = rays.size() / 6;
+  for (size_t i = 0; i < m; ++i) {
+    const float* q = &rays[6 * i];
+    const FhRay r = fh_ray(q[0], q[1], q[2], q[3], q[4], q[5]);
+    // |d| zero, infinite or NaN: a unit direction that is not one
+    odd_rays += !(std::isfinite(r.len) && r.len > 0.0f && std::isfinite(r.ux) && std::isfinite(r.uy) &&
+                  std::isfinite(r.uz));
+    hits += check_ray(T, r, &tl).body >= 0;
+  }
+  std::printf(
+      "{\"bodies\": %d, \"rays\": %zu, \"hits\": %lld, \"misses\": %lld, \"odd_rays\": %lld, \"big_bodies\": %d, "
+      "\"tree_nodes\": {\"2\": %zu, \"4\": %zu, \"8\": %zu}, \"mismatches\": {\"2\": %lld, \"4\": %lld, \"8\": %lld}, "
+      "\"stack_peak\": %d, \"stack_over_depth\": %lld, \"max_depth\": %d}\n",
+      static_cast<int>(sph.size() / 4), m, hits, static_cast<long long>(m) - hits, odd_rays,
+      static_cast<int>(T.bvh[1].big.size()), T.bvh[0].nodes.size(), T.bvh[1].nodes.size(), T.bvh[2].nodes.size(),
+      tl.mismatches[0], tl.mismatches[1], tl.mismatches[2], tl.peak, tl.stack_over, T.max_depth);
+  return (tl.mismatches[0] | tl.mismatches[1] | tl.mismatches[2] | tl.stack_over) ? 1 : 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+  const char *scene_path = nullptr, *rays_path = nullptr;
+  for (int i = 1; i + 1 < argc; ++i) {
+    if (!std::strcmp(argv[i], "--scene")) scene_path = argv[i + 1];
+    if (!std::strcmp(argv[i], "--rays")) rays_path = argv[i + 1];
+  }
+  if (scene_path || rays_path) {
+    if (!scene_path || !rays_path) {
+      std::fprintf(stderr, "usage: first_hit_check [seed] | --scene FILE --rays FILE\n");
+      return 2;
+    }
+    return check_files(scene_path, rays_path);
+  }
   const uint64_t seed = argc > 1 ? std::strtoull(argv[1], nullptr, 10) : 42;
   Rng rng{seed};
   std::vector<Scene> scenes(3);
@@ -169,42 +298,17 @@ int main(int argc, char** argv) {
     }
     scenes[2] = {"duplicated", dup};
   }
-  long long rays_all = 0, cam_rays = 0, cam_hits = 0, tie_rays = 0, big_hits = 0, stack_over = 0;
-  long long mismatches[3] = {0, 0, 0};
-  int cover_big = 0, peak = 0, max_depth = 0;
+  long long rays_all = 0, cam_rays = 0, cam_hits = 0, tie_rays = 0, big_hits = 0;
+  Tally tl;
+  int cover_big = 0, max_depth = 0;
   for (size_t si = 0; si < scenes.size(); ++si) {
     const Scene& sc = scenes[si];
     const int n = sc.n();
-    std::vector<float> geo(4 * static_cast<size_t>(n));
-    for (int i = 0; i < n; ++i) {
-      for (int k = 0; k < 3; ++k) geo[4 * i + k] = sc.sph[4 * i + k];
-      geo[4 * i + 3] = -(sc.sph[4 * i + 3] * sc.sph[4 * i + 3]);
-    }
-    BvhHost bvh[3];
-    std::vector<char> blob[3];
-    FhTree tree[3];
-    for (int k = 0; k < 3; ++k) {
-      bvh_build(sc.sph.data(), n, &bvh[k], 2 << k, true);
-      const BvhHost& b = bvh[k];
-      const size_t nb = b.nodes.size() * sizeof(BvhNode), pb = b.pairs.size() * sizeof(float),
-                   ib = b.pidx.size() * sizeof(int);
-      blob[k].assign(nb + pb + ib, 0);
-      std::memcpy(blob[k].data(), b.nodes.data(), nb);
-      std::memcpy(blob[k].data() + nb, b.pairs.data(), pb);
-      std::memcpy(blob[k].data() + nb + pb, b.pidx.data(), ib);
-      FhTree& t = tree[k];
-      t.base = blob[k].data();
-      t.off_pairs = static_cast<int>(nb);
-      t.off_pidx = static_cast<int>(nb + pb);
-      t.leaf_pairs = 1 << k;
-      t.big_pair0 = b.big_pair0;
-      t.n_big_leaves = b.n_big_leaves;
-      t.ref_mul = static_cast<int>(sizeof(BvhNode));
-      for (int j = 0; j < 3; ++j) t.c[j] = b.center[j];
-      t.r = b.radius;
-      t.c0 = kPadRmax * b.r_max;
-      max_depth = b.depth > max_depth ? b.depth : max_depth;
-    }
+    Trees T;
+    build_trees(sc.sph, &T);
+    const BvhHost* bvh = T.bvh;
+    const std::vector<float>& geo = T.geo;
+    max_depth = T.max_depth > max_depth ? T.max_depth : max_depth;
     if (si == 0) cover_big = static_cast<int>(bvh[1].big.size());
     std::vector<char> is_big(n, 0);
     for (int i : bvh[1].big) is_big[i] = 1;
@@ -216,8 +320,7 @@ int main(int argc, char** argv) {
     for (size_t ri = 0; ri < rays.size(); ++ri) {
       const Ray& q = rays[ri];
       const FhRay r = fh_ray(q.o[0], q.o[1], q.o[2], q.d[0], q.d[1], q.d[2]);
-      FhBest ref = fh_none();
-      fh_scan(r, geo.data(), n, ref);
+      const FhBest ref = check_ray(T, r, &tl);
       ++rays_all;
       if (ri < n_cam) {
         ++cam_rays;
@@ -231,17 +334,11 @@ int main(int argc, char** argv) {
                 geo[4 * (ref.body + 32) + 3], ref.body + 32, twin);
         tie_rays += twin.body >= 0 && bits(twin.t) == bits(ref.t);
       }
-      for (int k = 0; k < 3; ++k) {
-        HostStack st;
-        FhBest got = fh_none();
-        fh_walk(r, tree[k], st, got);
-        if (got.body != ref.body || bits(got.t) != bits(ref.t) || st.over) ++mismatches[k];
-        // the device's stack holds depth + 1 rows: depth - 1 suffice
-        if (st.peak > bvh[k].depth - 1 && st.peak > 0) ++stack_over;
-        peak = st.peak > peak ? st.peak : peak;
-      }
     }
   }
+  const long long* mismatches = tl.mismatches;
+  const long long stack_over = tl.stack_over;
+  const int peak = tl.peak;
   std::printf(
       "{\"rays\": %lld, \"camera_rays\": %lld, \"camera_hits\": %lld, \"camera_misses\": %lld, \"tie_rays\": %lld, "
       "\"cover_big_bodies\": %d, \"big_hits\": %lld, \"mismatches\": {\"2\": %lld, \"4\": %lld, \"8\": %lld}, "
