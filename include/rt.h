@@ -691,6 +691,134 @@ int rt_denoise_profile(rt_denoiser* dn, const rt_denoise_opts* o, const float* d
 int rt_denoise_host(const rt_denoise_opts* o, const float* half0, const float* half1, const float* feat,
                     int width, int rows, float* out);
 
+/* ---- temporal accumulation: history reprojected through first-hit depth -------
+ * What a sequence of low-sample frames of compute-pixel's loop
+ * (raytracing.clj:141-155) keeps from one frame to the next: per pixel, the
+ * accumulated colour of the frames already drawn, fetched from where the
+ * pixel's surface point was in the previous frame (found through
+ * rt_feat_resolve's depth and the two cameras) if the previous frame saw the
+ * same surface there, and blended with the current sample -- the temporal half
+ * of SVGF (Schied et al. 2017), between the resolves and rt_denoise.  The two
+ * half-frames are accumulated separately: half 0's history only ever receives
+ * half-0 samples, so the halves stay independent estimates and rt_denoise's
+ * variance term (0.25 d) d shrinks on its own as the history builds.  As the
+ * denoiser, a fixed sequence of single fp32 operations, each rounded once in
+ * the order written (no fma; / and sqrt IEEE), which the device kernel,
+ * rt_temporal_host and a NumPy restatement (tests/test_temporal_host.py) give
+ * bit for bit, whatever the workgroup shape.
+ *
+ * Image: rows x width, contiguous; image row y is camera row row0 + y.  A
+ * contiguous row band may be filtered on its own; taps outside the band count
+ * as outside the image.
+ * Inputs per step: half0, half1 (rows x width x 3 floats each) and feat (rows x
+ * width x 8 floats) as for rt_denoise, and the camera that drew them.
+ * Options (NULL: the defaults; outside the ranges: RT_E_ARG):
+ *   max_history  32    1..65536        cap on the history length
+ *   sigma_z      0.1   finite > 0      relative depth tolerance
+ *   normal_min   0.9   finite, -1..1   least normal dot product accepted
+ * History, per pixel: a0, a1 the accumulated halves (rgb each), g = (n_x, n_y,
+ * n_z, z) the guides of the frame that wrote them, and a length L >= 0 as a
+ * float (0: none); and a copy of the previous camera (primed below).
+ *
+ * Host set-up, once per step, in double on the previous camera's fp32 fields,
+ * widened:
+ *   q = p00' - center'
+ *   c0 = dv' x q, c1 = q x du', c2 = du' x dv'  ((a x b)_x = a_y b_z - a_z b_y
+ *   and cyclic), det = du' . c0 summed as (x + y) + z,
+ *   R_k = c_k / det, each component rounded once to fp32 (k = 0, 1, 2).
+ * A det that is 0 or not finite: RT_E_ARG.  dc = center - center' per
+ * component in fp32.
+ *
+ * Per pixel (x, y), j = row0 + y:
+ *   1. e_c = ((p00_c + float(x) * du_c) + float(j) * dv_c) - center_c  (the pixel
+ *      centre's pinhole ray; the lens jitter is ignored, see below).
+ *   2. z_p = feat[6].  If z_p is finite: len = sqrt((e_x^2 + e_y^2) + e_z^2),
+ *      sc = z_p / len, w_c = sc * e_c + dc_c, zexp = sqrt((w_x^2 + w_y^2) + w_z^2).
+ *      Otherwise (sky): w = e, zexp = +inf.
+ *   3. alpha = (R0_x w_x + R0_y w_y) + R0_z w_z; beta, gamma likewise from R1,
+ *      R2.  gamma not > 0: no history.  Else fx = alpha / gamma,
+ *      fy = beta / gamma - float(row0); fx not (> -1 and < float(width)), or fy
+ *      not (> -1 and < float(rows)): no history.  NaN fails these comparisons;
+ *      no float is converted to an integer before them.
+ *   4. x0 = floor(fx), tx = fx - x0; tx < 2^-6: tx = 0; else tx > 1 - 2^-6:
+ *      x0 += 1, tx = 0.  The same for y.  (A still camera is an exact identity,
+ *      and no resampling blur below 1/64 pixel.)
+ *   5. Taps (x0 + dx, y0 + dy), dy outer, each 0..1, with
+ *      b = (dx ? tx : 1 - tx) * (dy ? ty : 1 - ty); a tap with b == 0 or outside
+ *      the image is skipped before any load.  A tap q is valid iff L'_q >= 1,
+ *      and both z'_q and zexp are +inf, or both are finite and
+ *      |z'_q - zexp| <= sigma_z * zexp and
+ *      (n_p.x n'_q.x + n_p.y n'_q.y) + n_p.z n'_q.z >= normal_min
+ *      (n_p = feat[3..5]).  Over the valid taps, in tap order, from 0:
+ *      acc0_c += b * a0'_q.c, acc1_c += b * a1'_q.c, accL += b * L'_q, bsum += b.
+ *   6. History is accepted iff bsum >= 0.25: h0 = acc0 / bsum, h1 = acc1 / bsum,
+ *      Lh = accL / bsum, N = min(Lh + 1, float(max_history)), k = 1 / N,
+ *      out0_c = h0_c + k * (half0_c - h0_c), out1_c likewise.  Without history
+ *      out = half and N = 1.
+ *   7. a0 = out0, a1 = out1, g = feat[3..6], L = N are stored; the current
+ *      camera becomes the previous one.
+ * The first step after create or reset has no history (L' = 0 everywhere): it
+ * returns its inputs.
+ *
+ * To know: glass and mirrors are reprojected as their first surface, so what
+ * they show lags the camera; the depth is rt_feat's nearest hit over jittered,
+ * defocused rays, used as if through the pinhole pixel centre -- that error is
+ * what sigma_z absorbs; colour is accumulated modulated, so texture is
+ * bilinearly resampled under motion (the scenes here have one albedo per
+ * body); moving bodies are not handled (a scene is static between frames);
+ * and the sample indices of successive frames must differ (the caller's
+ * sample_begin or seed), or the history repeats one estimate.
+ *
+ * The inputs are never written.  Outputs may not overlap inputs or each other
+ * (RT_E_ARG).  Inputs are expected as the library produces them; other values
+ * -- NaN colours, a depth <= 0, cameras far apart -- give unspecified numbers,
+ * never an out-of-range index, a fault or a hang.  A failed call leaves the
+ * state, the previous camera included, unchanged. */
+typedef struct rt_temporal_opts {
+  int max_history;
+  float sigma_z, normal_min;
+} rt_temporal_opts;
+typedef struct rt_temporal rt_temporal;
+/* raytracing.clj:141-155's frames, one after another: the history of rows x
+ * width images whose first row is camera row row0, on `device`, empty.  It
+ * owns two history sets -- a step gathers from the old one while it writes the
+ * new -- of three 16-byte words a pixel each: (a0 rgb, L), (a1 rgb, 0) and the
+ * guides.  RT_E_ARG on width or rows <= 0, more than 2^31 - 1 pixels or a
+ * negative row0, RT_E_NODEV on a device that is not there. */
+int rt_temporal_create(int device, int width, int rows, int row0, rt_temporal** out);
+int rt_temporal_free(rt_temporal* t);   /* NULL: 0 */
+/* raytracing.clj:141-155's loop from its start: forget the history (L = 0
+ * everywhere, enqueued on hip_stream) and the previous camera. */
+int rt_temporal_reset(rt_temporal* t, void* hip_stream);
+/* Steps since the last reset (raytracing.clj:141-155's frame counter); -1 on NULL. */
+int64_t rt_temporal_frames(const rt_temporal* t);
+/* One step (raytracing.clj:141-155, per frame).  Asynchronous, on hip_stream
+ * (NULL: the default stream) of t's device: d_out0, d_out1 (device, rows x
+ * width x 3 floats each) = the accumulated halves, which are also the new
+ * history.  d_half0, d_half1, d_feat are device pointers, aligned as floats.
+ * Steps of one object go on one stream, or are ordered by the caller.
+ * RT_E_ARG on a NULL argument, bad options, a degenerate previous camera, an
+ * output overlapping an input or the other output, or a stream of another
+ * device. */
+int rt_temporal_step(rt_temporal* t, const rt_temporal_opts* o, const rt_camera* cam, const float* d_half0,
+                     const float* d_half1, const float* d_feat, float* d_out0, float* d_out1, void* hip_stream);
+/* The current history copied out behind hip_stream's work (tests, checkpoints;
+ * raytracing.clj:141-155's state): host_a0, host_a1 (rows x width x 3 floats),
+ * host_guide (rows x width x 4), host_len (rows x width); any may be NULL.
+ * Returns when they are there. */
+int rt_temporal_read(const rt_temporal* t, float* host_a0, float* host_a1, float* host_guide, float* host_len,
+                     void* hip_stream);
+/* The same step on the host, in plain C++ (no device; raytracing.clj:141-155):
+ * the yardstick of the kernel.  prev_cam == NULL: no history (the prev_ arrays
+ * are not read); else prev_a0, prev_a1, prev_guide, prev_len are the history
+ * in rt_temporal_read's layout.  out0, out1 (rows x width x 3) and out_len
+ * (rows x width) are the new history's a0, a1 and L; its guides are
+ * feat[3..6]. */
+int rt_temporal_host(const rt_temporal_opts* o, const rt_camera* cam, const rt_camera* prev_cam, int width, int rows,
+                     int row0, const float* half0, const float* half1, const float* feat, const float* prev_a0,
+                     const float* prev_a1, const float* prev_guide, const float* prev_len, float* out0, float* out1,
+                     float* out_len);
+
 /* Asynchronous: enqueue rt_quantize on hip_stream's device for n channels
  * already in HBM (d_lin: n floats, d_out: n bytes, device pointers): the same
  * bytes as rt_quantize for every float (NaN, infinities and denormals

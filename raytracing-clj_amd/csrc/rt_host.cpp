@@ -33,6 +33,7 @@
 #include "denoise.h"
 #include "first_hit.h"
 #include "rt_internal.h"
+#include "temporal.h"
 
 namespace rtclj {
 
@@ -297,6 +298,19 @@ extern "C" int rt_denoise_host(const rt_denoise_opts* o, const float* half0, con
   const std::vector<DnTexel>& last = tex[opt.levels & 1];
   for (size_t i = 0; i < n_px; ++i) dn_finish(last[i], feat + RT_FEAT_CHANNELS * i, out + 3 * i);
   return RT_OK;
+}
+
+// rt_temporal_step on the host (temporal.h's tp_host_step: the checks and
+// tp_pixel, the text the kernel runs)
+extern "C" int rt_temporal_host(const rt_temporal_opts* o, const rt_camera* cam, const rt_camera* prev_cam, int width,
+                                int rows, int row0, const float* half0, const float* half1, const float* feat,
+                                const float* prev_a0, const float* prev_a1, const float* prev_guide,
+                                const float* prev_len, float* out0, float* out1, float* out_len) {
+  clear_error();
+  const char* why = nullptr;
+  const int rc = tp_host_step(o, cam, prev_cam, width, rows, row0, half0, half1, feat, prev_a0, prev_a1, prev_guide,
+                              prev_len, out0, out1, out_len, &why);
+  return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_temporal_host: ") + (why ? why : "failed"));
 }
 
 extern "C" int rt_write_ppm(const char* path, const uint8_t* rgb, int width, int height) {

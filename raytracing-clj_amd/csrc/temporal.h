@@ -1,0 +1,364 @@
+// temporal.h — temporal accumulation (rt_temporal_*, include/rt.h): the
+// accumulated half-frames of the frames already drawn, reprojected through
+// rt_feat_resolve's first-hit depth into the current camera and blended with
+// the current halves -- the temporal half of SVGF (Schied et al. 2017), whose
+// spatial half is denoise.h.  The two halves are accumulated separately, so
+// they stay independent estimates and rt_denoise's variance term shrinks on
+// its own as the history builds.
+//
+// Replaces nothing the reference computes: it consumes what compute-pixel's
+// loop (src/raytracing.clj:141-155) leaves in rt_accum / rt_adapt / rt_feat,
+// one frame after another.
+//
+// Three parts, as denoise.h.
+//  1. The definition as plain inline functions that compile for the device
+//     (the kernel below) and for the host (rt_temporal_host): one pixel of one
+//     step.  One text for both: every line is one fp32 operation rounded once,
+//     in rt.h's order (built with -ffp-contract=off); / and sqrt are IEEE on
+//     either side.  A pixel reads the history through a `Src` -- three
+//     accessors -- so the host may keep it as plain arrays and the device as
+//     16-byte words.
+//  2. The step on the host, checks included (tp_host_step): what
+//     rt_temporal_host runs, and what tools/temporal_check.cpp runs under the
+//     sanitizers.
+//  3. The device kernel (under __HIPCC__ and RT_TEMPORAL_KERNEL): one thread
+//     per pixel, no atomics, no scratch; the bits cannot depend on the launch
+//     shape.
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+
+#include "denoise.h"
+
+namespace rtclj {
+
+// A history word: (a0 rgb, L) or (a1 rgb, 0).
+struct alignas(16) TpWord {
+  float r, g, b, l;
+};
+
+constexpr int kTpMaxHistory = 65536;
+
+// rt.h's defaults
+RT_DN_FN rt_temporal_opts tp_default_opts() {
+  rt_temporal_opts o;
+  o.max_history = 32;
+  o.sigma_z = 0.1f;
+  o.normal_min = 0.9f;
+  return o;
+}
+// nullptr, or which rule of rt.h's table the options break
+inline const char* tp_opts_error(const rt_temporal_opts& o) {
+  if (o.max_history < 1 || o.max_history > kTpMaxHistory) return "max_history outside 1..65536";
+  if (!(o.sigma_z > 0.0f) || !(o.sigma_z < INFINITY)) return "sigma_z is not finite and > 0";
+  if (!(o.normal_min >= -1.0f) || !(o.normal_min <= 1.0f)) return "normal_min outside -1..1";
+  return nullptr;
+}
+// nullptr, or what is wrong with an image of rows x width whose first row is
+// camera row row0 (the kernel's grid has a block row per kDnBy image rows)
+inline const char* tp_shape_error(int width, int rows, int row0) {
+  if (width <= 0 || rows <= 0 || static_cast<int64_t>(width) * rows > 0x7fffffffll) return "bad width/rows";
+  if (row0 < 0 || static_cast<int64_t>(row0) + rows > 0x7fffffffll) return "bad row0";
+  return nullptr;
+}
+
+// What one step needs besides the arrays: the current camera's pinhole part,
+// the previous camera's inverse basis R (rows R0, R1, R2) and dc = center -
+// center', the image and the options.  The kernel takes it by value.
+struct TpFrame {
+  float center[3], p00[3], du[3], dv[3];
+  float R[9], dc[3];
+  int width, rows, row0, have_prev;
+  float max_history, sigma_z, normal_min;
+};
+
+// The host set-up of a step (rt.h): R and dc from the previous camera, in
+// double on its fp32 fields.  false: det is 0 or not finite.
+inline bool tp_setup(const rt_camera& cur, const rt_camera& prev, float* R9, float* dc3) {
+  double q[3], du[3], dv[3];
+  for (int c = 0; c < 3; ++c) {
+    q[c] = static_cast<double>(prev.p00[c]) - static_cast<double>(prev.center[c]);
+    du[c] = prev.du[c];
+    dv[c] = prev.dv[c];
+  }
+  auto cross = [](const double* a, const double* b, double* o) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+  };
+  double c0[3], c1[3], c2[3];
+  cross(dv, q, c0);
+  cross(q, du, c1);
+  cross(du, dv, c2);
+  const double det = (du[0] * c0[0] + du[1] * c0[1]) + du[2] * c0[2];
+  if (det == 0.0 || !std::isfinite(det)) return false;
+  for (int c = 0; c < 3; ++c) {
+    R9[c] = static_cast<float>(c0[c] / det);
+    R9[3 + c] = static_cast<float>(c1[c] / det);
+    R9[6 + c] = static_cast<float>(c2[c] / det);
+    dc3[c] = cur.center[c] - prev.center[c];
+  }
+  return true;
+}
+
+inline TpFrame tp_frame(const rt_temporal_opts& o, const rt_camera& cam, int width, int rows, int row0) {
+  TpFrame f{};
+  for (int c = 0; c < 3; ++c) {
+    f.center[c] = cam.center[c];
+    f.p00[c] = cam.p00[c];
+    f.du[c] = cam.du[c];
+    f.dv[c] = cam.dv[c];
+  }
+  f.width = width;
+  f.rows = rows;
+  f.row0 = row0;
+  f.have_prev = 0;
+  f.max_history = static_cast<float>(o.max_history);
+  f.sigma_z = o.sigma_z;
+  f.normal_min = o.normal_min;
+  return f;
+}
+
+RT_DN_FN float tp_floor(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return floorf(x);
+#else
+  return std::floor(x);
+#endif
+}
+RT_DN_FN bool tp_finite(float x) { return dn_abs(x) < INFINITY; }
+
+// One axis of step 4: the tap's first index and its fraction, snapped.  f is
+// inside (-1, size) here, so the conversion is in range.
+RT_DN_FN void tp_split(float f, int* i0, float* t) {
+  const float fl = tp_floor(f);
+  int i = static_cast<int>(fl);
+  float tt = f - fl;
+  if (tt < 0x1p-6f) {
+    tt = 0.0f;
+  } else if (tt > 1.0f - 0x1p-6f) {
+    i += 1;
+    tt = 0.0f;
+  }
+  *i0 = i;
+  *t = tt;
+}
+
+// One pixel (x, y) of a step: o0, o1 (3 floats each) and the returned length
+// N from the current halves h0, h1 (3 floats each), the current features feat
+// (8 floats) and the history.  Src:
+//   TpWord w0(size_t i)   (a0 rgb, L) of history pixel i = y * width + x
+//   TpWord w1(size_t i)   (a1 rgb, -)
+//   DnGuide guide(size_t i)
+// read for pixels inside the image only, and only with f.have_prev.
+template <class Src>
+RT_DN_FN float tp_pixel(const Src& src, const TpFrame& f, int x, int y, const float* h0, const float* h1,
+                        const float* feat, float* o0, float* o1) {
+  bool hist = f.have_prev != 0;
+  float fx = 0.0f, fy = 0.0f, zexp = INFINITY;
+  if (hist) {
+    // 1. the pixel centre's pinhole ray
+    const float xf = static_cast<float>(x), jf = static_cast<float>(f.row0 + y);
+    float e[3], w[3];
+    for (int c = 0; c < 3; ++c) e[c] = ((f.p00[c] + xf * f.du[c]) + jf * f.dv[c]) - f.center[c];
+    // 2. the surface point relative to the previous camera's centre
+    const float zp = feat[6];
+    if (tp_finite(zp)) {
+      const float len = dn_sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+      const float sc = zp / len;
+      for (int c = 0; c < 3; ++c) w[c] = sc * e[c] + f.dc[c];
+      zexp = dn_sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+    } else {
+      for (int c = 0; c < 3; ++c) w[c] = e[c];
+    }
+    // 3. where the previous camera saw it (NaN fails every comparison)
+    const float al = (f.R[0] * w[0] + f.R[1] * w[1]) + f.R[2] * w[2];
+    const float be = (f.R[3] * w[0] + f.R[4] * w[1]) + f.R[5] * w[2];
+    const float ga = (f.R[6] * w[0] + f.R[7] * w[1]) + f.R[8] * w[2];
+    hist = ga > 0.0f;
+    if (hist) {
+      fx = al / ga;
+      fy = be / ga - static_cast<float>(f.row0);
+      hist = fx > -1.0f && fx < static_cast<float>(f.width) && fy > -1.0f && fy < static_cast<float>(f.rows);
+    }
+  }
+  float acc0[3] = {0.0f, 0.0f, 0.0f}, acc1[3] = {0.0f, 0.0f, 0.0f}, accl = 0.0f, bsum = 0.0f;
+  if (hist) {
+    // 4. the 2 x 2 taps' corner and fractions
+    int x0, y0;
+    float tx, ty;
+    tp_split(fx, &x0, &tx);
+    tp_split(fy, &y0, &ty);
+    const float tol = f.sigma_z * zexp;
+    const bool pinf = zexp == INFINITY, pfin = tp_finite(zexp);
+    // 5. the valid taps
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int dy = 0; dy <= 1; ++dy) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+      for (int dx = 0; dx <= 1; ++dx) {
+        const float b = (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty);
+        const int qx = x0 + dx, qy = y0 + dy;
+        if (b == 0.0f || qx < 0 || qx >= f.width || qy < 0 || qy >= f.rows) continue;
+        const size_t q = static_cast<size_t>(qy) * f.width + qx;
+        const TpWord a = src.w0(q);
+        if (!(a.l >= 1.0f)) continue;
+        const DnGuide g = src.guide(q);
+        if (!(pinf && g.z == INFINITY)) {
+          if (!(pfin && tp_finite(g.z))) continue;
+          if (!(dn_abs(g.z - zexp) <= tol)) continue;
+          const float dot = (feat[3] * g.nx + feat[4] * g.ny) + feat[5] * g.nz;
+          if (!(dot >= f.normal_min)) continue;
+        }
+        const TpWord a1 = src.w1(q);
+        acc0[0] += b * a.r;
+        acc0[1] += b * a.g;
+        acc0[2] += b * a.b;
+        acc1[0] += b * a1.r;
+        acc1[1] += b * a1.g;
+        acc1[2] += b * a1.b;
+        accl += b * a.l;
+        bsum += b;
+      }
+    }
+  }
+  // 6. the blend
+  if (hist && bsum >= 0.25f) {
+    const float lh = accl / bsum;
+    const float n = dn_min(lh + 1.0f, f.max_history);
+    const float k = 1.0f / n;
+    for (int c = 0; c < 3; ++c) {
+      const float a = acc0[c] / bsum, b = acc1[c] / bsum;
+      o0[c] = a + k * (h0[c] - a);
+      o1[c] = b + k * (h1[c] - b);
+    }
+    return n;
+  }
+  for (int c = 0; c < 3; ++c) {
+    o0[c] = h0[c];
+    o1[c] = h1[c];
+  }
+  return 1.0f;
+}
+
+// The history as plain arrays (the host): a0, a1 rows x width x 3, guide
+// rows x width x 4, len rows x width.
+struct TpPlain {
+  const float *a0, *a1, *g, *len;
+  TpWord w0(size_t i) const { return TpWord{a0[3 * i], a0[3 * i + 1], a0[3 * i + 2], len[i]}; }
+  TpWord w1(size_t i) const { return TpWord{a1[3 * i], a1[3 * i + 1], a1[3 * i + 2], 0.0f}; }
+  DnGuide guide(size_t i) const { return DnGuide{g[4 * i], g[4 * i + 1], g[4 * i + 2], g[4 * i + 3]}; }
+};
+
+inline bool tp_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  if (!a || !b) return false;
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+
+// rt_temporal_host (rt.h): the checks, then every pixel.  0, or RT_E_ARG with
+// *why set.
+inline int tp_host_step(const rt_temporal_opts* o, const rt_camera* cam, const rt_camera* prev_cam, int width,
+                        int rows, int row0, const float* half0, const float* half1, const float* feat,
+                        const float* prev_a0, const float* prev_a1, const float* prev_guide, const float* prev_len,
+                        float* out0, float* out1, float* out_len, const char** why) {
+  *why = nullptr;
+  if (!cam || !half0 || !half1 || !feat || !out0 || !out1 || !out_len ||
+      (prev_cam && (!prev_a0 || !prev_a1 || !prev_guide || !prev_len))) {
+    *why = "NULL argument";
+    return RT_E_ARG;
+  }
+  if ((*why = tp_shape_error(width, rows, row0)) != nullptr) return RT_E_ARG;
+  const rt_temporal_opts opt = o ? *o : tp_default_opts();
+  if ((*why = tp_opts_error(opt)) != nullptr) return RT_E_ARG;
+  const size_t n_px = static_cast<size_t>(width) * rows, fb = sizeof(float);
+  const void* outs[3] = {out0, out1, out_len};
+  const size_t out_b[3] = {n_px * 3 * fb, n_px * 3 * fb, n_px * fb};
+  const void* ins[7] = {half0, half1, feat, prev_a0, prev_a1, prev_guide, prev_len};
+  const size_t in_b[7] = {n_px * 3 * fb, n_px * 3 * fb, n_px * RT_FEAT_CHANNELS * fb, n_px * 3 * fb,
+                          n_px * 3 * fb, n_px * 4 * fb, n_px * fb};
+  for (int a = 0; a < 3; ++a) {
+    for (int b = 0; b < 7; ++b)
+      if ((b < 3 || prev_cam) && tp_overlap(outs[a], out_b[a], ins[b], in_b[b])) {
+        *why = "an output overlaps an input";
+        return RT_E_ARG;
+      }
+    for (int b = a + 1; b < 3; ++b)
+      if (tp_overlap(outs[a], out_b[a], outs[b], out_b[b])) {
+        *why = "the outputs overlap";
+        return RT_E_ARG;
+      }
+  }
+  TpFrame f = tp_frame(opt, *cam, width, rows, row0);
+  if (prev_cam) {
+    if (!tp_setup(*cam, *prev_cam, f.R, f.dc)) {
+      *why = "the previous camera is degenerate (det is 0 or not finite)";
+      return RT_E_ARG;
+    }
+    f.have_prev = 1;
+  }
+  const TpPlain src{prev_a0, prev_a1, prev_guide, prev_len};
+  for (int y = 0; y < rows; ++y)
+    for (int x = 0; x < width; ++x) {
+      const size_t i = static_cast<size_t>(y) * width + x;
+      out_len[i] = tp_pixel(src, f, x, y, half0 + 3 * i, half1 + 3 * i, feat + RT_FEAT_CHANNELS * i, out0 + 3 * i,
+                            out1 + 3 * i);
+    }
+  return RT_OK;
+}
+
+#if defined(__HIPCC__) && defined(RT_TEMPORAL_KERNEL)
+// -------------------------------------------------------------- the kernel ----
+// The history as the device keeps it: three 16-byte words a pixel.
+struct TpPacked {
+  const TpWord* a0;
+  const TpWord* a1;
+  const DnGuide* g;
+  __device__ __forceinline__ TpWord w0(size_t i) const { return a0[i]; }
+  __device__ __forceinline__ TpWord w1(size_t i) const { return a1[i]; }
+  __device__ __forceinline__ DnGuide guide(size_t i) const { return g[i]; }
+};
+
+// A workgroup is kDnBx x kDnBy pixels, a wave one row of 64; thread (x, y)
+// owns pixel (x, y).  The current inputs are read as single floats (they need
+// no more than a float's alignment); the history is gathered as 16-byte words
+// straight from global memory -- where a tap lies depends on the data, so no
+// LDS tile; the taps of neighbouring pixels are neighbours under any smooth
+// motion and meet in the vector L1 and the L2 -- and the three new history
+// words and both outputs are written by the owning thread.  The old and the
+// new history are different buffers (rt_temporal's two sets).
+__global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_kernel(
+    const TpFrame f, const float* __restrict__ half0, const float* __restrict__ half1, const float* __restrict__ feat,
+    const TpWord* __restrict__ prev_a0, const TpWord* __restrict__ prev_a1, const DnGuide* __restrict__ prev_g,
+    TpWord* __restrict__ new_a0, TpWord* __restrict__ new_a1, DnGuide* __restrict__ new_g, float* __restrict__ out0,
+    float* __restrict__ out1) {
+  const int x = static_cast<int>(blockIdx.x) * kDnBx + static_cast<int>(threadIdx.x);
+  const int y = static_cast<int>(blockIdx.y) * kDnBy + static_cast<int>(threadIdx.y);
+  if (x >= f.width || y >= f.rows) return;
+  const size_t i = static_cast<size_t>(y) * f.width + x;
+  float h0[3], h1[3], ft[RT_FEAT_CHANNELS], o0[3], o1[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    h0[c] = half0[i * 3 + c];
+    h1[c] = half1[i * 3 + c];
+  }
+#pragma unroll
+  for (int c = 0; c < RT_FEAT_CHANNELS; ++c) ft[c] = feat[i * RT_FEAT_CHANNELS + c];
+  const TpPacked src{prev_a0, prev_a1, prev_g};
+  const float n = tp_pixel(src, f, x, y, h0, h1, ft, o0, o1);
+  new_a0[i] = TpWord{o0[0], o0[1], o0[2], n};
+  new_a1[i] = TpWord{o1[0], o1[1], o1[2], 0.0f};
+  new_g[i] = DnGuide{ft[3], ft[4], ft[5], ft[6]};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    out0[i * 3 + c] = o0[c];
+    out1[i * 3 + c] = o1[c];
+  }
+}
+#endif  // __HIPCC__ && RT_TEMPORAL_KERNEL
+
+}  // namespace rtclj

@@ -10,12 +10,15 @@
 // here too.  Which variant a launch runs and the LDS it needs
 // is variant_policy.h's (pure functions, checked on the CPU); the device
 // buffers the host side owns are dev_buf.h's DevBuf.  The denoiser's kernels
-// (denoise.h) and the rt_denoiser entries close the file.
+// (denoise.h) and the rt_denoiser entries, then temporal accumulation's kernel
+// (temporal.h) and the rt_temporal entries close the file.
 #include "trace_kernel.h"
 #define RT_FIRST_HIT_KERNEL
 #include "first_hit.h"
 #define RT_DENOISE_KERNEL
 #include "denoise.h"
+#define RT_TEMPORAL_KERNEL
+#include "temporal.h"
 #include "variant_policy.h"
 #include "dev_buf.h"
 
@@ -2193,6 +2196,172 @@ extern "C" int rt_denoise_profile(rt_denoiser* dn, const rt_denoise_opts* o, con
   for (hipEvent_t v : ev)
     if (v) (void)hipEventDestroy(v);
   return rc;
+}
+
+// ---- temporal accumulation (rt.h, temporal.h) --------------------------------
+// The history on the device: two sets of three packed arrays -- a step gathers
+// from set `cur` and writes set cur ^ 1 -- and, on the host, the camera that
+// wrote set `cur`.  mu orders the calls' enqueues (the sets themselves are
+// ordered by the caller's stream).
+struct rt_temporal {
+  int device = 0, width = 0, rows = 0, row0 = 0;
+  size_t n_px = 0;
+  mutable std::mutex mu;
+  DevBuf<TpWord> a0[2], a1[2];
+  DevBuf<DnGuide> guide[2];
+  int cur = 0;
+  bool have_prev = false;
+  rt_camera prev{};
+  int64_t frames = 0;
+};
+
+extern "C" int rt_temporal_create(int device, int width, int rows, int row0, rt_temporal** out) {
+  clear_error();
+  if (!out) return set_error(RT_E_ARG, "rt_temporal_create: NULL argument");
+  *out = nullptr;
+  if (const char* why = tp_shape_error(width, rows, row0))
+    return set_error(RT_E_ARG, std::string("rt_temporal_create: ") + why);
+  // (the kernel's grid has a block row per kDnBy image rows)
+  if ((rows + kDnBy - 1) / kDnBy > 65535) return set_error(RT_E_ARG, "rt_temporal_create: bad width/rows");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return set_error(RT_E_NODEV, "rt_temporal_create: device " + std::to_string(device) + " not available");
+  HIP_TRY(hipSetDevice(device));
+  rt_temporal* t = new rt_temporal;
+  t->device = device;
+  t->width = width;
+  t->rows = rows;
+  t->row0 = row0;
+  t->n_px = static_cast<size_t>(width) * rows;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+    e = t->a0[k].alloc(t->n_px);
+    if (e == hipSuccess) e = t->a1[k].alloc(t->n_px);
+    if (e == hipSuccess) e = t->guide[k].alloc(t->n_px);
+  }
+  // the set a first rt_temporal_read shows: L = 0 everywhere
+  if (e == hipSuccess) e = fill_zero(t->a0[0], t->n_px, nullptr);
+  if (e == hipSuccess) e = fill_zero(t->a1[0], t->n_px, nullptr);
+  if (e == hipSuccess) e = fill_zero(t->guide[0], t->n_px, nullptr);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess) {
+    delete t;
+    return hip_fail(e, "rt_temporal_create");
+  }
+  *out = t;
+  return RT_OK;
+}
+
+extern "C" int rt_temporal_free(rt_temporal* t) {
+  if (!t) return RT_OK;
+  (void)hipSetDevice(t->device);
+  delete t;
+  return RT_OK;
+}
+
+// nullptr's device, or whether `stream` belongs to t's device
+static int tp_stream_check(const std::string& me, const rt_temporal* t, hipStream_t stream) {
+  if (stream) {
+    hipDevice_t sdev = 0;
+    if (hipStreamGetDevice(stream, &sdev) == hipSuccess && static_cast<int>(sdev) != t->device)
+      return set_error(RT_E_ARG, me + ": the stream is on device " + std::to_string(static_cast<int>(sdev)) +
+                                     ", the history on device " + std::to_string(t->device));
+  }
+  return RT_OK;
+}
+
+extern "C" int rt_temporal_reset(rt_temporal* t, void* hip_stream) {
+  clear_error();
+  if (!t) return set_error(RT_E_ARG, "rt_temporal_reset: NULL argument");
+  std::lock_guard<std::mutex> lk(t->mu);
+  HIP_TRY(hipSetDevice(t->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (const int rc = tp_stream_check("rt_temporal_reset", t, stream)) return rc;
+  HIP_TRY(fill_zero(t->a0[t->cur], t->n_px, stream));
+  HIP_TRY(fill_zero(t->a1[t->cur], t->n_px, stream));
+  HIP_TRY(fill_zero(t->guide[t->cur], t->n_px, stream));
+  t->have_prev = false;
+  t->frames = 0;
+  return RT_OK;
+}
+
+extern "C" int64_t rt_temporal_frames(const rt_temporal* t) {
+  if (!t) return -1;
+  std::lock_guard<std::mutex> lk(t->mu);
+  return t->frames;
+}
+
+extern "C" int rt_temporal_step(rt_temporal* t, const rt_temporal_opts* o, const rt_camera* cam, const float* d_half0,
+                                const float* d_half1, const float* d_feat, float* d_out0, float* d_out1,
+                                void* hip_stream) {
+  clear_error();
+  const std::string me("rt_temporal_step");
+  if (!t || !cam || !d_half0 || !d_half1 || !d_feat || !d_out0 || !d_out1)
+    return set_error(RT_E_ARG, me + ": NULL argument");
+  const rt_temporal_opts opt = o ? *o : tp_default_opts();
+  if (const char* why = tp_opts_error(opt)) return set_error(RT_E_ARG, me + ": " + why);
+  const size_t cb = t->n_px * 3 * sizeof(float), fb = t->n_px * RT_FEAT_CHANNELS * sizeof(float);
+  for (const float* d_out : {d_out0, d_out1})
+    if (tp_overlap(d_out, cb, d_half0, cb) || tp_overlap(d_out, cb, d_half1, cb) || tp_overlap(d_out, cb, d_feat, fb))
+      return set_error(RT_E_ARG, me + ": an output overlaps an input");
+  if (tp_overlap(d_out0, cb, d_out1, cb)) return set_error(RT_E_ARG, me + ": the outputs overlap");
+  std::lock_guard<std::mutex> lk(t->mu);
+  TpFrame f = tp_frame(opt, *cam, t->width, t->rows, t->row0);
+  if (t->have_prev) {
+    if (!tp_setup(*cam, t->prev, f.R, f.dc))
+      return set_error(RT_E_ARG, me + ": the previous camera is degenerate (det is 0 or not finite)");
+    f.have_prev = 1;
+  }
+  HIP_TRY(hipSetDevice(t->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (const int rc = tp_stream_check(me, t, stream)) return rc;
+  const int src = t->cur, dst = t->cur ^ 1;
+  const dim3 grid(static_cast<unsigned>((t->width + kDnBx - 1) / kDnBx),
+                  static_cast<unsigned>((t->rows + kDnBy - 1) / kDnBy)),
+      block(kDnBx, kDnBy);
+  HIP_TRY(enqueue(temporal_step_kernel, grid, block, 0, stream, f, d_half0, d_half1, d_feat, t->a0[src].p,
+                  t->a1[src].p, t->guide[src].p, t->a0[dst].p, t->a1[dst].p, t->guide[dst].p, d_out0, d_out1));
+  t->cur = dst;
+  t->prev = *cam;
+  t->have_prev = true;
+  t->frames += 1;
+  return RT_OK;
+}
+
+extern "C" int rt_temporal_read(const rt_temporal* t, float* host_a0, float* host_a1, float* host_guide,
+                                float* host_len, void* hip_stream) {
+  clear_error();
+  if (!t) return set_error(RT_E_ARG, "rt_temporal_read: NULL argument");
+  std::lock_guard<std::mutex> lk(t->mu);
+  HIP_TRY(hipSetDevice(t->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (const int rc = tp_stream_check("rt_temporal_read", t, stream)) return rc;
+  std::vector<TpWord> w0, w1;
+  if (host_a0 || host_len) {
+    w0.resize(t->n_px);
+    HIP_TRY(hipMemcpyAsync(w0.data(), t->a0[t->cur].p, t->n_px * sizeof(TpWord), hipMemcpyDeviceToHost, stream));
+  }
+  if (host_a1) {
+    w1.resize(t->n_px);
+    HIP_TRY(hipMemcpyAsync(w1.data(), t->a1[t->cur].p, t->n_px * sizeof(TpWord), hipMemcpyDeviceToHost, stream));
+  }
+  if (host_guide)
+    HIP_TRY(hipMemcpyAsync(host_guide, t->guide[t->cur].p, t->n_px * sizeof(DnGuide), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  for (size_t i = 0; i < t->n_px; ++i) {
+    if (host_a0) {
+      host_a0[3 * i] = w0[i].r;
+      host_a0[3 * i + 1] = w0[i].g;
+      host_a0[3 * i + 2] = w0[i].b;
+    }
+    if (host_len) host_len[i] = w0[i].l;
+    if (host_a1) {
+      host_a1[3 * i] = w1[i].r;
+      host_a1[3 * i + 1] = w1[i].g;
+      host_a1[3 * i + 2] = w1[i].b;
+    }
+  }
+  return RT_OK;
 }
 
 // A device's start-up ahead of the first render (rt.h): the context, the

@@ -82,6 +82,14 @@ class rt_denoise_opts(C.Structure):
 DENOISE_DEFAULTS = dict(levels=5, normal_pow2=5, sigma_c=4.0, sigma_z=0.05)
 
 
+class rt_temporal_opts(C.Structure):
+    _fields_ = [("max_history", C.c_int), ("sigma_z", C.c_float), ("normal_min", C.c_float)]
+
+
+# rt_temporal_step's defaults (include/rt.h)
+TEMPORAL_DEFAULTS = dict(max_history=32, sigma_z=0.1, normal_min=0.9)
+
+
 # symbol -> (restype, argtypes); every function include/rt.h declares
 SIGNATURES = {
     "rt_camera_setup": (C.c_int, [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -158,6 +166,16 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
     "rt_denoise_host": (C.c_int, [C.POINTER(rt_denoise_opts), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                   C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "rt_temporal_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "rt_temporal_free": (C.c_int, [C.c_void_p]),
+    "rt_temporal_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_temporal_frames": (C.c_int64, [C.c_void_p]),
+    "rt_temporal_step": (C.c_int, [C.c_void_p, C.POINTER(rt_temporal_opts), C.POINTER(rt_camera), C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_temporal_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                   C.POINTER(C.c_float), C.c_void_p]),
+    "rt_temporal_host": (C.c_int, [C.POINTER(rt_temporal_opts), C.POINTER(rt_camera), C.POINTER(rt_camera), C.c_int,
+                                   C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 10),
     "rt_quantize_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rt_set_variant": (C.c_int, [C.c_int]),
     "rt_resolve_variant": (C.c_int, [C.c_void_p]),
@@ -184,7 +202,8 @@ ADDITIVE = {"rt_prepare", "rt_render_u8", "rt_quantize_device", "rt_render_submi
             "rt_feat_clear", "rt_feat_samples", "rt_launch_feat", "rt_feat_resolve", "rt_feat_read",
             "rt_feat_add", "rt_feat_resolve_host", "rt_feat_occupancy", "rt_adapt_resolve_half",
             "rt_denoiser_create", "rt_denoiser_free", "rt_denoise", "rt_denoise_profile",
-            "rt_denoise_host"}
+            "rt_denoise_host", "rt_temporal_create", "rt_temporal_free", "rt_temporal_reset", "rt_temporal_frames",
+            "rt_temporal_step", "rt_temporal_read", "rt_temporal_host"}
 
 RT_FEAT_CHANNELS = 8   # rt_feat_resolve's floats per pixel: albedo rgb, normal xyz, depth, coverage
 

@@ -24,9 +24,9 @@ from fractions import Fraction
 import numpy as np
 
 from . import hittable, material
-from ._lib import (DENOISE_DEFAULTS, RT_DIELECTRIC, RT_FEAT_CHANNELS, RT_LAMBERTIAN, RT_METAL, RT_NONE, RTError, check,
-                   dptr, fptr, i64ptr, iptr, lib, rt_adapt_opts, rt_camera, rt_denoise_opts, rt_params, rt_scene,
-                   rt_stats, u8ptr, u32ptr, u64ptr)
+from ._lib import (DENOISE_DEFAULTS, RT_DIELECTRIC, RT_FEAT_CHANNELS, RT_LAMBERTIAN, RT_METAL, RT_NONE,
+                   TEMPORAL_DEFAULTS, RTError, check, dptr, fptr, i64ptr, iptr, lib, rt_adapt_opts, rt_camera,
+                   rt_denoise_opts, rt_params, rt_scene, rt_stats, rt_temporal_opts, u8ptr, u32ptr, u64ptr)
 
 # ---- scene (raytracing.clj:63-78) --------------------------------------------
 hittables = [
@@ -232,6 +232,13 @@ class Progressive:
         first sample index again."""
         self._check(self._dll.rt_accum_clear(self._acc, self._stream))
         self._next = self._first
+
+    def restart(self, cam: rt_camera, sample_begin: int) -> None:
+        """Another frame in the same accumulator (a sequence's next frame):
+        clear(), then the passes are `cam`'s, from sample index `sample_begin`."""
+        self.cam = cam
+        self._first = int(sample_begin)
+        self.clear()
 
     def close(self) -> None:
         if getattr(self, "_acc", None):
@@ -480,6 +487,13 @@ class Features:
         self._check(self._dll.rt_feat_clear(self._ft, self._stream))
         self._next = self._first
 
+    def restart(self, cam: rt_camera, sample_begin: int) -> None:
+        """Another frame in the same buffers (a sequence's next frame):
+        clear(), then the passes are `cam`'s, from sample index `sample_begin`."""
+        self.cam = cam
+        self._first = int(sample_begin)
+        self.clear()
+
     def close(self) -> None:
         if getattr(self, "_ft", None):
             self._dll.rt_feat_free(self._ft)
@@ -615,6 +629,187 @@ def render_denoised(scene, cam: rt_camera, width: int, height: int, spp: int = 8
         feat = d_feat.cpu().numpy().reshape(height, width, RT_FEAT_CHANNELS)
         out = d_out.cpu().numpy().reshape(height, width, 3)
     return out, np.float32(0.5) * (h0 + h1), feat
+
+
+def _temporal_opts(opts: dict) -> rt_temporal_opts:
+    unknown = set(opts) - set(TEMPORAL_DEFAULTS)
+    if unknown:
+        raise TypeError(f"temporal: unknown option(s) {sorted(unknown)}")
+    o = {**TEMPORAL_DEFAULTS, **opts}
+    return rt_temporal_opts(max_history=int(o["max_history"]), sigma_z=float(o["sigma_z"]),
+                            normal_min=float(o["normal_min"]))
+
+
+def temporal_host(cam: rt_camera, prev_cam, half0, half1, feat, prev=None, row0: int = 0, library=None, **opts):
+    """rt_temporal_host (include/rt.h): one step of temporal accumulation on the
+    host, in plain C++ -- the bits Temporal.step gives on the device.  half0,
+    half1: float32 (rows, width, 3); feat: float32 (rows, width, 8); cam: the
+    camera that drew them.  prev_cam and prev = (a0, a1, guide, length) are
+    the previous camera and the history as Temporal.read() gives it -- (rows,
+    width, 3) twice, (rows, width, 4), (rows, width) -- or both None: no
+    history.  Options: max_history, sigma_z, normal_min.  Returns (out0, out1,
+    length): the new history's halves and its length; its guides are
+    feat[..., 3:7]."""
+    dll = library if library is not None else lib
+    half0 = np.ascontiguousarray(half0, np.float32)
+    half1 = np.ascontiguousarray(half1, np.float32)
+    feat = np.ascontiguousarray(feat, np.float32)
+    if half0.ndim != 3 or half0.shape[2] != 3 or half1.shape != half0.shape or \
+            feat.shape != half0.shape[:2] + (RT_FEAT_CHANNELS,):
+        raise ValueError("temporal_host: half0, half1 must be (rows, width, 3) and feat (rows, width, 8)")
+    rows, width = half0.shape[:2]
+    if (prev_cam is None) != (prev is None):
+        raise ValueError("temporal_host: prev_cam and prev come together")
+    hist = [None] * 4
+    if prev is not None:
+        hist = [np.ascontiguousarray(a, np.float32) for a in prev]
+        if [a.shape for a in hist] != [(rows, width, 3), (rows, width, 3), (rows, width, 4), (rows, width)]:
+            raise ValueError("temporal_host: prev must be (a0, a1, guide, length) of the frame's size")
+    out0, out1 = np.empty(half0.shape, np.float32), np.empty(half0.shape, np.float32)
+    length = np.empty((rows, width), np.float32)
+    o = _temporal_opts(opts)
+    code = dll.rt_temporal_host(C.byref(o), C.byref(cam), C.byref(prev_cam) if prev_cam is not None else None, width,
+                                rows, int(row0), fptr(half0), fptr(half1), fptr(feat),
+                                *(fptr(a) if a is not None else None for a in hist), fptr(out0), fptr(out1),
+                                fptr(length))
+    if code < 0:
+        raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+    return out0, out1, length
+
+
+class Temporal:
+    """Temporal accumulation on device `device` for images of rows x width
+    whose first row is camera row row0 (rt_temporal, include/rt.h): it owns the
+    history -- the accumulated halves, the guides and the length per pixel --
+    and the previous camera.
+
+        with Temporal(400, 225) as tp:
+            for cam in cameras:
+                ...                                          # the resolves
+                tp.step(cam, d_half0, d_half1, d_feat, d_out0, d_out1)
+                dn.run(d_out0, d_out1, d_feat, d_out)
+
+    step() is asynchronous, on `stream` (a HIP stream handle, int; default the
+    NULL stream); steps of one object go on one stream.  The sample indices of
+    successive frames must differ."""
+
+    def __init__(self, width: int, rows: int, row0: int = 0, device: int = 0, library=None):
+        self._dll = library if library is not None else lib
+        self.width, self.rows, self.row0 = int(width), int(rows), int(row0)
+        self._tp = C.c_void_p()
+        self._check(self._dll.rt_temporal_create(int(device), self.width, self.rows, self.row0, C.byref(self._tp)))
+        self.shape = (self.rows, self.width, 3)
+
+    def _check(self, code):
+        if code < 0:
+            raise RTError(code, self._dll.rt_last_error().decode(errors="replace"))
+        return code
+
+    @property
+    def frames(self) -> int:
+        """Steps since the last reset (rt_temporal_frames)."""
+        return int(self._dll.rt_temporal_frames(self._tp))
+
+    def step(self, cam: rt_camera, d_half0: int, d_half1: int, d_feat: int, d_out0: int, d_out1: int, stream=None,
+             **opts) -> None:
+        """Enqueue one step (rt_temporal_step) on device addresses; options as
+        temporal_host."""
+        o = _temporal_opts(opts)
+        self._check(self._dll.rt_temporal_step(self._tp, C.byref(o), C.byref(cam), C.c_void_p(d_half0),
+                                               C.c_void_p(d_half1), C.c_void_p(d_feat), C.c_void_p(d_out0),
+                                               C.c_void_p(d_out1), C.c_void_p(stream) if stream else None))
+
+    def read(self, stream=None):
+        """(a0, a1, guide, length): the current history copied out behind the
+        stream's work (rt_temporal_read), as temporal_host's `prev`."""
+        a0, a1 = np.empty(self.shape, np.float32), np.empty(self.shape, np.float32)
+        guide = np.empty((self.rows, self.width, 4), np.float32)
+        length = np.empty((self.rows, self.width), np.float32)
+        self._check(self._dll.rt_temporal_read(self._tp, fptr(a0), fptr(a1), fptr(guide), fptr(length),
+                                               C.c_void_p(stream) if stream else None))
+        return a0, a1, guide, length
+
+    def reset(self, stream=None) -> None:
+        """Forget the history and the previous camera (rt_temporal_reset)."""
+        self._check(self._dll.rt_temporal_reset(self._tp, C.c_void_p(stream) if stream else None))
+
+    def close(self) -> None:
+        if getattr(self, "_tp", None):
+            self._dll.rt_temporal_free(self._tp)
+            self._tp = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def render_sequence(scene, cameras, width: int, height: int, spp: int = 4, max_depth: int = 50, seed: int = 1,
+                    flags: int = 0, library=None, temporal=None, stages: bool = False, **opts):
+    """A sequence of low-sample frames of a static scene, one per camera of
+    `cameras`, each temporally accumulated and then denoised, on device 0: a
+    generator that yields float32 (height, width, 3) per camera.  Per frame f:
+    two accumulators of spp / 2 samples each (sample indices f * spp ... so
+    that no frame repeats another's samples), the first-hit features of all
+    spp, everything resolved on the device, Temporal.step, Denoiser.run on the
+    accumulated halves.  `spp` must be even.  `temporal`: options of the step
+    (max_history, sigma_z, normal_min); further keywords: the denoiser's.  With
+    `stages` it yields (denoised, half0, half1, feat, acc0, acc1) instead: the
+    resolves and the step's outputs beside the frame.  The device buffers are
+    torch's (import torch before rtclj, as render_denoised)."""
+    if spp <= 0 or spp % 2:
+        raise ValueError("render_sequence: spp must be even and positive")
+    _denoise_opts(opts)
+    topts = dict(temporal or {})
+    _temporal_opts(topts)
+    import torch
+    if not torch.cuda.is_available():
+        raise RTError(-5, "render_sequence: torch sees no GPU (import torch before rtclj)")
+    half = spp // 2
+    sc = scene if isinstance(scene, Scene) else Scene.from_bodies(scene)
+    dev = torch.device("cuda", 0)
+    n_px = width * height
+    d_h = [torch.empty(n_px * 3, dtype=torch.float32, device=dev) for _ in range(2)]
+    d_acc = [torch.empty(n_px * 3, dtype=torch.float32, device=dev) for _ in range(2)]
+    d_feat = torch.empty(n_px * RT_FEAT_CHANNELS, dtype=torch.float32, device=dev)
+    d_out = torch.empty(n_px * 3, dtype=torch.float32, device=dev)
+    torch.cuda.synchronize(dev)   # (the passes below run on the NULL stream)
+    cameras = iter(cameras)
+    try:
+        cam = next(cameras)
+    except StopIteration:
+        return
+    with Progressive(sc, cam, width, height, max_depth, seed, flags=flags, library=library) as a0, \
+            Progressive(sc, cam, width, height, max_depth, seed, flags=flags, library=library) as a1, \
+            Features(sc, cam, width, height, seed=seed, flags=flags, library=library) as ft, \
+            Temporal(width, height, library=library) as tp, Denoiser(width, height, library=library) as dn:
+        f = 0
+        while cam is not None:
+            for acc, begin in ((a0, f * spp), (a1, f * spp + half), (ft, f * spp)):
+                acc.restart(cam, begin)
+            a0.add(half)
+            a1.add(half)
+            ft.add(spp)
+            a0.resolve_into(d_h[0].data_ptr())
+            a1.resolve_into(d_h[1].data_ptr())
+            ft.resolve_into(d_feat.data_ptr())
+            tp.step(cam, d_h[0].data_ptr(), d_h[1].data_ptr(), d_feat.data_ptr(), d_acc[0].data_ptr(),
+                    d_acc[1].data_ptr(), **topts)
+            dn.run(d_acc[0].data_ptr(), d_acc[1].data_ptr(), d_feat.data_ptr(), d_out.data_ptr(), **opts)
+            torch.cuda.synchronize(dev)
+            out = d_out.cpu().numpy().reshape(height, width, 3)
+            if stages:
+                yield (out,) + tuple(d.cpu().numpy().reshape(height, width, 3) for d in d_h) + \
+                    (d_feat.cpu().numpy().reshape(height, width, RT_FEAT_CHANNELS),) + \
+                    tuple(d.cpu().numpy().reshape(height, width, 3) for d in d_acc)
+            else:
+                yield out
+            cam = next(cameras, None)
+            f += 1
 
 
 def pass_sizes(spp: int, passes: int):
@@ -792,4 +987,4 @@ if __name__ == "__main__":  # python -m rtclj.raytracing [spp] [depth]
 
 
 __all__ = ["hittables", "REFERENCE_CAMERA", "image_height", "flatten", "flatten64", "Scene", "camera", "render", "Progressive", "Adaptive", "pass_sizes",
-           "Features", "denoise_host", "Denoiser", "render_denoised", "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]
+           "Features", "denoise_host", "Denoiser", "render_denoised", "temporal_host", "Temporal", "render_sequence", "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]
