@@ -593,6 +593,66 @@ int rt_feat_resolve_host(const int64_t* sums, const uint32_t* hits, const float*
  * in LDS, 1 = BVH in global memory, 2 = linear scan}. */
 int rt_feat_occupancy(const rt_dscene* ds, int* out4);
 
+/* ---- body ids: which body a pixel shows -----------------------------------------
+ * The index hit-anything's reduce (raytracing.clj:33-43) ends on, per pixel,
+ * for the pixel centre's pinhole ray: an object-id buffer (picking, masks), and
+ * what rt_temporal_step_motion needs to know whose displacement to subtract.
+ * The device kernel and rt_ids_host give the same integers.
+ *
+ * Image: rows x width int32, contiguous; image row y is camera row row0 + y (a
+ * contiguous row band, as rt_temporal_create's).
+ * Per pixel (x, y), j = row0 + y:
+ *   1. The ray is the one rt_temporal_step's step 1 uses: origin = center,
+ *      direction e_c = ((p00_c + float(x) * du_c) + float(j) * dv_c) - center_c,
+ *      each operation one fp32 operation rounded once (no fma); no jitter, no
+ *      defocus, no random number.
+ *   2. The closest hit of (center, e) over the bodies as rt_launch_feat finds
+ *      it: |e| and 1 / |e| correctly rounded, u = e * (1 / |e|), t-min = 1e-3 in
+ *      |e| units; per body (centre c, radius r), with oc = c - center, in fp32
+ *      with the fma written out: h = fma(u_z, oc_z, fma(u_y, oc_y, u_x * oc_x)),
+ *      cc = fma(oc_x, oc_x, fma(oc_z, oc_z, fma(oc_y, oc_y, -(r * r)))),
+ *      disc = fma(h, h, -cc); no root unless min(disc, max(h, -cc)) >= 0; the
+ *      root t = h - sqrt(disc) if that is > t-min, else h + sqrt(disc); accepted
+ *      iff t > t-min and (t, index) is lexicographically below the best so far
+ *      (ties go to the lower index; no self-hit guard: a camera ray leaves no
+ *      body).  A body whose radius is NaN or infinite, or whose r * r overflows,
+ *      is never hit.
+ *   3. ids[y * width + x] = the body's index in the scene's array order, or -1
+ *      where nothing is hit.
+ * The device reads the tree rt_scene_upload made (or scans, as rt_launch_feat
+ * does under rt_set_variant: 5 the scan, 12 the tree in global memory,
+ * otherwise the tree in LDS where it fits -- the faster of the two trees even
+ * at one ray a thread); the walk gives the scan's answer bit
+ * for bit.
+ *
+ * To know: the id is the pinhole centre's body, while rt_feat's depth is the
+ * nearest hit over jittered, defocused rays -- on a silhouette pixel the two
+ * can belong to different bodies. */
+/* raytracing.clj:33-43's index, on the device.  Asynchronous, on hip_stream
+ * (NULL: the default stream) of ds's device: d_ids (device, rows x width
+ * int32) is written, every element.  RT_E_ARG on a NULL argument, width or
+ * rows <= 0, more than 2^31 - 1 pixels, a negative row0, or a stream of another
+ * device -- before anything is enqueued. */
+int rt_launch_ids(const rt_dscene* ds, const rt_camera* c, int width, int rows, int row0, int32_t* d_ids,
+                  void* hip_stream);
+/* The same on the host, in plain C++ (no device; raytracing.clj:33-43's scan in
+ * array order, over the (centre, -r^2) table rt_scene_upload builds): the
+ * yardstick of the kernel, and ids for frames that are on the host. */
+int rt_ids_host(const rt_scene* s, const rt_camera* c, int width, int rows, int row0, int32_t* out);
+/* The body-id kernel a launch on ds would run under the current selector
+ * (diagnostic; raytracing.clj:33-43's scan as it is run): out4 as
+ * rt_feat_occupancy's. */
+int rt_ids_occupancy(const rt_dscene* ds, int* out4);
+/* How far each body of raytracing.clj:63-78's scene moved between two frames:
+ * out (n x 4 floats) = per body b, out[4 b + c] = cur.center_c - prev.center_c
+ * (one fp32 subtraction per component, c = 0, 1, 2) and out[4 b + 3] = 0.  A
+ * body whose radius, material kind or any of its four material floats differs
+ * by bits between the scenes has no past: its three components are NaN (which
+ * rt_temporal_step_motion turns into "no history").  RT_E_ARG on a NULL
+ * argument or when the body counts differ.  Only rigid translation is
+ * described; a sphere's rotation is invisible with one albedo per body. */
+int rt_body_motion(const rt_scene* cur, const rt_scene* prev, float* out);
+
 /* ---- feature-guided denoiser: an a-trous filter over rt_feat's guides --------
  * What a low-sample frame of compute-pixel's loop (raytracing.clj:141-155)
  * looks like after an edge-avoiding a-trous wavelet filter (Dammertz et al.
@@ -765,7 +825,10 @@ int rt_denoise_host(const rt_denoise_opts* o, const float* half0, const float* h
  * defocused rays, used as if through the pinhole pixel centre -- that error is
  * what sigma_z absorbs; colour is accumulated modulated, so texture is
  * bilinearly resampled under motion (the scenes here have one albedo per
- * body); moving bodies are not handled (a scene is static between frames);
+ * body); rt_temporal_step takes the scene as static between frames -- a body
+ * that moved is reprojected as if it had stood still, and on a body of one
+ * albedo the depth and normal tests mostly let that pass: for moving bodies
+ * use rt_temporal_step_motion (below) with rt_launch_ids and rt_body_motion;
  * and the sample indices of successive frames must differ (the caller's
  * sample_begin or seed), or the history repeats one estimate.
  *
@@ -818,6 +881,48 @@ int rt_temporal_host(const rt_temporal_opts* o, const rt_camera* cam, const rt_c
                      int row0, const float* half0, const float* half1, const float* feat, const float* prev_a0,
                      const float* prev_a1, const float* prev_guide, const float* prev_len, float* out0, float* out1,
                      float* out_len);
+
+/* ---- moving bodies: the step with a per-body displacement -----------------------
+ * raytracing.clj:141-155's frames when raytracing.clj:63-78's bodies move
+ * between them.  The definition above changes in step 2 only.  Two more inputs:
+ * ids (rows x width int32, as rt_launch_ids writes them for the current scene
+ * and camera) and motion (n_bodies x 4 floats, as rt_body_motion(current scene,
+ * previous scene) writes them).
+ *   2'. For a finite z_p let b = ids[p]; m = motion[4 b .. 4 b + 2] if
+ *       0 <= b < n_bodies, else (0, 0, 0) -- the range test is on the integer,
+ *       before any load of the table.  Then w_c = (sc * e_c + dc_c) - m_c (one
+ *       more fp32 subtraction), zexp from that w.  A sky pixel (z_p not finite)
+ *       ignores ids.
+ * Steps 1 and 3-7 are unchanged.  x - (+0) is x for every x, so an all-zero
+ * table, ids of -1 or n_bodies = 0 give rt_temporal_step's bits.  Both entries
+ * work on the same rt_temporal and may alternate.
+ *
+ * To know: a NaN displacement (a body rt_body_motion found changed) fails
+ * gamma > 0, so the pixel has no history; only rigid translation is followed
+ * (rotation of a sphere of one albedo is invisible); shadows, reflections and
+ * what glass shows of a moving body lag, as they already do under camera
+ * motion, bounded by max_history; and the id is the pinhole centre's body
+ * while the depth is rt_feat's nearest hit over jittered rays, so on a
+ * silhouette pixel the two can belong to different bodies -- the depth and
+ * normal tests are what catch that.
+ *
+ * rt_temporal_step's arguments and errors, plus RT_E_ARG on a NULL d_ids,
+ * n_bodies < 0, a NULL d_motion with n_bodies > 0, a d_motion that is not
+ * 16-byte aligned (the kernel loads a row as one word), and an output
+ * overlapping d_ids or d_motion.  ids outside 0 .. n_bodies - 1, NaN or huge
+ * displacements give "no displacement" or "no history", never an out-of-range
+ * index.  A failed call leaves the history and the previous camera unchanged. */
+int rt_temporal_step_motion(rt_temporal* t, const rt_temporal_opts* o, const rt_camera* cam, const float* d_half0,
+                            const float* d_half1, const float* d_feat, const int32_t* d_ids, const float* d_motion,
+                            int n_bodies, float* d_out0, float* d_out1, void* hip_stream);
+/* The same step on the host, in plain C++ (no device; raytracing.clj:141-155):
+ * rt_temporal_host's arguments with ids, motion and n_bodies before the
+ * outputs (no alignment is asked of motion here). */
+int rt_temporal_host_motion(const rt_temporal_opts* o, const rt_camera* cam, const rt_camera* prev_cam, int width,
+                            int rows, int row0, const float* half0, const float* half1, const float* feat,
+                            const float* prev_a0, const float* prev_a1, const float* prev_guide, const float* prev_len,
+                            const int32_t* ids, const float* motion, int n_bodies, float* out0, float* out1,
+                            float* out_len);
 
 /* Asynchronous: enqueue rt_quantize on hip_stream's device for n channels
  * already in HBM (d_lin: n floats, d_out: n bytes, device pointers): the same

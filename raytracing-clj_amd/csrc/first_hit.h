@@ -106,6 +106,15 @@ RT_FH_FN void fh_test(const FhRay& r, float cx, float cy, float cz, float nr2, i
   b.body = acc ? s : b.body;
 }
 
+// A body's entry in the scan's table from its (cx, cy, cz, r): the centre and
+// -r^2, the square rounded once.  The one construction: rt_scene_upload's
+// table and rt_ids_host's are both made here.
+inline void fh_geo(const float* sphere4, float* geo4) {
+  const float r = sphere4[3];
+  geo4[0] = sphere4[0], geo4[1] = sphere4[1], geo4[2] = sphere4[2];
+  geo4[3] = -(r * r);
+}
+
 // the linear scan: geo = n x (cx, cy, cz, -r^2), in array order
 RT_FH_FN void fh_scan(const FhRay& r, const float* geo, int n, FhBest& b) {
   for (int s = 0; s < n; ++s) fh_test(r, geo[4 * s], geo[4 * s + 1], geo[4 * s + 2], geo[4 * s + 3], s, b);

@@ -30,6 +30,7 @@
 #include <thread>
 #include <vector>
 
+#include "body_ids.h"
 #include "denoise.h"
 #include "first_hit.h"
 #include "rt_internal.h"
@@ -311,6 +312,37 @@ extern "C" int rt_temporal_host(const rt_temporal_opts* o, const rt_camera* cam,
   const int rc = tp_host_step(o, cam, prev_cam, width, rows, row0, half0, half1, feat, prev_a0, prev_a1, prev_guide,
                               prev_len, out0, out1, out_len, &why);
   return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_temporal_host: ") + (why ? why : "failed"));
+}
+
+// rt_temporal_step_motion on the host (temporal.h's tp_host_step_motion: the
+// same text with step 2's displacement)
+extern "C" int rt_temporal_host_motion(const rt_temporal_opts* o, const rt_camera* cam, const rt_camera* prev_cam,
+                                       int width, int rows, int row0, const float* half0, const float* half1,
+                                       const float* feat, const float* prev_a0, const float* prev_a1,
+                                       const float* prev_guide, const float* prev_len, const int32_t* ids,
+                                       const float* motion, int n_bodies, float* out0, float* out1, float* out_len) {
+  clear_error();
+  const char* why = nullptr;
+  const int rc = tp_host_step_motion(o, cam, prev_cam, width, rows, row0, half0, half1, feat, prev_a0, prev_a1,
+                                     prev_guide, prev_len, ids, motion, n_bodies, out0, out1, out_len, &why);
+  return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_temporal_host_motion: ") + (why ? why : "failed"));
+}
+
+// rt_launch_ids on the host (body_ids.h's ids_host_pass: the pinhole ray, then
+// first_hit.h's scan over the table rt_scene_upload builds)
+extern "C" int rt_ids_host(const rt_scene* s, const rt_camera* c, int width, int rows, int row0, int32_t* out) {
+  clear_error();
+  const char* why = nullptr;
+  const int rc = ids_host_pass(s, c, width, rows, row0, out, &why);
+  return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_ids_host: ") + (why ? why : "failed"));
+}
+
+// the bodies' displacement between two scenes (body_ids.h's body_motion)
+extern "C" int rt_body_motion(const rt_scene* cur, const rt_scene* prev, float* out) {
+  clear_error();
+  const char* why = nullptr;
+  const int rc = body_motion(cur, prev, out, &why);
+  return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_body_motion: ") + (why ? why : "failed"));
 }
 
 extern "C" int rt_write_ppm(const char* path, const uint8_t* rgb, int width, int height) {

@@ -24,6 +24,11 @@
 //  3. The device kernel (under __HIPCC__ and RT_TEMPORAL_KERNEL): one thread
 //     per pixel, no atomics, no scratch; the bits cannot depend on the launch
 //     shape.
+// Moving bodies (rt_temporal_step_motion): tp_pixel<MOTION>
+// takes the displacement of the pixel's body as a parameter (tp_motion: the
+// row of a per-body table, by the pixel's id from body_ids.h) and subtracts it
+// in step 2; the MOTION = false instantiation never reads it and is the text
+// above unchanged.  tp_host_step_any and a second kernel carry both.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -152,9 +157,12 @@ RT_DN_FN void tp_split(float f, int* i0, float* t) {
 //   TpWord w1(size_t i)   (a1 rgb, -)
 //   DnGuide guide(size_t i)
 // read for pixels inside the image only, and only with f.have_prev.
-template <class Src>
+// MOTION (rt_temporal_step_motion): m (3 floats) is the displacement of the
+// pixel's body since the previous frame (tp_motion), subtracted in step 2;
+// without it m is not read and the text is rt_temporal_step's.
+template <bool MOTION, class Src>
 RT_DN_FN float tp_pixel(const Src& src, const TpFrame& f, int x, int y, const float* h0, const float* h1,
-                        const float* feat, float* o0, float* o1) {
+                        const float* feat, const float* m, float* o0, float* o1) {
   bool hist = f.have_prev != 0;
   float fx = 0.0f, fy = 0.0f, zexp = INFINITY;
   if (hist) {
@@ -167,7 +175,7 @@ RT_DN_FN float tp_pixel(const Src& src, const TpFrame& f, int x, int y, const fl
     if (tp_finite(zp)) {
       const float len = dn_sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
       const float sc = zp / len;
-      for (int c = 0; c < 3; ++c) w[c] = sc * e[c] + f.dc[c];
+      for (int c = 0; c < 3; ++c) w[c] = MOTION ? (sc * e[c] + f.dc[c]) - m[c] : sc * e[c] + f.dc[c];
       zexp = dn_sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
     } else {
       for (int c = 0; c < 3; ++c) w[c] = e[c];
@@ -255,35 +263,62 @@ struct TpPlain {
 };
 
 inline bool tp_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  if (!a || !b) return false;
+  if (!a || !b || na == 0 || nb == 0) return false;
   const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
   return a0 < b0 + nb && b0 < a0 + na;
 }
 
-// rt_temporal_host (rt.h): the checks, then every pixel.  0, or RT_E_ARG with
-// *why set.
-inline int tp_host_step(const rt_temporal_opts* o, const rt_camera* cam, const rt_camera* prev_cam, int width,
-                        int rows, int row0, const float* half0, const float* half1, const float* feat,
-                        const float* prev_a0, const float* prev_a1, const float* prev_guide, const float* prev_len,
-                        float* out0, float* out1, float* out_len, const char** why) {
+// Step 2's displacement of a pixel whose body is b = ids[p] (rt.h): row b of
+// `motion` (n_bodies x 4 floats) if 0 <= b < n_bodies, else (0, 0, 0).  The
+// range test is on the integer, before any load of the table.
+RT_DN_FN void tp_motion(int32_t b, const float* motion, int n_bodies, float* m) {
+  m[0] = m[1] = m[2] = 0.0f;
+  if (static_cast<uint32_t>(b) < static_cast<uint32_t>(n_bodies)) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float4 row = reinterpret_cast<const float4*>(motion)[b];   // one 16-byte load (the table is 16-byte aligned)
+    m[0] = row.x, m[1] = row.y, m[2] = row.z;
+#else
+    for (int c = 0; c < 3; ++c) m[c] = motion[4 * static_cast<size_t>(b) + c];
+#endif
+  }
+}
+// what the motion-aware step asks of its extra arguments, or nullptr
+inline const char* tp_motion_error(const int32_t* ids, const float* motion, int n_bodies) {
+  if (!ids) return "NULL argument";
+  if (n_bodies < 0) return "n_bodies < 0";
+  if (n_bodies > 0 && !motion) return "NULL argument";
+  return nullptr;
+}
+
+// rt_temporal_host and rt_temporal_host_motion (rt.h): the checks, then every
+// pixel.  0, or RT_E_ARG with *why set.
+template <bool MOTION>
+inline int tp_host_step_any(const rt_temporal_opts* o, const rt_camera* cam, const rt_camera* prev_cam, int width,
+                            int rows, int row0, const float* half0, const float* half1, const float* feat,
+                            const float* prev_a0, const float* prev_a1, const float* prev_guide, const float* prev_len,
+                            const int32_t* ids, const float* motion, int n_bodies, float* out0, float* out1,
+                            float* out_len, const char** why) {
   *why = nullptr;
   if (!cam || !half0 || !half1 || !feat || !out0 || !out1 || !out_len ||
       (prev_cam && (!prev_a0 || !prev_a1 || !prev_guide || !prev_len))) {
     *why = "NULL argument";
     return RT_E_ARG;
   }
+  if (MOTION && (*why = tp_motion_error(ids, motion, n_bodies)) != nullptr) return RT_E_ARG;
   if ((*why = tp_shape_error(width, rows, row0)) != nullptr) return RT_E_ARG;
   const rt_temporal_opts opt = o ? *o : tp_default_opts();
   if ((*why = tp_opts_error(opt)) != nullptr) return RT_E_ARG;
   const size_t n_px = static_cast<size_t>(width) * rows, fb = sizeof(float);
   const void* outs[3] = {out0, out1, out_len};
   const size_t out_b[3] = {n_px * 3 * fb, n_px * 3 * fb, n_px * fb};
-  const void* ins[7] = {half0, half1, feat, prev_a0, prev_a1, prev_guide, prev_len};
-  const size_t in_b[7] = {n_px * 3 * fb, n_px * 3 * fb, n_px * RT_FEAT_CHANNELS * fb, n_px * 3 * fb,
-                          n_px * 3 * fb, n_px * 4 * fb, n_px * fb};
+  const void* ins[9] = {half0,      half1,    feat, prev_a0, prev_a1,
+                        prev_guide, prev_len, MOTION ? ids : nullptr, MOTION ? motion : nullptr};
+  const size_t in_b[9] = {n_px * 3 * fb, n_px * 3 * fb, n_px * RT_FEAT_CHANNELS * fb,
+                          n_px * 3 * fb, n_px * 3 * fb, n_px * 4 * fb,
+                          n_px * fb,     n_px * sizeof(int32_t), static_cast<size_t>(MOTION ? n_bodies : 0) * 4 * fb};
   for (int a = 0; a < 3; ++a) {
-    for (int b = 0; b < 7; ++b)
-      if ((b < 3 || prev_cam) && tp_overlap(outs[a], out_b[a], ins[b], in_b[b])) {
+    for (int b = 0; b < 9; ++b)
+      if ((b < 3 || b > 6 || prev_cam) && tp_overlap(outs[a], out_b[a], ins[b], in_b[b])) {
         *why = "an output overlaps an input";
         return RT_E_ARG;
       }
@@ -305,10 +340,27 @@ inline int tp_host_step(const rt_temporal_opts* o, const rt_camera* cam, const r
   for (int y = 0; y < rows; ++y)
     for (int x = 0; x < width; ++x) {
       const size_t i = static_cast<size_t>(y) * width + x;
-      out_len[i] = tp_pixel(src, f, x, y, half0 + 3 * i, half1 + 3 * i, feat + RT_FEAT_CHANNELS * i, out0 + 3 * i,
-                            out1 + 3 * i);
+      const float* ft = feat + RT_FEAT_CHANNELS * i;
+      float m[3] = {0.0f, 0.0f, 0.0f};
+      if (MOTION && tp_finite(ft[6])) tp_motion(ids[i], motion, n_bodies, m);   // (a sky pixel ignores its id)
+      out_len[i] = tp_pixel<MOTION>(src, f, x, y, half0 + 3 * i, half1 + 3 * i, ft, m, out0 + 3 * i, out1 + 3 * i);
     }
   return RT_OK;
+}
+inline int tp_host_step(const rt_temporal_opts* o, const rt_camera* cam, const rt_camera* prev_cam, int width,
+                        int rows, int row0, const float* half0, const float* half1, const float* feat,
+                        const float* prev_a0, const float* prev_a1, const float* prev_guide, const float* prev_len,
+                        float* out0, float* out1, float* out_len, const char** why) {
+  return tp_host_step_any<false>(o, cam, prev_cam, width, rows, row0, half0, half1, feat, prev_a0, prev_a1, prev_guide,
+                                 prev_len, nullptr, nullptr, 0, out0, out1, out_len, why);
+}
+inline int tp_host_step_motion(const rt_temporal_opts* o, const rt_camera* cam, const rt_camera* prev_cam, int width,
+                               int rows, int row0, const float* half0, const float* half1, const float* feat,
+                               const float* prev_a0, const float* prev_a1, const float* prev_guide,
+                               const float* prev_len, const int32_t* ids, const float* motion, int n_bodies,
+                               float* out0, float* out1, float* out_len, const char** why) {
+  return tp_host_step_any<true>(o, cam, prev_cam, width, rows, row0, half0, half1, feat, prev_a0, prev_a1, prev_guide,
+                                prev_len, ids, motion, n_bodies, out0, out1, out_len, why);
 }
 
 #if defined(__HIPCC__) && defined(RT_TEMPORAL_KERNEL)
@@ -349,7 +401,42 @@ __global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_kernel(
 #pragma unroll
   for (int c = 0; c < RT_FEAT_CHANNELS; ++c) ft[c] = feat[i * RT_FEAT_CHANNELS + c];
   const TpPacked src{prev_a0, prev_a1, prev_g};
-  const float n = tp_pixel(src, f, x, y, h0, h1, ft, o0, o1);
+  const float n = tp_pixel<false>(src, f, x, y, h0, h1, ft, nullptr, o0, o1);
+  new_a0[i] = TpWord{o0[0], o0[1], o0[2], n};
+  new_a1[i] = TpWord{o1[0], o1[1], o1[2], 0.0f};
+  new_g[i] = DnGuide{ft[3], ft[4], ft[5], ft[6]};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    out0[i * 3 + c] = o0[c];
+    out1[i * 3 + c] = o1[c];
+  }
+}
+
+// rt_temporal_step_motion's kernel: the same thread, loads and stores, plus the
+// pixel's body id (one dword) and, for an id inside the table, that body's row
+// (one 16-byte word; neighbouring pixels mostly share a body, and the whole
+// table -- 16 bytes a body -- stays in the caches).  A sky pixel loads neither.
+__global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_motion_kernel(
+    const TpFrame f, const float* __restrict__ half0, const float* __restrict__ half1, const float* __restrict__ feat,
+    const int32_t* __restrict__ ids, const float* __restrict__ motion, const int n_bodies,
+    const TpWord* __restrict__ prev_a0, const TpWord* __restrict__ prev_a1, const DnGuide* __restrict__ prev_g,
+    TpWord* __restrict__ new_a0, TpWord* __restrict__ new_a1, DnGuide* __restrict__ new_g, float* __restrict__ out0,
+    float* __restrict__ out1) {
+  const int x = static_cast<int>(blockIdx.x) * kDnBx + static_cast<int>(threadIdx.x);
+  const int y = static_cast<int>(blockIdx.y) * kDnBy + static_cast<int>(threadIdx.y);
+  if (x >= f.width || y >= f.rows) return;
+  const size_t i = static_cast<size_t>(y) * f.width + x;
+  float h0[3], h1[3], ft[RT_FEAT_CHANNELS], o0[3], o1[3], m[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    h0[c] = half0[i * 3 + c];
+    h1[c] = half1[i * 3 + c];
+  }
+#pragma unroll
+  for (int c = 0; c < RT_FEAT_CHANNELS; ++c) ft[c] = feat[i * RT_FEAT_CHANNELS + c];
+  if (tp_finite(ft[6])) tp_motion(ids[i], motion, n_bodies, m);
+  const TpPacked src{prev_a0, prev_a1, prev_g};
+  const float n = tp_pixel<true>(src, f, x, y, h0, h1, ft, m, o0, o1);
   new_a0[i] = TpWord{o0[0], o0[1], o0[2], n};
   new_a1[i] = TpWord{o1[0], o1[1], o1[2], 0.0f};
   new_g[i] = DnGuide{ft[3], ft[4], ft[5], ft[6]};

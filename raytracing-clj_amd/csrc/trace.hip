@@ -11,7 +11,9 @@
 // is variant_policy.h's (pure functions, checked on the CPU); the device
 // buffers the host side owns are dev_buf.h's DevBuf.  The denoiser's kernels
 // (denoise.h) and the rt_denoiser entries, then temporal accumulation's kernel
-// (temporal.h) and the rt_temporal entries close the file.
+// (temporal.h) and the rt_temporal entries close the file;
+// the body-id pass (body_ids.h, rt_launch_ids) stands behind the feature pass
+// and the motion-aware step beside rt_temporal_step.
 #include "trace_kernel.h"
 #define RT_FIRST_HIT_KERNEL
 #include "first_hit.h"
@@ -19,6 +21,8 @@
 #include "denoise.h"
 #define RT_TEMPORAL_KERNEL
 #include "temporal.h"
+#define RT_BODY_IDS_KERNEL
+#include "body_ids.h"
 #include "variant_policy.h"
 #include "dev_buf.h"
 
@@ -782,7 +786,9 @@ extern "C" int rt_scene_upload(int device, const rt_scene* s, rt_dscene** out) {
   for (int i = 0; i < n; ++i) {
     const float* q = s->sphere + 4 * i;
     const float r = q[3];
-    geo[i] = make_float4(q[0], q[1], q[2], -(r * r));
+    float g[4];
+    fh_geo(q, g);   // (centre, -r^2): first_hit.h's, which rt_ids_host builds too
+    geo[i] = make_float4(g[0], g[1], g[2], g[3]);
     sph[i] = make_float4(q[0], q[1], q[2], 1.0f / r);                   // 1/r for the normal
     const float* m = s->mat + 4 * i;
     mat[i] = make_float4(m[0], m[1], m[2], m[3]);
@@ -2060,6 +2066,70 @@ extern "C" int rt_feat_occupancy(const rt_dscene* ds, int* out4) {
   return RT_OK;
 }
 
+// ---- the body-id pass (rt.h, body_ids.h) --------------------------------------
+static const void* ids_fn(int src) {
+  return src == FEAT_LDS      ? reinterpret_cast<const void*>(&ids_kernel<FEAT_LDS>)
+         : src == FEAT_GLOBAL ? reinterpret_cast<const void*>(&ids_kernel<FEAT_GLOBAL>)
+                              : reinterpret_cast<const void*>(&ids_kernel<FEAT_SCAN>);
+}
+
+extern "C" int rt_launch_ids(const rt_dscene* ds, const rt_camera* c, int width, int rows, int row0, int32_t* d_ids,
+                             void* hip_stream) {
+  clear_error();
+  const std::string me("rt_launch_ids");
+  if (!ds || !c || !d_ids) return set_error(RT_E_ARG, me + ": NULL argument");
+  if (const char* why = tp_shape_error(width, rows, row0)) return set_error(RT_E_ARG, me + ": " + why);
+  // (the kernel's grid has a block row per kDnBy image rows)
+  if ((rows + kDnBy - 1) / kDnBy > 65535) return set_error(RT_E_ARG, me + ": bad width/rows");
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (stream) {
+    hipDevice_t sdev = 0;
+    if (hipStreamGetDevice(stream, &sdev) == hipSuccess && static_cast<int>(sdev) != ds->device)
+      return set_error(RT_E_ARG, me + ": the stream is on device " + std::to_string(static_cast<int>(sdev)) +
+                                     ", the scene on device " + std::to_string(ds->device));
+  }
+  HIP_TRY(hipSetDevice(ds->device));
+  const policy::Scene si = scene_info(*ds);
+  const int src = policy::ids_source(si, g_variant.load(), kDiag);
+  const DTree& tr = ds->tree[1];
+  IdsArgs a{};
+  a.geo = ds->geo;
+  a.blob = tr.blob;
+  a.blob_f4 = tr.blob_f4;
+  a.off_pairs = tr.off_pairs;
+  a.off_pidx = tr.off_pidx;
+  a.leaf_pairs = 2;
+  a.big_pair0 = tr.big_pair0;
+  a.n_big_leaves = tr.n_big_leaves;
+  a.ref_mul = 1;   // (rt_scene_upload made the 4-body tree's inner refs byte offsets)
+  for (int k = 0; k < 3; ++k) a.bvh_c[k] = tr.c[k];
+  a.bvh_r = tr.r;
+  a.bvh_c0 = tr.c0;
+  ids_cam12(*c, a.cam);
+  a.n = ds->n;
+  a.width = width;
+  a.rows = rows;
+  a.row0 = row0;
+  a.ids = d_ids;
+  const dim3 grid(static_cast<unsigned>((width + kDnBx - 1) / kDnBx), static_cast<unsigned>((rows + kDnBy - 1) / kDnBy)),
+      block(kDnBx, kDnBy);
+  HIP_TRY(enqueue(ids_fn(src), grid, block, policy::feat_lds(si, src), stream, a));
+  return RT_OK;
+}
+
+// The body-id kernel a launch on ds would run under the current selector
+// (diagnostic, tools/motion_time.py): out4 as rt_feat_occupancy's.
+extern "C" int rt_ids_occupancy(const rt_dscene* ds, int* out4) {
+  clear_error();
+  if (!ds || !out4) return set_error(RT_E_ARG, "rt_ids_occupancy: NULL argument");
+  HIP_TRY(hipSetDevice(ds->device));
+  const policy::Scene si = scene_info(*ds);
+  const int src = policy::ids_source(si, g_variant.load(), kDiag);
+  if (const int rc = occupancy_report(ids_fn(src), kFeatThreads, policy::feat_lds(si, src), out4)) return rc;
+  out4[3] = src;
+  return RT_OK;
+}
+
 // ---- the denoiser (rt.h, denoise.h) -----------------------------------------
 // Its scratch on the device: the two texel arrays the levels ping-pong between
 // and the guides the prep packs, for one image size.  mu orders the calls'
@@ -2291,18 +2361,26 @@ extern "C" int64_t rt_temporal_frames(const rt_temporal* t) {
   return t->frames;
 }
 
-extern "C" int rt_temporal_step(rt_temporal* t, const rt_temporal_opts* o, const rt_camera* cam, const float* d_half0,
-                                const float* d_half1, const float* d_feat, float* d_out0, float* d_out1,
-                                void* hip_stream) {
+// rt_temporal_step (motion == false: d_ids, d_motion and n_bodies are not
+// looked at) and rt_temporal_step_motion: the checks, the set-up, one kernel
+template <bool MOTION>
+static int temporal_step(const std::string& me, rt_temporal* t, const rt_temporal_opts* o, const rt_camera* cam,
+                         const float* d_half0, const float* d_half1, const float* d_feat, const int32_t* d_ids,
+                         const float* d_motion, int n_bodies, float* d_out0, float* d_out1, void* hip_stream) {
   clear_error();
-  const std::string me("rt_temporal_step");
   if (!t || !cam || !d_half0 || !d_half1 || !d_feat || !d_out0 || !d_out1)
     return set_error(RT_E_ARG, me + ": NULL argument");
+  if (MOTION) {
+    if (const char* why = tp_motion_error(d_ids, d_motion, n_bodies)) return set_error(RT_E_ARG, me + ": " + why);
+    if (reinterpret_cast<uintptr_t>(d_motion) % 16 != 0) return set_error(RT_E_ARG, me + ": d_motion is not 16-byte aligned");
+  }
   const rt_temporal_opts opt = o ? *o : tp_default_opts();
   if (const char* why = tp_opts_error(opt)) return set_error(RT_E_ARG, me + ": " + why);
   const size_t cb = t->n_px * 3 * sizeof(float), fb = t->n_px * RT_FEAT_CHANNELS * sizeof(float);
+  const size_t ib = MOTION ? t->n_px * sizeof(int32_t) : 0, mb = MOTION ? static_cast<size_t>(n_bodies) * 4 * sizeof(float) : 0;
   for (const float* d_out : {d_out0, d_out1})
-    if (tp_overlap(d_out, cb, d_half0, cb) || tp_overlap(d_out, cb, d_half1, cb) || tp_overlap(d_out, cb, d_feat, fb))
+    if (tp_overlap(d_out, cb, d_half0, cb) || tp_overlap(d_out, cb, d_half1, cb) || tp_overlap(d_out, cb, d_feat, fb) ||
+        tp_overlap(d_out, cb, d_ids, ib) || tp_overlap(d_out, cb, d_motion, mb))
       return set_error(RT_E_ARG, me + ": an output overlaps an input");
   if (tp_overlap(d_out0, cb, d_out1, cb)) return set_error(RT_E_ARG, me + ": the outputs overlap");
   std::lock_guard<std::mutex> lk(t->mu);
@@ -2319,13 +2397,33 @@ extern "C" int rt_temporal_step(rt_temporal* t, const rt_temporal_opts* o, const
   const dim3 grid(static_cast<unsigned>((t->width + kDnBx - 1) / kDnBx),
                   static_cast<unsigned>((t->rows + kDnBy - 1) / kDnBy)),
       block(kDnBx, kDnBy);
-  HIP_TRY(enqueue(temporal_step_kernel, grid, block, 0, stream, f, d_half0, d_half1, d_feat, t->a0[src].p,
-                  t->a1[src].p, t->guide[src].p, t->a0[dst].p, t->a1[dst].p, t->guide[dst].p, d_out0, d_out1));
+  if (MOTION)
+    HIP_TRY(enqueue(temporal_step_motion_kernel, grid, block, 0, stream, f, d_half0, d_half1, d_feat, d_ids, d_motion,
+                    n_bodies, t->a0[src].p, t->a1[src].p, t->guide[src].p, t->a0[dst].p, t->a1[dst].p, t->guide[dst].p,
+                    d_out0, d_out1));
+  else
+    HIP_TRY(enqueue(temporal_step_kernel, grid, block, 0, stream, f, d_half0, d_half1, d_feat, t->a0[src].p,
+                    t->a1[src].p, t->guide[src].p, t->a0[dst].p, t->a1[dst].p, t->guide[dst].p, d_out0, d_out1));
   t->cur = dst;
   t->prev = *cam;
   t->have_prev = true;
   t->frames += 1;
   return RT_OK;
+}
+
+extern "C" int rt_temporal_step(rt_temporal* t, const rt_temporal_opts* o, const rt_camera* cam, const float* d_half0,
+                                const float* d_half1, const float* d_feat, float* d_out0, float* d_out1,
+                                void* hip_stream) {
+  return temporal_step<false>("rt_temporal_step", t, o, cam, d_half0, d_half1, d_feat, nullptr, nullptr, 0, d_out0, d_out1,
+                              hip_stream);
+}
+
+extern "C" int rt_temporal_step_motion(rt_temporal* t, const rt_temporal_opts* o, const rt_camera* cam,
+                                       const float* d_half0, const float* d_half1, const float* d_feat,
+                                       const int32_t* d_ids, const float* d_motion, int n_bodies, float* d_out0,
+                                       float* d_out1, void* hip_stream) {
+  return temporal_step<true>("rt_temporal_step_motion", t, o, cam, d_half0, d_half1, d_feat, d_ids, d_motion, n_bodies,
+                             d_out0, d_out1, hip_stream);
 }
 
 extern "C" int rt_temporal_read(const rt_temporal* t, float* host_a0, float* host_a1, float* host_guide,

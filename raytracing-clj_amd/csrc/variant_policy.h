@@ -292,6 +292,15 @@ inline size_t feat_lds(const Scene& ds, int src) {
   return src == FEAT_SCAN ? 0 : feat_stack_bytes(t) + (src == FEAT_LDS ? static_cast<size_t>(t.blob_f4) * 16 : 0);
 }
 
+// Where a body-id launch on ds (body_ids.h, rt_launch_ids) takes its bodies
+// from: a feature launch's source and LDS (the same tree, the same stack rows
+// for the same 256 lanes).  A workgroup traces one ray a thread here, against
+// 64 x spp of feat_kernel, and stages the same image; staging still wins on
+// C1's frame -- 19.8 us with the tree in LDS, 27.6 us with it in global memory
+// (tools/motion_time.py) -- so the default is the feature
+// pass's.
+inline int ids_source(const Scene& ds, int vsel, bool diag) { return feat_source(ds, vsel, diag); }
+
 // Sample split (rt_launch): split every tile of a launch with fewer tiles
 // than kSplitRounds (RTCLJ_SPLIT_ROUNDS, default 3) x (resident workgroups), into enough splits to reach that
 // (at most kSplitMax).  tools/shard_time.py on C1's 1/2/4/8-GPU shards

@@ -176,6 +176,17 @@ SIGNATURES = {
                                    C.POINTER(C.c_float), C.c_void_p]),
     "rt_temporal_host": (C.c_int, [C.POINTER(rt_temporal_opts), C.POINTER(rt_camera), C.POINTER(rt_camera), C.c_int,
                                    C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 10),
+    "rt_temporal_step_motion": (C.c_int, [C.c_void_p, C.POINTER(rt_temporal_opts), C.POINTER(rt_camera), C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "rt_temporal_host_motion": (C.c_int, [C.POINTER(rt_temporal_opts), C.POINTER(rt_camera), C.POINTER(rt_camera),
+                                          C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 7 +
+                                [C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int] + [C.POINTER(C.c_float)] * 3),
+    "rt_launch_ids": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_ids_host": (C.c_int, [C.POINTER(rt_scene), C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int,
+                              C.POINTER(C.c_int32)]),
+    "rt_ids_occupancy": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rt_body_motion": (C.c_int, [C.POINTER(rt_scene), C.POINTER(rt_scene), C.POINTER(C.c_float)]),
     "rt_quantize_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rt_set_variant": (C.c_int, [C.c_int]),
     "rt_resolve_variant": (C.c_int, [C.c_void_p]),
@@ -203,7 +214,8 @@ ADDITIVE = {"rt_prepare", "rt_render_u8", "rt_quantize_device", "rt_render_submi
             "rt_feat_add", "rt_feat_resolve_host", "rt_feat_occupancy", "rt_adapt_resolve_half",
             "rt_denoiser_create", "rt_denoiser_free", "rt_denoise", "rt_denoise_profile",
             "rt_denoise_host", "rt_temporal_create", "rt_temporal_free", "rt_temporal_reset", "rt_temporal_frames",
-            "rt_temporal_step", "rt_temporal_read", "rt_temporal_host"}
+            "rt_temporal_step", "rt_temporal_read", "rt_temporal_host", "rt_temporal_step_motion",
+            "rt_temporal_host_motion", "rt_launch_ids", "rt_ids_host", "rt_ids_occupancy", "rt_body_motion"}
 
 RT_FEAT_CHANNELS = 8   # rt_feat_resolve's floats per pixel: albedo rgb, normal xyz, depth, coverage
 
@@ -254,6 +266,10 @@ def fptr(a):
 
 def iptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def i32ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
 def u8ptr(a):

@@ -26,7 +26,7 @@ import numpy as np
 from . import hittable, material
 from ._lib import (DENOISE_DEFAULTS, RT_DIELECTRIC, RT_FEAT_CHANNELS, RT_LAMBERTIAN, RT_METAL, RT_NONE,
                    TEMPORAL_DEFAULTS, RTError, check, dptr, fptr, i64ptr, iptr, lib, rt_adapt_opts, rt_camera,
-                   rt_denoise_opts, rt_params, rt_scene, rt_stats, rt_temporal_opts, u8ptr, u32ptr, u64ptr)
+                   i32ptr, rt_denoise_opts, rt_params, rt_scene, rt_stats, rt_temporal_opts, u8ptr, u32ptr, u64ptr)
 
 # ---- scene (raytracing.clj:63-78) --------------------------------------------
 hittables = [
@@ -640,16 +640,19 @@ def _temporal_opts(opts: dict) -> rt_temporal_opts:
                             normal_min=float(o["normal_min"]))
 
 
-def temporal_host(cam: rt_camera, prev_cam, half0, half1, feat, prev=None, row0: int = 0, library=None, **opts):
+def temporal_host(cam: rt_camera, prev_cam, half0, half1, feat, prev=None, row0: int = 0, library=None, ids=None,
+                  motion=None, **opts):
     """rt_temporal_host (include/rt.h): one step of temporal accumulation on the
     host, in plain C++ -- the bits Temporal.step gives on the device.  half0,
     half1: float32 (rows, width, 3); feat: float32 (rows, width, 8); cam: the
     camera that drew them.  prev_cam and prev = (a0, a1, guide, length) are
     the previous camera and the history as Temporal.read() gives it -- (rows,
     width, 3) twice, (rows, width, 4), (rows, width) -- or both None: no
-    history.  Options: max_history, sigma_z, normal_min.  Returns (out0, out1,
-    length): the new history's halves and its length; its guides are
-    feat[..., 3:7]."""
+    history.  Options: max_history, sigma_z, normal_min.  With `ids` (int32
+    (rows, width), as ids_host gives them) it is rt_temporal_host_motion:
+    `motion` (float32 (n_bodies, 4), as body_motion gives it; None: no body
+    moved) is subtracted for the pixel's body.  Returns (out0, out1, length):
+    the new history's halves and its length; its guides are feat[..., 3:7]."""
     dll = library if library is not None else lib
     half0 = np.ascontiguousarray(half0, np.float32)
     half1 = np.ascontiguousarray(half1, np.float32)
@@ -668,10 +671,21 @@ def temporal_host(cam: rt_camera, prev_cam, half0, half1, feat, prev=None, row0:
     out0, out1 = np.empty(half0.shape, np.float32), np.empty(half0.shape, np.float32)
     length = np.empty((rows, width), np.float32)
     o = _temporal_opts(opts)
-    code = dll.rt_temporal_host(C.byref(o), C.byref(cam), C.byref(prev_cam) if prev_cam is not None else None, width,
-                                rows, int(row0), fptr(half0), fptr(half1), fptr(feat),
-                                *(fptr(a) if a is not None else None for a in hist), fptr(out0), fptr(out1),
-                                fptr(length))
+    head = (C.byref(o), C.byref(cam), C.byref(prev_cam) if prev_cam is not None else None, width, rows, int(row0),
+            fptr(half0), fptr(half1), fptr(feat), *(fptr(a) if a is not None else None for a in hist))
+    if ids is None:
+        if motion is not None:
+            raise ValueError("temporal_host: motion comes with ids")
+        code = dll.rt_temporal_host(*head, fptr(out0), fptr(out1), fptr(length))
+    else:
+        ids = np.ascontiguousarray(ids, np.int32)
+        if ids.shape != (rows, width):
+            raise ValueError("temporal_host: ids must be int32 (rows, width)")
+        motion = np.zeros((0, 4), np.float32) if motion is None else np.ascontiguousarray(motion, np.float32)
+        if motion.ndim != 2 or motion.shape[1] != 4:
+            raise ValueError("temporal_host: motion must be float32 (n_bodies, 4)")
+        code = dll.rt_temporal_host_motion(*head, i32ptr(ids), fptr(motion) if len(motion) else None, len(motion),
+                                           fptr(out0), fptr(out1), fptr(length))
     if code < 0:
         raise RTError(code, dll.rt_last_error().decode(errors="replace"))
     return out0, out1, length
@@ -711,13 +725,25 @@ class Temporal:
         return int(self._dll.rt_temporal_frames(self._tp))
 
     def step(self, cam: rt_camera, d_half0: int, d_half1: int, d_feat: int, d_out0: int, d_out1: int, stream=None,
-             **opts) -> None:
+             d_ids=None, d_motion=None, n_bodies: int = 0, **opts) -> None:
         """Enqueue one step (rt_temporal_step) on device addresses; options as
-        temporal_host."""
+        temporal_host.  With `d_ids` (int32 (rows, width) on the device, as
+        body_ids_into writes them) it is rt_temporal_step_motion: `d_motion`
+        is body_motion's table on the device (n_bodies x 4 float32, 16-byte
+        aligned).  Both kinds of step may alternate on one object."""
         o = _temporal_opts(opts)
-        self._check(self._dll.rt_temporal_step(self._tp, C.byref(o), C.byref(cam), C.c_void_p(d_half0),
-                                               C.c_void_p(d_half1), C.c_void_p(d_feat), C.c_void_p(d_out0),
-                                               C.c_void_p(d_out1), C.c_void_p(stream) if stream else None))
+        st = C.c_void_p(stream) if stream else None
+        if d_ids is None:
+            if d_motion is not None or n_bodies:
+                raise ValueError("Temporal.step: d_motion and n_bodies come with d_ids")
+            self._check(self._dll.rt_temporal_step(self._tp, C.byref(o), C.byref(cam), C.c_void_p(d_half0),
+                                                   C.c_void_p(d_half1), C.c_void_p(d_feat), C.c_void_p(d_out0),
+                                                   C.c_void_p(d_out1), st))
+        else:
+            self._check(self._dll.rt_temporal_step_motion(
+                self._tp, C.byref(o), C.byref(cam), C.c_void_p(d_half0), C.c_void_p(d_half1), C.c_void_p(d_feat),
+                C.c_void_p(d_ids), C.c_void_p(d_motion) if d_motion else None, int(n_bodies), C.c_void_p(d_out0),
+                C.c_void_p(d_out1), st))
 
     def read(self, stream=None):
         """(a0, a1, guide, length): the current history copied out behind the
@@ -810,6 +836,164 @@ def render_sequence(scene, cameras, width: int, height: int, spp: int = 4, max_d
                 yield out
             cam = next(cameras, None)
             f += 1
+
+
+def ids_host(scene, cam: rt_camera, width: int, rows: int, row0: int = 0, library=None) -> np.ndarray:
+    """rt_ids_host (include/rt.h): per pixel of a rows x width image whose first
+    row is camera row row0, the index of the body the pixel centre's pinhole
+    ray meets first, or -1 -- on the host, in plain C++; the integers
+    body_ids_into gives on the device.  Returns int32 (rows, width)."""
+    dll = library if library is not None else lib
+    sc = scene if isinstance(scene, Scene) else Scene.from_bodies(scene)
+    out = np.empty((max(int(rows), 0), max(int(width), 0)), np.int32)
+    code = dll.rt_ids_host(C.byref(sc.c), C.byref(cam), int(width), int(rows), int(row0), i32ptr(out))
+    if code < 0:
+        raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+    return out
+
+
+def body_ids_into(scene, cam: rt_camera, width: int, height: int, d_ids: int, rows=None, stream=None, device: int = 0,
+                  library=None) -> None:
+    """rt_launch_ids (include/rt.h) for a scene on the host: upload it, enqueue
+    the body-id pass for camera rows `rows` = (first, end) (default: all
+    `height`) into d_ids (a device address: int32, (end - first) x width), wait
+    for it and free the scene.  A caller with an uploaded scene calls
+    rt_launch_ids itself (render_animation does)."""
+    dll = library if library is not None else lib
+    sc = scene if isinstance(scene, Scene) else Scene.from_bodies(scene)
+    r0, r1 = (0, height) if rows is None else rows
+    st = C.c_void_p(stream) if stream else None
+    ds = C.c_void_p()
+
+    def ok(code):
+        if code < 0:
+            raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+
+    try:
+        ok(dll.rt_scene_upload(int(device), C.byref(sc.c), C.byref(ds)))
+        ok(dll.rt_launch_ids(ds, C.byref(cam), int(width), int(r1 - r0), int(r0), C.c_void_p(d_ids), st))
+        _stream_wait(st)
+    finally:
+        dll.rt_scene_free(ds)
+
+
+def _stream_wait(st) -> None:
+    """Wait for a HIP stream's work through torch's runtime (the process's one)."""
+    import torch
+    if st is None or not st.value:
+        torch.cuda.synchronize()
+    else:
+        torch.cuda.ExternalStream(st.value).synchronize()
+
+
+def body_motion(cur_scene, prev_scene, library=None) -> np.ndarray:
+    """rt_body_motion (include/rt.h): float32 (n, 4), per body its centre's
+    displacement from prev_scene to cur_scene (lane 3 is 0); NaN for a body
+    whose radius or material changed -- it has no past."""
+    dll = library if library is not None else lib
+    cur = cur_scene if isinstance(cur_scene, Scene) else Scene.from_bodies(cur_scene)
+    prev = prev_scene if isinstance(prev_scene, Scene) else Scene.from_bodies(prev_scene)
+    out = np.empty((len(cur), 4), np.float32)
+    code = dll.rt_body_motion(C.byref(cur.c), C.byref(prev.c), fptr(out))
+    if code < 0:
+        raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+    return out
+
+
+def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max_depth: int = 50, seed: int = 1,
+                     flags: int = 0, library=None, temporal=None, stages: bool = False, **opts):
+    """render_sequence for bodies that move: one Scene per frame (all with the
+    same body count), zipped with `cameras`; a generator that yields float32
+    (height, width, 3) per frame, on device 0.  Per frame f: the scene's upload
+    (rt_scene_upload builds its trees on the host; they are not refitted), two
+    accumulators of spp / 2 samples each from sample index f * spp, the
+    first-hit features of all spp, the body ids (rt_launch_ids), body_motion
+    against the previous frame's scene (frame 0: no displacement), the
+    motion-aware step (rt_temporal_step_motion) and Denoiser.run.  `spp` must be
+    even; `temporal` and further keywords as render_sequence.  With `stages` it
+    yields (denoised, half0, half1, feat, acc0, acc1, ids).  With identical
+    scenes it gives render_sequence's bits."""
+    if spp <= 0 or spp % 2:
+        raise ValueError("render_animation: spp must be even and positive")
+    _denoise_opts(opts)
+    topts = dict(temporal or {})
+    _temporal_opts(topts)
+    import torch
+    if not torch.cuda.is_available():
+        raise RTError(-5, "render_animation: torch sees no GPU (import torch before rtclj)")
+    dll = library if library is not None else lib
+
+    def ok(code):
+        if code < 0:
+            raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+
+    half = spp // 2
+    dev = torch.device("cuda", 0)
+    n_px = width * height
+    d_h = [torch.empty(n_px * 3, dtype=torch.float32, device=dev) for _ in range(2)]
+    d_acc = [torch.empty(n_px * 3, dtype=torch.float32, device=dev) for _ in range(2)]
+    d_feat = torch.empty(n_px * RT_FEAT_CHANNELS, dtype=torch.float32, device=dev)
+    d_ids = torch.empty(n_px, dtype=torch.int32, device=dev)
+    d_out = torch.empty(n_px * 3, dtype=torch.float32, device=dev)
+    d_motion = None
+    torch.cuda.synchronize(dev)   # (the passes below run on the NULL stream)
+    shape = rt_params(width=width, height=height, row_begin=0, row_end=height, spp=0, max_depth=max_depth, seed=seed,
+                      flags=flags)
+    ds, acc, ft = C.c_void_p(), [C.c_void_p(), C.c_void_p()], C.c_void_p()
+    prev_sc = None
+    try:
+        with Temporal(width, height, library=library) as tp, Denoiser(width, height, library=library) as dn:
+            for f, (scene, cam) in enumerate(zip(scenes, cameras)):
+                sc = scene if isinstance(scene, Scene) else Scene.from_bodies(scene)
+                if prev_sc is not None and len(sc) != len(prev_sc):
+                    raise ValueError("render_animation: every scene must have the same body count")
+                ok(dll.rt_scene_upload(0, C.byref(sc.c), C.byref(ds)))
+                if f == 0:
+                    for a in acc:
+                        ok(dll.rt_accum_create(ds, C.byref(shape), C.byref(a)))
+                    ok(dll.rt_feat_create(ds, C.byref(shape), C.byref(ft)))
+                    motion = np.zeros((len(sc), 4), np.float32)
+                else:
+                    for a in acc:
+                        ok(dll.rt_accum_clear(a, None))
+                    ok(dll.rt_feat_clear(ft, None))
+                    motion = body_motion(sc, prev_sc, library=library)
+                for a, begin, n in ((acc[0], f * spp, half), (acc[1], f * spp + half, half)):
+                    p = rt_params.from_buffer_copy(shape)
+                    p.spp, p.sample_begin = n, begin
+                    ok(dll.rt_launch_accum(ds, C.byref(cam), C.byref(p), a, None, None))
+                p = rt_params.from_buffer_copy(shape)
+                p.spp, p.sample_begin, p.max_depth = spp, f * spp, 1
+                ok(dll.rt_launch_feat(ds, C.byref(cam), C.byref(p), ft, None, None))
+                ok(dll.rt_launch_ids(ds, C.byref(cam), width, height, 0, C.c_void_p(d_ids.data_ptr()), None))
+                ok(dll.rt_accum_resolve(acc[0], flags, C.c_void_p(d_h[0].data_ptr()), None))
+                ok(dll.rt_accum_resolve(acc[1], flags, C.c_void_p(d_h[1].data_ptr()), None))
+                ok(dll.rt_feat_resolve(ft, C.c_void_p(d_feat.data_ptr()), None))
+                d_motion = torch.from_numpy(motion.reshape(-1)).to(dev)   # (torch's allocations are 256-byte aligned)
+                tp.step(cam, d_h[0].data_ptr(), d_h[1].data_ptr(), d_feat.data_ptr(), d_acc[0].data_ptr(),
+                        d_acc[1].data_ptr(), d_ids=d_ids.data_ptr(), d_motion=d_motion.data_ptr() if len(sc) else None,
+                        n_bodies=len(sc), **topts)
+                dn.run(d_acc[0].data_ptr(), d_acc[1].data_ptr(), d_feat.data_ptr(), d_out.data_ptr(), **opts)
+                torch.cuda.synchronize(dev)
+                ok(dll.rt_scene_free(ds))
+                ds = C.c_void_p()
+                prev_sc = sc
+                out = d_out.cpu().numpy().reshape(height, width, 3)
+                if stages:
+                    yield (out,) + tuple(d.cpu().numpy().reshape(height, width, 3) for d in d_h) + \
+                        (d_feat.cpu().numpy().reshape(height, width, RT_FEAT_CHANNELS),) + \
+                        tuple(d.cpu().numpy().reshape(height, width, 3) for d in d_acc) + \
+                        (d_ids.cpu().numpy().reshape(height, width),)
+                else:
+                    yield out
+    finally:
+        if ds:
+            dll.rt_scene_free(ds)
+        for a in acc:
+            if a:
+                dll.rt_accum_free(a)
+        if ft:
+            dll.rt_feat_free(ft)
 
 
 def pass_sizes(spp: int, passes: int):
@@ -987,4 +1171,4 @@ if __name__ == "__main__":  # python -m rtclj.raytracing [spp] [depth]
 
 
 __all__ = ["hittables", "REFERENCE_CAMERA", "image_height", "flatten", "flatten64", "Scene", "camera", "render", "Progressive", "Adaptive", "pass_sizes",
-           "Features", "denoise_host", "Denoiser", "render_denoised", "temporal_host", "Temporal", "render_sequence", "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]
+           "Features", "denoise_host", "Denoiser", "render_denoised", "temporal_host", "Temporal", "render_sequence", "ids_host", "body_ids_into", "body_motion", "render_animation", "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]
