@@ -924,6 +924,105 @@ int rt_temporal_host_motion(const rt_temporal_opts* o, const rt_camera* cam, con
                             const int32_t* ids, const float* motion, int n_bodies, float* out0, float* out1,
                             float* out_len);
 
+/* ---- moving bodies: an uploaded scene updated in place --------------------------
+ * raytracing.clj:63-78's bodies at new centres, without a new rt_scene_upload:
+ * the scene's trees keep their topology and are refitted on the device.
+ *
+ * rt_scene_update: sphere is a host array of ds's n x 4 floats (centre, radius)
+ * in body order; the scene's materials, kinds and radii stay.  After the call,
+ * in the order of hip_stream (NULL: the default stream), the scene on the
+ * device is what rt_scene_upload would have made of the new spheres had its
+ * builder kept the upload's topology: which bodies are out of the tree, which
+ * are big, each leaf's bodies, each node's children.
+ *
+ * Preconditions; any violation returns RT_E_ARG and nothing on the device or
+ * in ds has changed:
+ *   - no argument is NULL (a NULL sphere is allowed when n == 0);
+ *   - every radius equals the upload's bit for bit (so the median, the big
+ *     list, r_max, c0, -r^2, 1/r and the Schlick terms stay valid);
+ *   - for every body whose r * r is finite, "all three centre coordinates are
+ *     finite" is what it was at the upload: a body in the tree or the big list
+ *     cannot leave it, one left out for its centre cannot join; a body left
+ *     out for its radius may have any centre;
+ *   - hip_stream is a stream of ds's device.
+ * The scene keeps a host copy of the upload's spheres to check this.
+ *
+ * Tables: geo[i] and its pair-interleaved copy get body i's new centre (and
+ * the same -r^2); sph[i] its new centre, the 1/r lane untouched.  Every leaf
+ * record slot that holds a body (the tree's leaves and the big bodies') gets
+ * that body's x, y, z; w, the pads, the indices, materials and kinds are not
+ * written.
+ * Per tree k in {0, 1, 2}: centre and radius come by the build's own formula
+ * over the tree's bodies (the centre of their box; the farthest surface from
+ * it, in double, x (1 + 1e-6) + 1e-6), on the host inside the call: they are
+ * launch arguments, stored in ds on return, so a launch enqueued after the
+ * call carries the new ones and one enqueued before it carried the old.
+ * Per tree k, node and child: B = the union over the bodies under that child
+ * of the body's box (per axis c -+ |r|, one fp32 operation, then one step
+ * outward); each stored bound is float(double(B.lo) - double(centre)) stepped
+ * once towards -inf, the max plane likewise towards +inf, the third pair a
+ * copy of the first.  A tree without bodies has B = the point 0 for both root
+ * children; a tree of one leaf has that leaf under both.  Child refs are not
+ * written.  Min and max are exact, so the bytes do not depend on the order of
+ * evaluation: an update with the upload's own spheres changes no byte, and
+ * the device's bytes are rt_tree_refit_host's.
+ *
+ * Ordering: the work is enqueued on hip_stream and the call does not wait for
+ * it; sphere may be reused as soon as the call returns (the scene copies it to
+ * page-locked staging of its own; the fifth update in flight waits for the
+ * first's copy).  Work on the same stream sees the scene before or after the
+ * update, by its place in the stream.  Work already enqueued on *other*
+ * streams that reads this scene races with the update, as work on another
+ * stream does with rt_accum's buffers: order it yourself.  Calls on one scene
+ * are not to run concurrently with one another or with launches on it from
+ * other threads.  A failed device call leaves ds's host scalars at their old
+ * values.  The tile-cost records of the adaptive order (rt_set_schedule), the
+ * scene's id and its allocations are kept.
+ * To know: the refitted tree is as tight as its topology allows, not as a
+ * fresh build would be; rt_tree_cost_host tells how far it has loosened.  A
+ * change of radius, material, kind or body count needs a fresh upload. */
+int rt_scene_update(rt_dscene* ds, const float* sphere, void* hip_stream);
+
+/* One tree of a scene as the device holds it: blob = nodes | pairs | pidx.
+ * Nodes are 80 bytes: the two child boxes as x[6], y[6], z[6] floats -- per
+ * axis (min0, min1, max0, max1, min0, min1), relative to center -- and two int
+ * child refs (>= 0 an inner node: its index, or for the 4-body tree its byte
+ * offset; < 0 a leaf: ~ its first pair).  Pairs are 8 floats (x0 x1 y0 y1 z0 z1
+ * w0 w1, w = -r^2, +inf for a pad); a leaf is leaf_size / 2 consecutive pairs;
+ * the big bodies' n_big_leaves leaves start at pair big_pair0.  pidx holds two
+ * body indices per pair, idx_bytes each (4: int, -1 a pad; 2: u16, 0xffff a
+ * pad), padded to 16 bytes.  Offsets in bytes.  c0: the walk's padding term
+ * (3 x the tree bodies' largest |radius|). */
+typedef struct rt_tree_info {
+  int n_nodes, off_pairs, off_pidx, blob_bytes, big_pair0, n_big_leaves, depth, leaf_size, idx_bytes;
+  float center[3], radius, c0;
+} rt_tree_info;
+
+/* Host entries (plain C++, no device).  k = 0, 1, 2: the tree of 2-, 4- and
+ * 8-body leaves.
+ * rt_tree_build_host: exactly the blob rt_scene_upload uploads for tree k of
+ * the n bodies `sphere` (n x 4 floats), into blob (cap bytes), described in
+ * info.  RT_E_ARG on a NULL sphere (n > 0) or info, bad n or k; and when cap
+ * is too small (blob may then be NULL): info is filled, blob_bytes is the size
+ * needed, blob is not written. */
+int rt_tree_build_host(const float* sphere, int n, int k, void* blob, size_t cap, rt_tree_info* info);
+/* rt_scene_update's definition applied to a host blob in place, for one tree:
+ * sphere_at_upload is what the blob was built from, sphere_now the new
+ * spheres; info's center and radius are updated.  The same preconditions and
+ * errors, plus RT_E_ARG for an info or blob that is not a tree over n bodies;
+ * on an error the blob and info are unchanged. */
+int rt_tree_refit_host(void* blob, rt_tree_info* info, const float* sphere_at_upload, const float* sphere_now, int n);
+/* *cost = the sum over nodes and their two children of the child box's surface
+ * area 2 (dx dy + dy dz + dz dx), in double, in node order: the figure a
+ * surface-area build minimises; its ratio to the value at the upload tells
+ * how far refits have loosened a tree. */
+int rt_tree_cost_host(const void* blob, const rt_tree_info* info, double* cost);
+/* The device's counterparts (tests, tools): tree k of ds as it stands, and
+ * its blob copied to the host (cap >= info's blob_bytes) behind hip_stream's
+ * work: the call waits for the stream, then copies. */
+int rt_scene_tree_info(const rt_dscene* ds, int k, rt_tree_info* info);
+int rt_scene_tree_read(const rt_dscene* ds, int k, void* blob, size_t cap, void* hip_stream);
+
 /* Asynchronous: enqueue rt_quantize on hip_stream's device for n channels
  * already in HBM (d_lin: n floats, d_out: n bytes, device pointers): the same
  * bytes as rt_quantize for every float (NaN, infinities and denormals

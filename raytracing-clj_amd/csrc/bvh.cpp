@@ -29,6 +29,7 @@
 //   the big bodies' leaves follow the tree's in pairs / pidx (big_pair0,
 //   n_big_leaves)
 #include "bvh.h"
+#include "bvh_refit.h"
 
 #include <algorithm>
 #include <climits>
@@ -51,13 +52,13 @@ struct Box {
   }
 };
 
-// exact float box of a body, rounded outward
+// exact float box of a body, rounded outward: bvh_refit.h's, the text a refit runs
 Box body_box(const float* s) {
+  const RfBox r = rf_body_box(s);
   Box b;
-  const float r = std::fabs(s[3]);
   for (int k = 0; k < 3; ++k) {
-    b.lo[k] = std::nextafter(s[k] - r, -INFINITY);
-    b.hi[k] = std::nextafter(s[k] + r, INFINITY);
+    b.lo[k] = r.lo[k];
+    b.hi[k] = r.hi[k];
   }
   return b;
 }
@@ -194,6 +195,28 @@ struct Builder {
 
 }  // namespace
 
+// bounding sphere of the bodies prim[0 .. cnt) (centre of their box, radius to
+// the farthest surface): D = |O - centre| + radius bounds |oc| + r per ray;
+// r_max their largest |radius|.  Min and max only: any order of prim gives the
+// same bits.  The build's and a refit's (tree_blob.cpp).
+void bvh_bounds(const float* sph, const int* prim, int cnt, float* center, float* radius, float* r_max) {
+  Box all;
+  for (int j = 0; j < cnt; ++j) all.add(body_box(sph + 4 * prim[j]));
+  double bc[3] = {0, 0, 0}, br = 0, rmax = 0;
+  if (cnt > 0) {
+    for (int k = 0; k < 3; ++k) bc[k] = 0.5 * (double(all.lo[k]) + all.hi[k]);
+    for (int j = 0; j < cnt; ++j) {
+      const float* s = sph + 4 * prim[j];
+      const double dx = s[0] - bc[0], dy = s[1] - bc[1], dz = s[2] - bc[2];
+      br = std::max(br, std::sqrt(dx * dx + dy * dy + dz * dz) + std::fabs(s[3]));
+      rmax = std::max(rmax, double(std::fabs(s[3])));
+    }
+  }
+  for (int k = 0; k < 3; ++k) center[k] = static_cast<float>(bc[k]);
+  *radius = static_cast<float>(br * (1.0 + 1e-6)) + 1e-6f;
+  *r_max = static_cast<float>(rmax * (1.0 + 1e-6));
+}
+
 int bvh_build(const float* sph, int n, BvhHost* out, int leaf_size, bool sah) {
   *out = BvhHost{};
   if (leaf_size != 2 && leaf_size != 4 && leaf_size != 8) leaf_size = 2;
@@ -251,23 +274,7 @@ int bvh_build(const float* sph, int n, BvhHost* out, int leaf_size, bool sah) {
   std::sort(out->big.begin(), out->big.end());
   for (int i = 0; i < n; ++i)
     if (finite[i] && !is_big[i]) b.prim.push_back(i);
-  // bounding sphere of the tree's bodies (centre of their box, radius to the
-  // farthest surface): D = |O - centre| + radius bounds |oc| + r per ray
-  Box all;
-  for (int i : b.prim) all.add(body_box(sph + 4 * i));
-  double bc[3] = {0, 0, 0}, br = 0, rmax = 0;
-  if (!b.prim.empty()) {
-    for (int k = 0; k < 3; ++k) bc[k] = 0.5 * (double(all.lo[k]) + all.hi[k]);
-    for (int i : b.prim) {
-      const float* s = sph + 4 * i;
-      const double dx = s[0] - bc[0], dy = s[1] - bc[1], dz = s[2] - bc[2];
-      br = std::max(br, std::sqrt(dx * dx + dy * dy + dz * dz) + std::fabs(s[3]));
-      rmax = std::max(rmax, double(std::fabs(s[3])));
-    }
-  }
-  for (int k = 0; k < 3; ++k) out->center[k] = static_cast<float>(bc[k]);
-  out->radius = static_cast<float>(br * (1.0 + 1e-6)) + 1e-6f;
-  out->r_max = static_cast<float>(rmax * (1.0 + 1e-6));
+  bvh_bounds(sph, b.prim.data(), static_cast<int>(b.prim.size()), out->center, &out->radius, &out->r_max);
   // root is always node 0 with two children (a leaf-only tree gets a root)
   out->nodes.emplace_back();
   const int cnt = static_cast<int>(b.prim.size());
@@ -298,8 +305,8 @@ int bvh_build(const float* sph, int n, BvhHost* out, int leaf_size, bool sah) {
     float* ax[3] = {nd.x, nd.y, nd.z};
     for (int k = 0; k < 3; ++k)
       for (int c = 0; c < 2; ++c) {
-        ax[k][c] = std::nextafter(static_cast<float>(double(ax[k][c]) - out->center[k]), -INFINITY);
-        ax[k][2 + c] = std::nextafter(static_cast<float>(double(ax[k][2 + c]) - out->center[k]), INFINITY);
+        ax[k][c] = rf_down(rf_rel(ax[k][c], out->center[k]));
+        ax[k][2 + c] = rf_up(rf_rel(ax[k][2 + c], out->center[k]));
         ax[k][4 + c] = ax[k][c];
       }
   }

@@ -39,5 +39,7 @@ constexpr int kBvhBigMax = 8;
 
 // sah: surface-area-heuristic splits (else median splits)
 int bvh_build(const float* sphere, int n, BvhHost* out, int leaf_size = 2, bool sah = true);
+// centre, radius and r_max of BvhHost from the tree's bodies prim[0 .. cnt) (bvh.cpp)
+void bvh_bounds(const float* sphere, const int* prim, int cnt, float* center, float* radius, float* r_max);
 
 }  // namespace rtclj

@@ -109,7 +109,7 @@ RT_FH_FN void fh_test(const FhRay& r, float cx, float cy, float cz, float nr2, i
 // A body's entry in the scan's table from its (cx, cy, cz, r): the centre and
 // -r^2, the square rounded once.  The one construction: rt_scene_upload's
 // table and rt_ids_host's are both made here.
-inline void fh_geo(const float* sphere4, float* geo4) {
+RT_FH_FN void fh_geo(const float* sphere4, float* geo4) {
   const float r = sphere4[3];
   geo4[0] = sphere4[0], geo4[1] = sphere4[1], geo4[2] = sphere4[2];
   geo4[3] = -(r * r);

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "body_ids.h"
+#include "bvh_refit.h"
 #include "denoise.h"
 #include "first_hit.h"
 #include "rt_internal.h"
@@ -343,6 +344,38 @@ extern "C" int rt_body_motion(const rt_scene* cur, const rt_scene* prev, float* 
   const char* why = nullptr;
   const int rc = body_motion(cur, prev, out, &why);
   return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_body_motion: ") + (why ? why : "failed"));
+}
+
+// one of rt_scene_upload's trees on the host (bvh.cpp's build, tree_blob.cpp's layout)
+extern "C" int rt_tree_build_host(const float* sphere, int n, int k, void* blob, size_t cap, rt_tree_info* info) {
+  clear_error();
+  if (!info || n < 0 || (n > 0 && !sphere)) return set_error(RT_E_ARG, "rt_tree_build_host: NULL argument");
+  if (n > RT_MAX_SPHERES || k < 0 || k > 2) return set_error(RT_E_ARG, "rt_tree_build_host: bad n or k");
+  BvhHost bvh;
+  bvh_build(sphere, n, &bvh, 2 << k, bvh_sah_default());
+  std::vector<char> bytes;
+  tree_pack(bvh, k, &bytes, info);
+  if (!blob || cap < bytes.size())
+    return set_error(RT_E_ARG, "rt_tree_build_host: the blob needs " + std::to_string(bytes.size()) + " bytes");
+  std::memcpy(blob, bytes.data(), bytes.size());
+  return RT_OK;
+}
+
+// a refit on the host (bvh_refit.h's text, tree_blob.cpp's pass)
+extern "C" int rt_tree_refit_host(void* blob, rt_tree_info* info, const float* sphere_at_upload, const float* sphere_now,
+                                  int n) {
+  clear_error();
+  const char* why = nullptr;
+  const int rc = tree_refit(static_cast<char*>(blob), info, sphere_at_upload, sphere_now, n, &why);
+  return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_tree_refit_host: ") + (why ? why : "failed"));
+}
+
+extern "C" int rt_tree_cost_host(const void* blob, const rt_tree_info* info, double* cost) {
+  clear_error();
+  if (!blob || !info || !cost) return set_error(RT_E_ARG, "rt_tree_cost_host: NULL argument");
+  const char* why = nullptr;
+  const int rc = tree_cost(static_cast<const char*>(blob), *info, cost, &why);
+  return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_tree_cost_host: ") + (why ? why : "failed"));
 }
 
 extern "C" int rt_write_ppm(const char* path, const uint8_t* rgb, int width, int height) {

@@ -13,7 +13,9 @@
 // (denoise.h) and the rt_denoiser entries, then temporal accumulation's kernel
 // (temporal.h) and the rt_temporal entries close the file;
 // the body-id pass (body_ids.h, rt_launch_ids) stands behind the feature pass
-// and the motion-aware step beside rt_temporal_step.
+// and the motion-aware step beside rt_temporal_step;
+// rt_scene_update and the refit kernel (bvh_refit.h) are the last section
+// (DESIGN.md §3.11).
 #include "trace_kernel.h"
 #define RT_FIRST_HIT_KERNEL
 #include "first_hit.h"
@@ -23,6 +25,8 @@
 #include "temporal.h"
 #define RT_BODY_IDS_KERNEL
 #include "body_ids.h"
+#define RT_REFIT_KERNEL
+#include "bvh_refit.h"
 #include "variant_policy.h"
 #include "dev_buf.h"
 
@@ -505,11 +509,9 @@ static const void* variant_sweep(int v) { return v == policy::kCompact ? RT_KSW(
 static std::atomic<int> g_variant{0};
 // tile schedule: 0 = adaptive longest-first, 1 = dispatch order
 static std::atomic<int> g_schedule{0};
-// BVH build: surface-area splits (default) or median splits (RTCLJ_BVH=median, for A/B)
-static const bool g_bvh_sah = [] {
-  const char* e = std::getenv("RTCLJ_BVH");
-  return !(e && std::strcmp(e, "median") == 0);
-}();
+// BVH build: surface-area splits (default) or median splits (RTCLJ_BVH=median,
+// for A/B): tree_blob.cpp's bvh_sah_default
+static const bool g_bvh_sah = bvh_sah_default();
 #ifdef RTCLJ_DIAG
 // diagnostic build: RTCLJ_TIMELINE=1 records every launch's wave timeline
 static const bool g_timeline = [] {
@@ -599,6 +601,37 @@ struct DTree {
   int blob_f4, off_pairs, off_pidx, big_pair0, n_big_leaves, depth, n_nodes;
   float c[3], r;
   float c0;   // kPadRmax x the tree bodies' largest radius (bvh_pad.h)
+};
+
+// What rt_scene_update needs beyond the blobs (bvh_refit.h).  The host part is
+// derived once at the upload; the device buffers and the staging are made by
+// the first update, so a scene that is never updated pays for none of them.
+constexpr int kRefitSlots = 4;
+struct RefitState {
+  std::vector<float> sph0;          // the upload's spheres: the preconditions' yardstick
+  std::vector<int> bodies;          // the trees' bodies (one set for the three trees), ascending
+  std::vector<int> order[3], lvl[3];   // tree_levels
+  int empty = 0;                    // no body in the trees
+  DevBuf<float4> src;               // the new spheres on the device
+  DevBuf<int> d_order;              // order[0] | order[1] | order[2]
+  // page-locked staging the caller's array is copied to, a ring: a slot is
+  // reused once the copy out of it has run (its event)
+  float* pin[kRefitSlots] = {};
+  hipEvent_t ev[kRefitSlots] = {};
+  int next = 0;
+  bool ready = false;
+  std::mutex mu;
+  void release() {
+    for (int i = 0; i < kRefitSlots; ++i) {
+      if (ev[i]) (void)hipEventDestroy(ev[i]);
+      if (pin[i]) (void)hipHostFree(pin[i]);
+      ev[i] = nullptr;
+      pin[i] = nullptr;
+    }
+    src.reset();
+    d_order.reset();
+    ready = false;
+  }
 };
 
 // Adaptive tile schedule (rt_launch): per stream, the per-tile durations of
@@ -706,6 +739,7 @@ struct rt_dscene {
   bool unit_albedo;            // every lambertian/metal albedo channel within [-1, 1] (compact_ok)
   uint64_t uid;                // upload id (scene_uid): contexts name scenes by it, not by address
   mutable ScheduleSet sched;   // rt_launch's adaptive tile order
+  RefitState refit;            // rt_scene_update's
 };
 static std::atomic<uint64_t> g_scene_uid{0};
 uint64_t rtclj::scene_uid(const rt_dscene* ds) { return ds ? ds->uid : 0; }
@@ -834,40 +868,32 @@ extern "C" int rt_scene_upload(int device, const rt_scene* s, rt_dscene** out) {
     for (std::thread& t : th) t.join();
   }
   hipError_t e = hipMalloc(&d->geo, n_pad * sizeof(float4));
-  // blob = nodes | pairs | pidx
+  // blob = nodes | pairs | pidx (tree_blob.cpp's tree_pack: rt_tree_build_host's bytes)
   for (int k = 0; k < 3 && e == hipSuccess; ++k) {
-    BvhHost& bvh = bvhs[k];
-    const size_t nb = bvh.nodes.size() * sizeof(BvhNode);
-    const size_t pb = bvh.pairs.size() * sizeof(float);
-    // body indices: u16 for the 8-body-leaf tree (RT_MAX_SPHERES < 65535; a
-    // pad's -1 -> 0xffff, never a candidate), int for the others
-    const size_t isz = k == 2 ? sizeof(uint16_t) : sizeof(int);
-    std::vector<uint16_t> pidx16(bvh.pidx.size());
-    for (size_t i = 0; i < pidx16.size(); ++i) pidx16[i] = static_cast<uint16_t>(bvh.pidx[i]);
-    const size_t ib = ((bvh.pidx.size() * isz + 15) / 16) * 16;
-    std::vector<char> blob(nb + pb + ib, 0);
-    if (k == 1)   // 4-body tree: inner-child refs as byte offsets (< 65536 while it fits LDS: u16 stack)
-      for (BvhNode& nd : bvh.nodes)
-        for (int& c : nd.child)
-          if (c >= 0) c *= static_cast<int>(sizeof(BvhNode));
-    std::memcpy(blob.data(), bvh.nodes.data(), nb);
-    std::memcpy(blob.data() + nb, bvh.pairs.data(), pb);
-    if (k == 2) std::memcpy(blob.data() + nb + pb, pidx16.data(), pidx16.size() * sizeof(uint16_t));
-    else std::memcpy(blob.data() + nb + pb, bvh.pidx.data(), bvh.pidx.size() * sizeof(int));
+    std::vector<char> blob;
+    rt_tree_info ti;
+    tree_pack(bvhs[k], k, &blob, &ti);
     DTree& t = d->tree[k];
     t.blob_f4 = static_cast<int>(blob.size() / 16);
-    t.off_pairs = static_cast<int>(nb);
-    t.off_pidx = static_cast<int>(nb + pb);
-    t.big_pair0 = bvh.big_pair0;
-    t.n_big_leaves = bvh.n_big_leaves;
-    t.depth = bvh.depth;
-    t.n_nodes = static_cast<int>(bvh.nodes.size());
-    for (int j = 0; j < 3; ++j) t.c[j] = bvh.center[j];
-    t.r = bvh.radius;
-    t.c0 = kPadRmax * bvh.r_max;
+    t.off_pairs = ti.off_pairs;
+    t.off_pidx = ti.off_pidx;
+    t.big_pair0 = ti.big_pair0;
+    t.n_big_leaves = ti.n_big_leaves;
+    t.depth = ti.depth;
+    t.n_nodes = ti.n_nodes;
+    for (int j = 0; j < 3; ++j) t.c[j] = ti.center[j];
+    t.r = ti.radius;
+    t.c0 = ti.c0;
+    // what a refit walks (rt_scene_update), from the bytes the device gets
+    tree_levels(blob.data(), ti, &d->refit.order[k], &d->refit.lvl[k]);
+    if (k == 0) {
+      d->refit.bodies = tree_bodies(blob.data(), ti);
+      d->refit.empty = d->refit.bodies.empty();
+    }
     e = hipMalloc(&t.blob, blob.size());
     if (e == hipSuccess) e = hipMemcpy(t.blob, blob.data(), blob.size(), hipMemcpyHostToDevice);
   }
+  if (n > 0) d->refit.sph0.assign(s->sphere, s->sphere + 4 * static_cast<size_t>(n));
   if (e == hipSuccess) e = hipMalloc(&d->geo2, n_pad * sizeof(float4));
   if (e == hipSuccess) e = hipMemcpy(d->geo2, geo2.data(), n_pad * sizeof(float4), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc(&d->sph, cnt * sizeof(float4));
@@ -902,6 +928,7 @@ extern "C" int rt_scene_free(rt_dscene* d) {
     if (t.blob) (void)hipFree(t.blob);
   }
   d->sched.release();
+  d->refit.release();
   if (d->sph) (void)hipFree(d->sph);
   if (d->mat) (void)hipFree(d->mat);
   if (d->kind) (void)hipFree(d->kind);
@@ -2574,3 +2601,144 @@ extern "C" int rt_debug_waves(int device, uint64_t* out, size_t n_waves) {
   return static_cast<int>(n_waves);
 }
 
+// ---- rt_scene_update (rt.h, bvh_refit.h) -------------------------------------
+// (The last section of the file, and refit_kernel a template, on purpose: a
+// template's code is emitted where it is first instantiated, so the refit
+// kernel follows every other kernel in the code object and none of them moves.)
+static rt_tree_info tree_info_of(const rt_dscene& ds, int k) {
+  const DTree& t = ds.tree[k];
+  rt_tree_info ti{};
+  ti.n_nodes = t.n_nodes;
+  ti.off_pairs = t.off_pairs;
+  ti.off_pidx = t.off_pidx;
+  ti.blob_bytes = t.blob_f4 * 16;
+  ti.big_pair0 = t.big_pair0;
+  ti.n_big_leaves = t.n_big_leaves;
+  ti.depth = t.depth;
+  ti.leaf_size = 2 << k;
+  ti.idx_bytes = k == 2 ? 2 : 4;
+  for (int j = 0; j < 3; ++j) ti.center[j] = t.c[j];
+  ti.radius = t.r;
+  ti.c0 = t.c0;
+  return ti;
+}
+
+static int stream_on_device(const std::string& me, hipStream_t stream, int device) {
+  if (!stream) return RT_OK;
+  hipDevice_t sdev = 0;
+  if (hipStreamGetDevice(stream, &sdev) == hipSuccess && static_cast<int>(sdev) != device)
+    return set_error(RT_E_ARG, me + ": the stream is on device " + std::to_string(static_cast<int>(sdev)) +
+                                   ", the scene on device " + std::to_string(device));
+  return RT_OK;
+}
+
+extern "C" int rt_scene_tree_info(const rt_dscene* ds, int k, rt_tree_info* info) {
+  clear_error();
+  if (!ds || !info) return set_error(RT_E_ARG, "rt_scene_tree_info: NULL argument");
+  if (k < 0 || k > 2) return set_error(RT_E_ARG, "rt_scene_tree_info: k must be 0, 1 or 2");
+  *info = tree_info_of(*ds, k);
+  return RT_OK;
+}
+
+extern "C" int rt_scene_tree_read(const rt_dscene* ds, int k, void* blob, size_t cap, void* hip_stream) {
+  clear_error();
+  const std::string me("rt_scene_tree_read");
+  if (!ds || !blob) return set_error(RT_E_ARG, me + ": NULL argument");
+  if (k < 0 || k > 2) return set_error(RT_E_ARG, me + ": k must be 0, 1 or 2");
+  const size_t bytes = static_cast<size_t>(ds->tree[k].blob_f4) * 16;
+  if (cap < bytes) return set_error(RT_E_ARG, me + ": the blob needs " + std::to_string(bytes) + " bytes");
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (const int rc = stream_on_device(me, stream, ds->device)) return rc;
+  HIP_TRY(hipSetDevice(ds->device));
+  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipMemcpy(blob, ds->tree[k].blob, bytes, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+// the first update's allocations: the spheres' device copy, the level orders,
+// the staging ring
+static int refit_prepare(rt_dscene& d) {
+  RefitState& rf = d.refit;
+  if (rf.ready) return RT_OK;
+  hipError_t e = rf.src.alloc(static_cast<size_t>(d.n));
+  std::vector<int> all;
+  for (int k = 0; k < 3; ++k) all.insert(all.end(), rf.order[k].begin(), rf.order[k].end());
+  if (e == hipSuccess) e = rf.d_order.alloc(all.size());
+  if (e == hipSuccess) e = hipMemcpy(rf.d_order.p, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice);
+  for (int i = 0; i < kRefitSlots && e == hipSuccess; ++i) {
+    e = hipHostMalloc(reinterpret_cast<void**>(&rf.pin[i]), 4 * sizeof(float) * static_cast<size_t>(d.n), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&rf.ev[i], hipEventDisableTiming);
+  }
+  if (e != hipSuccess) {
+    rf.release();
+    return hip_fail(e, "rt_scene_update");
+  }
+  rf.ready = true;
+  return RT_OK;
+}
+
+extern "C" int rt_scene_update(rt_dscene* ds, const float* sphere, void* hip_stream) {
+  clear_error();
+  const std::string me("rt_scene_update");
+  if (!ds || (!sphere && ds->n > 0)) return set_error(RT_E_ARG, me + ": NULL argument");
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (const int rc = stream_on_device(me, stream, ds->device)) return rc;
+  RefitState& rf = ds->refit;
+  std::lock_guard<std::mutex> lk(rf.mu);
+  const int n = ds->n;
+  if (const char* why = refit_spheres_error(rf.sph0.data(), sphere, n)) return set_error(RT_E_ARG, me + ": " + why);
+  if (n == 0) return RT_OK;   // (no body: no table entry, and the trees' boxes are the point 0)
+  // the launch arguments of the trees: one body set, so one centre and radius
+  float c[3], r = 0.0f, r_max = 0.0f;
+  bvh_bounds(sphere, rf.bodies.data(), static_cast<int>(rf.bodies.size()), c, &r, &r_max);
+  HIP_TRY(hipSetDevice(ds->device));
+  if (const int rc = refit_prepare(*ds)) return rc;
+  RefitArgs a{};
+  size_t max_nodes = 1, at = 0;
+  for (int k = 0; k < 3; ++k) {
+    const DTree& t = ds->tree[k];
+    RefitTreeArgs& ta = a.t[k];
+    const int n_levels = static_cast<int>(rf.lvl[k].size()) - 1;
+    if (n_levels > kRefitLevels) return set_error(RT_E_ARG, me + ": a tree is deeper than the build allows");
+    ta.blob = reinterpret_cast<char*>(t.blob);
+    ta.order = rf.d_order.p + at;
+    at += rf.order[k].size();
+    ta.off_pairs = t.off_pairs;
+    ta.off_pidx = t.off_pidx;
+    ta.idx_bytes = k == 2 ? 2 : 4;
+    ta.leaf_pairs = 1 << k;
+    ta.n_nodes = t.n_nodes;
+    ta.n_pairs = (t.off_pidx - t.off_pairs) / 32;
+    ta.ref_div = k == 1 ? static_cast<int>(sizeof(BvhNode)) : 1;
+    ta.empty = rf.empty;
+    ta.n_levels = n_levels;
+    for (int l = 0; l <= n_levels; ++l) ta.lvl[l] = rf.lvl[k][l];
+    for (int j = 0; j < 3; ++j) ta.c[j] = c[j];
+    max_nodes = std::max(max_nodes, static_cast<size_t>(t.n_nodes));
+  }
+  a.src = rf.src.p;
+  a.geo = ds->geo;
+  a.geo2 = reinterpret_cast<float*>(ds->geo2);
+  a.sph = ds->sph;
+  a.n = n;
+  const size_t lds = 6 * sizeof(float) * max_nodes;
+  if (lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&refit_kernel<kRefitThreads>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                static_cast<int>(lds)));
+  // the caller's array into a staging slot whose last copy has run, then
+  // stream-ordered: the copy to the device, the kernel
+  const int slot = rf.next;
+  HIP_TRY(hipEventSynchronize(rf.ev[slot]));
+  const size_t bytes = 4 * sizeof(float) * static_cast<size_t>(n);
+  std::memcpy(rf.pin[slot], sphere, bytes);
+  HIP_TRY(hipMemcpyAsync(rf.src.p, rf.pin[slot], bytes, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(rf.ev[slot], stream));
+  rf.next = (slot + 1) % kRefitSlots;
+  const unsigned blocks = 3u + static_cast<unsigned>((n + kRefitThreads - 1) / kRefitThreads);
+  HIP_TRY(enqueue(refit_kernel<kRefitThreads>, dim3(blocks), dim3(kRefitThreads), lds, stream, a));
+  for (int k = 0; k < 3; ++k) {
+    for (int j = 0; j < 3; ++j) ds->tree[k].c[j] = c[j];
+    ds->tree[k].r = r;
+  }
+  return RT_OK;
+}

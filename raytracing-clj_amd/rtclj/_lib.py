@@ -86,6 +86,15 @@ class rt_temporal_opts(C.Structure):
     _fields_ = [("max_history", C.c_int), ("sigma_z", C.c_float), ("normal_min", C.c_float)]
 
 
+class rt_tree_info(C.Structure):
+    _fields_ = [("n_nodes", C.c_int), ("off_pairs", C.c_int), ("off_pidx", C.c_int), ("blob_bytes", C.c_int),
+                ("big_pair0", C.c_int), ("n_big_leaves", C.c_int), ("depth", C.c_int), ("leaf_size", C.c_int),
+                ("idx_bytes", C.c_int), ("center", C.c_float * 3), ("radius", C.c_float), ("c0", C.c_float)]
+
+    def as_dict(self):
+        return {f: (tuple(getattr(self, f)) if f == "center" else getattr(self, f)) for f, _ in self._fields_}
+
+
 # rt_temporal_step's defaults (include/rt.h)
 TEMPORAL_DEFAULTS = dict(max_history=32, sigma_z=0.1, normal_min=0.9)
 
@@ -187,6 +196,14 @@ SIGNATURES = {
                               C.POINTER(C.c_int32)]),
     "rt_ids_occupancy": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rt_body_motion": (C.c_int, [C.POINTER(rt_scene), C.POINTER(rt_scene), C.POINTER(C.c_float)]),
+    "rt_scene_update": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_void_p]),
+    "rt_tree_build_host": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                     C.POINTER(rt_tree_info)]),
+    "rt_tree_refit_host": (C.c_int, [C.c_void_p, C.POINTER(rt_tree_info), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                     C.c_int]),
+    "rt_tree_cost_host": (C.c_int, [C.c_void_p, C.POINTER(rt_tree_info), C.POINTER(C.c_double)]),
+    "rt_scene_tree_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(rt_tree_info)]),
+    "rt_scene_tree_read": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rt_quantize_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rt_set_variant": (C.c_int, [C.c_int]),
     "rt_resolve_variant": (C.c_int, [C.c_void_p]),
@@ -215,7 +232,9 @@ ADDITIVE = {"rt_prepare", "rt_render_u8", "rt_quantize_device", "rt_render_submi
             "rt_denoiser_create", "rt_denoiser_free", "rt_denoise", "rt_denoise_profile",
             "rt_denoise_host", "rt_temporal_create", "rt_temporal_free", "rt_temporal_reset", "rt_temporal_frames",
             "rt_temporal_step", "rt_temporal_read", "rt_temporal_host", "rt_temporal_step_motion",
-            "rt_temporal_host_motion", "rt_launch_ids", "rt_ids_host", "rt_ids_occupancy", "rt_body_motion"}
+            "rt_temporal_host_motion", "rt_launch_ids", "rt_ids_host", "rt_ids_occupancy", "rt_body_motion",
+            "rt_scene_update", "rt_tree_build_host", "rt_tree_refit_host", "rt_tree_cost_host", "rt_scene_tree_info",
+            "rt_scene_tree_read"}
 
 RT_FEAT_CHANNELS = 8   # rt_feat_resolve's floats per pixel: albedo rgb, normal xyz, depth, coverage
 

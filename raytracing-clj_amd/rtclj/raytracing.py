@@ -26,7 +26,8 @@ import numpy as np
 from . import hittable, material
 from ._lib import (DENOISE_DEFAULTS, RT_DIELECTRIC, RT_FEAT_CHANNELS, RT_LAMBERTIAN, RT_METAL, RT_NONE,
                    TEMPORAL_DEFAULTS, RTError, check, dptr, fptr, i64ptr, iptr, lib, rt_adapt_opts, rt_camera,
-                   i32ptr, rt_denoise_opts, rt_params, rt_scene, rt_stats, rt_temporal_opts, u8ptr, u32ptr, u64ptr)
+                   i32ptr, rt_denoise_opts, rt_params, rt_scene, rt_stats, rt_temporal_opts, rt_tree_info, u8ptr, u32ptr,
+                   u64ptr)
 
 # ---- scene (raytracing.clj:63-78) --------------------------------------------
 hittables = [
@@ -900,12 +901,158 @@ def body_motion(cur_scene, prev_scene, library=None) -> np.ndarray:
     return out
 
 
+def _spheres(scene) -> np.ndarray:
+    if isinstance(scene, Scene):
+        return scene.sphere
+    if isinstance(scene, np.ndarray):
+        return np.ascontiguousarray(scene, np.float32).reshape(-1, 4)
+    return Scene.from_bodies(scene).sphere
+
+
+def tree_build_host(scene, k: int, library=None):
+    """rt_tree_build_host (include/rt.h): tree k (0, 1, 2: leaves of 2, 4, 8
+    bodies) of a scene (a Scene, a list of bodies or an (n, 4) array of
+    spheres) as rt_scene_upload uploads it, built on the host.  Returns
+    (rt_tree_info, uint8 array of info.blob_bytes)."""
+    dll = library if library is not None else lib
+    sph = _spheres(scene)
+    info = rt_tree_info()
+    dll.rt_tree_build_host(fptr(sph), len(sph), int(k), None, 0, C.byref(info))   # (the size: RT_E_ARG, info filled)
+    blob = np.zeros(max(info.blob_bytes, 0), np.uint8)
+    code = dll.rt_tree_build_host(fptr(sph), len(sph), int(k), blob.ctypes.data_as(C.c_void_p), blob.size,
+                                  C.byref(info))
+    if code < 0:
+        raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+    return info, blob
+
+
+def tree_refit_host(info: rt_tree_info, blob: np.ndarray, scene_at_upload, scene_now, library=None):
+    """rt_tree_refit_host (include/rt.h): the tree (info, blob) built from
+    scene_at_upload, refitted to scene_now's spheres on the host -- the bytes
+    rt_scene_update leaves on the device.  Returns a new (info, blob); the
+    arguments are not written.  RTError (RT_E_ARG) on a changed radius or a
+    centre whose finiteness changed."""
+    dll = library if library is not None else lib
+    s0, s1 = _spheres(scene_at_upload), _spheres(scene_now)
+    if len(s0) != len(s1):
+        raise ValueError("tree_refit_host: the scenes' body counts differ")
+    out_info = rt_tree_info.from_buffer_copy(info)
+    out = np.array(blob, np.uint8, copy=True)
+    if out.size != info.blob_bytes:
+        raise ValueError("tree_refit_host: blob is not info.blob_bytes long")
+    code = dll.rt_tree_refit_host(out.ctypes.data_as(C.c_void_p), C.byref(out_info), fptr(s0), fptr(s1), len(s0))
+    if code < 0:
+        raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+    return out_info, out
+
+
+def tree_cost(info: rt_tree_info, blob: np.ndarray, library=None) -> float:
+    """rt_tree_cost_host (include/rt.h): the sum of the child boxes' surface
+    areas; its ratio to the value at the upload tells how far refits have
+    loosened a tree."""
+    dll = library if library is not None else lib
+    blob = np.ascontiguousarray(blob, np.uint8)
+    if blob.size != info.blob_bytes:
+        raise ValueError("tree_cost: blob is not info.blob_bytes long")
+    cost = C.c_double()
+    code = dll.rt_tree_cost_host(blob.ctypes.data_as(C.c_void_p), C.byref(info), C.byref(cost))
+    if code < 0:
+        raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+    return cost.value
+
+
+class DeviceScene:
+    """A scene on a device (rt_scene_upload) that follows its bodies:
+    update(scene) moves them in place (rt_scene_update: same body count,
+    radii, kinds and materials; the trees are refitted on the device, in
+    stream order, without waiting), tree(k) reads a tree back.  `handle` is the
+    rt_dscene* the launch entries take.  A context manager; free() on exit."""
+
+    def __init__(self, scene=None, device: int = 0, library=None):
+        self._dll = library if library is not None else lib
+        self.device = int(device)
+        self.handle = C.c_void_p()
+        self.n = 0
+        if scene is not None:
+            self.upload(scene)
+
+    def _ok(self, code):
+        if code < 0:
+            raise RTError(code, self._dll.rt_last_error().decode(errors="replace"))
+        return code
+
+    def upload(self, scene):
+        """A fresh upload (the trees built on the host) in place of what it holds."""
+        sc = scene if isinstance(scene, Scene) else Scene.from_bodies(scene)
+        self.free()
+        self._ok(self._dll.rt_scene_upload(self.device, C.byref(sc.c), C.byref(self.handle)))
+        self.n = len(sc)
+        return self
+
+    def update(self, scene, stream=None):
+        """rt_scene_update with scene's spheres (a Scene, a list of bodies or an
+        (n, 4) array), enqueued on `stream` (a HIP stream address; None: the
+        default stream).  The array may be reused at once."""
+        if not self.handle:
+            raise RuntimeError("DeviceScene.update: nothing uploaded")
+        sph = _spheres(scene)
+        if len(sph) != self.n:
+            raise ValueError("DeviceScene.update: the body count differs from the upload's")
+        self._ok(self._dll.rt_scene_update(self.handle, fptr(sph) if self.n else None,
+                                           C.c_void_p(stream) if stream else None))
+        return self
+
+    def tree_info(self, k: int) -> rt_tree_info:
+        info = rt_tree_info()
+        self._ok(self._dll.rt_scene_tree_info(self.handle, int(k), C.byref(info)))
+        return info
+
+    def tree(self, k: int, stream=None):
+        """(rt_tree_info, uint8 array): tree k as the device holds it behind
+        `stream`'s work (rt_scene_tree_read: waits for the stream)."""
+        info = self.tree_info(k)
+        blob = np.zeros(info.blob_bytes, np.uint8)
+        self._ok(self._dll.rt_scene_tree_read(self.handle, int(k), blob.ctypes.data_as(C.c_void_p), blob.size,
+                                              C.c_void_p(stream) if stream else None))
+        return info, blob
+
+    def free(self):
+        if self.handle:
+            self._dll.rt_scene_free(self.handle)
+        self.handle = C.c_void_p()
+        self.n = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                self.free()
+        except Exception:   # (interpreter shutdown: the library may be gone)
+            pass
+
+
+def _same_but_centres(a: Scene, b: Scene) -> bool:
+    """Whether rt_scene_update can turn a's upload into b: the radii, kinds and
+    materials agree bit for bit (rt_body_motion's test for "the same body")."""
+    return (len(a) == len(b) and a.sphere[:, 3].tobytes() == b.sphere[:, 3].tobytes()
+            and a.kind.tobytes() == b.kind.tobytes() and a.mat.tobytes() == b.mat.tobytes())
+
+
 def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max_depth: int = 50, seed: int = 1,
-                     flags: int = 0, library=None, temporal=None, stages: bool = False, **opts):
+                     flags: int = 0, library=None, temporal=None, stages: bool = False, refit: bool = False, **opts):
     """render_sequence for bodies that move: one Scene per frame (all with the
     same body count), zipped with `cameras`; a generator that yields float32
     (height, width, 3) per frame, on device 0.  Per frame f: the scene's upload
-    (rt_scene_upload builds its trees on the host; they are not refitted), two
+    (rt_scene_upload builds its trees on the host; with `refit` only frame 0
+    is uploaded and every later frame is an rt_scene_update, which refits the
+    trees on the device -- a frame whose radii, kinds or materials differ from
+    frame 0's, or whose update is refused, is uploaded afresh; the bits are the
+    same either way, a refitted tree only costs time as it loosens), two
     accumulators of spp / 2 samples each from sample index f * spp, the
     first-hit features of all spp, the body ids (rt_launch_ids), body_motion
     against the previous frame's scene (frame 0: no displacement), the
@@ -940,14 +1087,22 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
     shape = rt_params(width=width, height=height, row_begin=0, row_end=height, spp=0, max_depth=max_depth, seed=seed,
                       flags=flags)
     ds, acc, ft = C.c_void_p(), [C.c_void_p(), C.c_void_p()], C.c_void_p()
-    prev_sc = None
+    prev_sc = first_sc = None
     try:
         with Temporal(width, height, library=library) as tp, Denoiser(width, height, library=library) as dn:
             for f, (scene, cam) in enumerate(zip(scenes, cameras)):
                 sc = scene if isinstance(scene, Scene) else Scene.from_bodies(scene)
                 if prev_sc is not None and len(sc) != len(prev_sc):
                     raise ValueError("render_animation: every scene must have the same body count")
-                ok(dll.rt_scene_upload(0, C.byref(sc.c), C.byref(ds)))
+                if refit and ds and _same_but_centres(first_sc, sc) and \
+                        dll.rt_scene_update(ds, fptr(sc.sphere) if len(sc) else None, None) >= 0:
+                    pass   # (moved in place, in the NULL stream's order)
+                else:
+                    if ds:   # (refit: a frame rt_scene_update cannot reach)
+                        ok(dll.rt_scene_free(ds))
+                        ds = C.c_void_p()
+                    ok(dll.rt_scene_upload(0, C.byref(sc.c), C.byref(ds)))
+                    first_sc = sc
                 if f == 0:
                     for a in acc:
                         ok(dll.rt_accum_create(ds, C.byref(shape), C.byref(a)))
@@ -975,8 +1130,9 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
                         n_bodies=len(sc), **topts)
                 dn.run(d_acc[0].data_ptr(), d_acc[1].data_ptr(), d_feat.data_ptr(), d_out.data_ptr(), **opts)
                 torch.cuda.synchronize(dev)
-                ok(dll.rt_scene_free(ds))
-                ds = C.c_void_p()
+                if not refit:
+                    ok(dll.rt_scene_free(ds))
+                    ds = C.c_void_p()
                 prev_sc = sc
                 out = d_out.cpu().numpy().reshape(height, width, 3)
                 if stages:
@@ -1171,4 +1327,4 @@ if __name__ == "__main__":  # python -m rtclj.raytracing [spp] [depth]
 
 
 __all__ = ["hittables", "REFERENCE_CAMERA", "image_height", "flatten", "flatten64", "Scene", "camera", "render", "Progressive", "Adaptive", "pass_sizes",
-           "Features", "denoise_host", "Denoiser", "render_denoised", "temporal_host", "Temporal", "render_sequence", "ids_host", "body_ids_into", "body_motion", "render_animation", "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]
+           "Features", "denoise_host", "Denoiser", "render_denoised", "temporal_host", "Temporal", "render_sequence", "ids_host", "body_ids_into", "body_motion", "tree_build_host", "tree_refit_host", "tree_cost", "DeviceScene", "render_animation", "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]

@@ -1,0 +1,380 @@
+"""Refitting a scene's trees on the host (include/rt.h: rt_tree_build_host,
+rt_tree_refit_host, rt_tree_cost_host; no GPU needed): the refit bit for bit
+against a NumPy restatement of rt.h's definition for all three trees, the
+identity refit, the refitted boxes against a rebuild's body boxes, centre and
+radius against a fresh build, the argument errors, the cost, the outward
+rounding against np.nextafter through the host entry, the stand-alone
+sanitizer program and the presence of the new entries.
+
+The scenes, motions and the restatement are shared with tests/test_gpu_refit.py.
+"""
+import ctypes as C
+import functools
+import json
+import re
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+ROOT = Path(__file__).resolve().parent.parent
+TOOL = ROOT / "raytracing-clj_amd" / "lib" / "refit_check"
+F = np.float32
+INF = F(np.inf)
+TINY = np.nextafter(F(0), F(1))          # the smallest subnormal
+REFIT_FUNCS = ("rt_scene_update", "rt_tree_build_host", "rt_tree_refit_host", "rt_tree_cost_host", "rt_scene_tree_info",
+               "rt_scene_tree_read")
+# the smallest cover grid whose 4-body tree has three levels of nodes and a big
+# body (asserted by test_the_cover_scene_has_levels_and_a_big_body)
+COVER_G = 3
+SCENES = ("reference", "cover", "nonfinite_few", "nonfinite_64", "nonfinite_65", "nonfinite_80", "neg_radius_field",
+          "bubble_negative_radius")
+MOTIONS = ("jitter", "carried", "plane")
+
+
+# ---- scenes and motions ----------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def scene(name):
+    from rtclj import scenes
+    if name == "reference":
+        return scenes.reference()
+    if name.startswith("cover"):      # "cover": the small one; "cover11": the benchmark's
+        return scenes.cover(COVER_G if name == "cover" else int(name[5:]))
+    import edge_scenes
+    return edge_scenes.case(name)[0]
+
+
+def in_tree_or_big(sph):
+    """bvh.cpp's `finite`: the bodies of the tree and of the big list."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.isfinite(sph[:, :3]).all(axis=1) & np.isfinite(sph[:, 3] * sph[:, 3])
+
+
+class Tree:
+    """A blob taken apart (rt.h, rt_tree_info)."""
+
+    def __init__(self, info, blob):
+        self.info, self.blob = info, np.array(blob, np.uint8, copy=True)
+        n, lp = info.n_nodes, info.leaf_size // 2
+        words = self.blob[:info.off_pairs].view(F).reshape(n, 20)
+        self.box = words[:, :18].reshape(n, 3, 6)             # per axis: min0 min1 max0 max1 min0 min1
+        self.child = words[:, 18:].view(np.int32)
+        self.n_pairs = (info.off_pidx - info.off_pairs) // 32
+        self.pairs = self.blob[info.off_pairs:info.off_pidx].view(F).reshape(self.n_pairs, 8)
+        raw = self.blob[info.off_pidx:info.off_pidx + 2 * self.n_pairs * info.idx_bytes]
+        if info.idx_bytes == 2:
+            idx = raw.view(np.uint16).astype(np.int64)
+            idx[idx == 0xffff] = -1
+        else:
+            idx = raw.view(np.int32).astype(np.int64)
+        self.pidx = idx
+        self.leaf_pairs = lp
+        self.ref_div = 80 if info.leaf_size == 4 else 1
+        self.bodies = np.unique(idx[:2 * info.big_pair0][idx[:2 * info.big_pair0] >= 0])
+        self.center = np.array(info.center, F)
+
+    def leaf_bodies(self, ref):
+        p = ~int(ref)
+        s = self.pidx[2 * p:2 * (p + self.leaf_pairs)]
+        return s[s >= 0]
+
+    def levels(self):
+        """Levels of nodes on the longest path from the root."""
+        depth = np.zeros(self.info.n_nodes, int)
+        for i in range(self.info.n_nodes):
+            for ref in self.child[i]:
+                if ref >= 0:
+                    depth[ref // self.ref_div] = depth[i] + 1
+        return int(depth.max()) + 1
+
+    def under(self, ref):
+        """The bodies under a child ref."""
+        if ref < 0:
+            return list(self.leaf_bodies(ref))
+        i = int(ref) // self.ref_div
+        return self.under(self.child[i][0]) + self.under(self.child[i][1])
+
+
+def body_boxes(sph):
+    """rt.h: per axis c -+ |r|, one fp32 operation, then one step outward."""
+    sph = np.asarray(sph, F)
+    r = np.abs(sph[:, 3:4])
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.nextafter(sph[:, :3] - r, -INF), np.nextafter(sph[:, :3] + r, INF)
+
+
+def bounds_np(sph, bodies):
+    """rt.h: the centre of the tree bodies' box and the farthest surface from
+    it, in double, x (1 + 1e-6) + 1e-6."""
+    sph = np.asarray(sph, F)
+    if len(bodies) == 0:
+        return np.zeros(3, F), F(0) + F(1e-6)
+    lo, hi = body_boxes(sph)
+    bc = 0.5 * (lo[bodies].min(axis=0).astype(np.float64) + hi[bodies].max(axis=0).astype(np.float64))
+    d = sph[bodies, :3].astype(np.float64) - bc
+    br = (np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]) + np.abs(sph[bodies, 3]).astype(np.float64)).max()
+    return bc.astype(F), F(br * (1.0 + 1e-6)) + F(1e-6)
+
+
+def refit_np(info, blob, sph_now):
+    """The definition of rt.h restated: the refitted blob's bytes, the centre
+    and the radius.  Float32 for the body boxes, float64 for the step to the
+    centre, unions by min and max, nodes from the last to the first (a node's
+    index is above its parent's)."""
+    t = Tree(info, blob)
+    sph = np.asarray(sph_now, F)
+    lo, hi = body_boxes(sph)
+    center, radius = bounds_np(sph, t.bodies)
+    for slot in np.nonzero(t.pidx >= 0)[0]:
+        t.pairs[slot >> 1, [slot & 1, 2 + (slot & 1), 4 + (slot & 1)]] = sph[t.pidx[slot], :3]
+    own = {}
+    for i in reversed(range(info.n_nodes)):
+        boxes = []
+        for c, ref in enumerate(t.child[i]):
+            if len(t.bodies) == 0:
+                b = (np.zeros(3, F), np.zeros(3, F))
+            elif ref < 0:
+                s = t.leaf_bodies(ref)
+                b = (lo[s].min(axis=0), hi[s].max(axis=0))
+            else:
+                b = own[int(ref) // t.ref_div]
+            boxes.append(b)
+            rel_lo = np.nextafter((b[0].astype(np.float64) - center.astype(np.float64)).astype(F), -INF)
+            rel_hi = np.nextafter((b[1].astype(np.float64) - center.astype(np.float64)).astype(F), INF)
+            t.box[i, :, c] = rel_lo
+            t.box[i, :, 2 + c] = rel_hi
+            t.box[i, :, 4 + c] = rel_lo
+        own[i] = (np.minimum(boxes[0][0], boxes[1][0]), np.maximum(boxes[0][1], boxes[1][1]))
+    return t.blob, center, radius
+
+
+def plane_x(centre_x, r):
+    """x with nextafter(fl(x - |r|), -inf) == centre_x, or None."""
+    r = np.abs(F(r))
+    want = np.nextafter(F(centre_x), INF)
+    x = F(want + r)
+    for cand in (x, np.nextafter(x, INF), np.nextafter(x, -INF)):
+        if F(cand - r) == want:
+            return cand
+    return None
+
+
+def moved(name, motion, seed=7):
+    """The scene's spheres under a motion (float32 (n, 4)): `jitter`, every
+    body of the tree and the big list displaced by a uniform draw of up to
+    +-0.5 per axis; `carried`, one tree body taken across the whole scene and
+    beyond; `plane`, every tree body that does not bound the tree on an axis
+    placed so that its box's min plane is the tree centre's coordinate (the stored bound of a
+    child that starts there is 0 stepped down: minus the smallest
+    subnormal)."""
+    from rtclj import raytracing as R
+    sc = scene(name)
+    sph = sc.sphere.copy()
+    ok = in_tree_or_big(sph)
+    t = Tree(*R.tree_build_host(sc, 0))
+    rng = np.random.default_rng(seed)
+    if motion == "jitter":
+        sph[ok, :3] += rng.uniform(-0.5, 0.5, (int(ok.sum()), 3)).astype(F)
+    elif motion == "carried":
+        lo, hi = body_boxes(sph)
+        j = t.bodies[len(t.bodies) // 2]
+        span = hi[t.bodies].max(axis=0) - lo[t.bodies].min(axis=0)
+        sph[j, :3] = hi[t.bodies].max(axis=0) + F(0.75) * span + F(3.0)
+    elif motion == "plane":
+        lo, hi = body_boxes(sph)
+        for ax in range(3):      # the first axis on which such a coordinate exists (none next to a centre of 0)
+            ends = (lo[t.bodies, ax] == lo[t.bodies, ax].min()) | (hi[t.bodies, ax] == hi[t.bodies, ax].max())
+            for j in t.bodies[~ends]:
+                x = plane_x(t.center[ax], sph[j, 3])
+                if x is not None and x + abs(sph[j, 3]) < hi[t.bodies, ax].max():
+                    sph[j, ax] = x
+            if not np.array_equal(sph, sc.sphere, equal_nan=True):
+                break
+    else:
+        raise ValueError(motion)
+    return sph
+
+
+# ---- 1. the NumPy restatement -----------------------------------------------------------
+@pytest.mark.parametrize("k", [0, 1, 2])
+@pytest.mark.parametrize("name", SCENES)
+def test_refit_equals_the_numpy_restatement(name, k):
+    from rtclj import raytracing as R
+    sc = scene(name)
+    info, blob = R.tree_build_host(sc, k)
+    planes = 0
+    for motion in MOTIONS:
+        sph = moved(name, motion)
+        assert not np.array_equal(sph, sc.sphere, equal_nan=True), motion
+        got_info, got = R.tree_refit_host(info, blob, sc, sph)
+        want, center, radius = refit_np(info, blob, sph)
+        assert got.tobytes() == want.tobytes(), (name, k, motion, int((got != want).sum()))
+        assert np.array(got_info.center, F).tobytes() == center.tobytes() and F(got_info.radius) == radius
+        if motion == "plane":
+            planes = int((Tree(got_info, got).box[:, :, :2].view(np.uint32) == 0x80000001).sum())
+    if name == "cover" and k == 0:
+        assert planes >= 1    # (a min plane on the centre was stored as minus the smallest subnormal)
+
+
+def test_the_cover_scene_has_levels_and_a_big_body():
+    from rtclj import raytracing as R
+    from rtclj import scenes
+    def ok(g):
+        t = Tree(*R.tree_build_host(scenes.cover(g), 1))
+        return t.levels() >= 3 and t.info.n_big_leaves >= 1
+    assert ok(COVER_G) and not any(ok(g) for g in range(1, COVER_G))
+    ref = Tree(*R.tree_build_host(scene("reference"), 1))
+    assert ref.info.n_big_leaves == 0 and ref.levels() == 1
+
+
+# ---- 2. identity ---------------------------------------------------------------------------
+@pytest.mark.parametrize("name", SCENES)
+def test_identity_refit_changes_nothing(name):
+    from rtclj import raytracing as R
+    sc = scene(name)
+    for k in range(3):
+        info, blob = R.tree_build_host(sc, k)
+        got_info, got = R.tree_refit_host(info, blob, sc, sc.sphere.copy())
+        assert got.tobytes() == blob.tobytes() and bytes(got_info) == bytes(info), (name, k)
+
+
+# ---- 3. against a rebuild ---------------------------------------------------------------------
+@pytest.mark.parametrize("name", SCENES)
+def test_refit_against_a_rebuild(name):
+    from rtclj import raytracing as R
+    sc = scene(name)
+    for motion in MOTIONS:
+        sph = moved(name, motion)
+        lo, hi = body_boxes(sph)
+        for k in range(3):
+            info, blob = R.tree_build_host(sc, k)
+            t = Tree(*R.tree_refit_host(info, blob, sc, sph))
+            fresh, _ = R.tree_build_host(sph, k)
+            # both are a function of the body set, and the set is the same
+            assert bytes(fresh)[36:] == bytes(t.info)[36:], (name, motion, k)     # center, radius, c0
+            c = t.center.astype(np.float64)
+            for i in range(t.info.n_nodes):
+                for ch, ref in enumerate(t.child[i]):
+                    s = t.under(ref)
+                    if not s:
+                        continue
+                    assert (c + t.box[i, :, ch] <= lo[s].astype(np.float64)).all(), (name, motion, k, i, ch)
+                    assert (c + t.box[i, :, 2 + ch] >= hi[s].astype(np.float64)).all(), (name, motion, k, i, ch)
+
+
+# ---- 4. errors -----------------------------------------------------------------------------------
+def test_errors_leave_the_blob_untouched():
+    import rtclj
+    from rtclj import raytracing as R
+    from rtclj._lib import RT_E_ARG, RTError, fptr, rt_tree_info
+    sc = scene("nonfinite_few")
+    ok = in_tree_or_big(sc.sphere)
+    body = int(np.nonzero(ok)[0][1])
+    left_for_centre = int(np.nonzero(~np.isfinite(sc.sphere[:, :3]).all(axis=1) & np.isfinite(sc.sphere[:, 3]))[0][0])
+    for k in range(3):
+        info, blob = R.tree_build_host(sc, k)
+        bad = []
+        s = sc.sphere.copy(); s[body, 3] = np.nextafter(s[body, 3], INF); bad.append(s)        # a changed radius
+        s = sc.sphere.copy(); s[body, 1] = np.nan; bad.append(s)                               # a tree body's centre NaN
+        s = sc.sphere.copy(); s[body, 2] = -np.inf; bad.append(s)
+        s = sc.sphere.copy(); s[left_for_centre, :3] = 0.25; bad.append(s)                     # one left out joins
+        for s in bad:
+            work, winfo = blob.copy(), rt_tree_info.from_buffer_copy(info)
+            code = rtclj.lib.rt_tree_refit_host(work.ctypes.data_as(C.c_void_p), C.byref(winfo), fptr(sc.sphere), fptr(s), len(sc))
+            assert code == RT_E_ARG and rtclj.lib.rt_last_error() != b""
+            assert work.tobytes() == blob.tobytes() and bytes(winfo) == bytes(info)
+            with pytest.raises(RTError):
+                R.tree_refit_host(info, blob, sc, s)
+        # a body left out for its radius may have any centre
+        s = sc.sphere.copy()
+        with np.errstate(over="ignore", invalid="ignore"):
+            free = np.nonzero(~np.isfinite(s[:, 3] * s[:, 3]))[0]
+        s[free, 0] = np.nan
+        s[free[0], :3] = 7.0
+        R.tree_refit_host(info, blob, sc, s)
+        # a cap too small: the needed size in info, nothing written
+        short = np.full(info.blob_bytes - 1, 0xa5, np.uint8)
+        need = rt_tree_info()
+        code = rtclj.lib.rt_tree_build_host(fptr(sc.sphere), len(sc), k, short.ctypes.data_as(C.c_void_p), short.size, C.byref(need))
+        assert code == RT_E_ARG and need.blob_bytes == info.blob_bytes and (short == 0xa5).all()
+    assert rtclj.lib.rt_tree_build_host(None, 3, 0, None, 0, C.byref(rt_tree_info())) == RT_E_ARG
+    assert rtclj.lib.rt_tree_build_host(fptr(sc.sphere), len(sc), 3, None, 0, C.byref(rt_tree_info())) == RT_E_ARG
+    assert rtclj.lib.rt_tree_refit_host(None, None, None, None, 0) == RT_E_ARG
+    assert rtclj.lib.rt_tree_cost_host(None, None, None) == RT_E_ARG
+    assert rtclj.lib.rt_scene_update(None, None, None) == RT_E_ARG
+    assert rtclj.lib.rt_scene_tree_info(None, 0, None) == RT_E_ARG
+    assert rtclj.lib.rt_scene_tree_read(None, 0, None, 0, None) == RT_E_ARG
+
+
+# ---- 5. cost ---------------------------------------------------------------------------------------
+def test_cost_follows_a_loosened_tree():
+    from rtclj import raytracing as R
+    for name in ("reference", "cover"):
+        sc = scene(name)
+        for k in range(3):
+            info, blob = R.tree_build_host(sc, k)
+            t = Tree(info, blob)
+            ext = t.box[:, :, 2:4].astype(np.float64) - t.box[:, :, 0:2].astype(np.float64)      # (nodes, axis, child)
+            want = 0.0
+            for i in range(info.n_nodes):
+                for c in range(2):
+                    dx, dy, dz = ext[i, :, c]
+                    want += 2.0 * (dx * dy + dy * dz + dz * dx)
+            cost0 = R.tree_cost(info, blob)
+            assert cost0 == want and cost0 > 0.0
+            assert R.tree_cost(*R.tree_refit_host(info, blob, sc, sc)) == cost0
+            assert R.tree_cost(*R.tree_refit_host(info, blob, sc, moved(name, "carried"))) > cost0
+
+
+# ---- 6. rounding -------------------------------------------------------------------------------------
+def test_outward_rounding_is_nextafter():
+    """Edge values through the host entry: two bodies of radius 0 at (+-v, 0, 0)
+    are one leaf of the 2-body tree, the tree centre is exactly 0, so the
+    stored x bounds are v stepped outward twice (the body's box, then the box
+    relative to the centre): +-0, +-subnormals, the normal range's ends,
+    neighbours of powers of two.  FLT_MAX itself appears as the second step's
+    input (v = its predecessor: the stored bound is +inf); as a centre it
+    would make the body's own box infinite and the tree centre NaN."""
+    from rtclj import raytracing as R
+    fmax = np.finfo(F).max
+    vals = [F(0.0), TINY, F(2) * TINY, np.nextafter(np.finfo(F).tiny, F(0)), np.finfo(F).tiny,
+            np.nextafter(np.finfo(F).tiny, F(1)), np.nextafter(fmax, F(0)), np.nextafter(np.nextafter(fmax, F(0)), F(0))]
+    for e in (-126, -100, -1, 0, 1, 24, 100, 127):
+        p = F(2.0) ** F(e)
+        vals += [np.nextafter(p, F(0)), p, np.nextafter(p, INF)]
+    base = np.array([[1, 0, 0, 0], [-1, 0, 0, 0]], F)
+    info, blob = R.tree_build_host(base, 0)
+    for v in vals:
+        for sign in (F(1), F(-1)):           # (which body is on which side; -0 for v = 0)
+            sph = base.copy()
+            sph[0, 0], sph[1, 0] = sign * v, -sign * v
+            t = Tree(*R.tree_refit_host(info, blob, base, sph))
+            assert t.center.tobytes() == np.zeros(3, F).tobytes()
+            with np.errstate(over="ignore"):      # (FLT_MAX steps to +inf)
+                lo = np.nextafter(np.nextafter(-v, -INF), -INF)
+                hi = np.nextafter(np.nextafter(v, INF), INF)
+            for c in range(2):
+                assert t.box[0, 0, c].tobytes() == F(lo).tobytes() and t.box[0, 0, 4 + c].tobytes() == F(lo).tobytes(), (v, sign)
+                assert t.box[0, 0, 2 + c].tobytes() == F(hi).tobytes(), (v, sign)
+            # y and z: 0 - 0 and 0 + 0 stepped outward twice
+            assert (t.box[0, 1:, :2] == -2 * TINY).all() and (t.box[0, 1:, 2:4] == 2 * TINY).all()
+
+
+# ---- 7. the sanitizer program, the entries ---------------------------------------------------------------
+def test_refit_check_runs_clean_under_the_sanitizers():
+    out = subprocess.run([str(TOOL)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    rep = json.loads(out.stdout)
+    assert rep["ok"] and rep["failures"] == 0 and rep["refits"] > 50 and rep["refused"] > 100 and rep["subnormal_bounds"] >= 3
+    assert "Sanitizer" not in out.stderr and "runtime error" not in out.stderr
+
+
+def test_the_entries_are_declared_bound_and_exported():
+    import rtclj
+    from rtclj._lib import ADDITIVE, SIGNATURES, rt_tree_info
+    hdr = (ROOT / "include" / "rt.h").read_text()
+    for name in REFIT_FUNCS:
+        assert re.search(r"\b%s\s*\(" % name, hdr) and name in SIGNATURES and name in ADDITIVE
+        assert hasattr(rtclj.lib, name)
+    assert C.sizeof(rt_tree_info) == 56 and rt_tree_info.center.offset == 36

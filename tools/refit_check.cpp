@@ -1,0 +1,308 @@
+// refit_check — the host side of a tree refit (csrc/bvh_refit.h: the outward
+// rounding, the body box, the child box from the bodies under it -- the text
+// refit_kernel runs; csrc/tree_blob.cpp: the blob's layout, the preconditions,
+// the level order and the pass behind rt_tree_refit_host) built for the host
+// under the sanitizers.
+//
+//   g++ -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined,float-cast-overflow
+//       -fno-sanitize-recover=all -static-libasan -static-libubsan tools/refit_check.cpp
+//       raytracing-clj_amd/csrc/tree_blob.cpp raytracing-clj_amd/csrc/bvh.cpp
+//
+// Every blob is a heap block of exactly its size, so a read or write outside
+// it is a report.  Cases: n = 0, 1, 2, 8, 9, 65 for each of the three trees;
+// never-hit bodies (NaN and infinite centres, NaN, infinite and 2^70 radii)
+// among the 65; a tree body whose new centre is NaN or infinite and a changed
+// radius (both refused, the bytes untouched); centres of +-3e38 and +-FLT_MAX
+// (bounds and radii that overflow); a body whose box plane falls exactly on
+// the tree centre (bound 0 -> -+ the smallest subnormal); a refit after a
+// refit; and the rounding against std::nextafter over a sweep of all floats.
+// Each refit is compared, bound by bound, with a restatement written here with
+// std::nextafter and a recursive descent, and with the box of a fresh build.
+// One JSON line; exit status 0 when everything held.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "../raytracing-clj_amd/csrc/bvh_refit.h"
+
+using namespace rtclj;
+
+namespace {
+
+int g_fail = 0;
+#define CHECK(cond)                                                     \
+  do {                                                                  \
+    if (!(cond)) {                                                      \
+      if (g_fail++ < 20) std::fprintf(stderr, "refit_check: line %d: %s\n", __LINE__, #cond); \
+    }                                                                   \
+  } while (0)
+
+struct Rng {
+  uint64_t s;
+  uint64_t next() {
+    uint64_t z = (s += 0x9e3779b97f4a7c15ull);
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+  }
+  float uni() { return static_cast<float>(next() >> 40) * 0x1p-24f; }
+};
+
+bool same_bits(float a, float b) { return std::memcmp(&a, &b, 4) == 0; }
+
+long check_rounding() {
+  long n = 0;
+  auto one = [&](uint32_t u) {
+    const float x = rf_float(u);
+    if (x != x) {   // NaN: unchanged
+      CHECK(rf_bits(rf_up(x)) == u && rf_bits(rf_down(x)) == u);
+    } else {
+      CHECK(same_bits(rf_up(x), std::nextafter(x, INFINITY)));
+      CHECK(same_bits(rf_down(x), std::nextafter(x, -INFINITY)));
+    }
+    ++n;
+  };
+  for (uint64_t u = 0; u < (1ull << 32); u += 4099) one(static_cast<uint32_t>(u));
+  for (uint32_t hi = 0; hi < 512; ++hi)   // around every exponent boundary, both signs
+    for (uint32_t d = 0; d < 8; ++d) one((hi << 23) + d - 4u);
+  return n;
+}
+
+struct Tree {
+  std::unique_ptr<char[]> blob;   // exactly info.blob_bytes
+  rt_tree_info info{};
+};
+
+Tree build(const std::vector<float>& sph, int k) {
+  const int n = static_cast<int>(sph.size() / 4);
+  BvhHost bvh;
+  bvh_build(sph.data(), n, &bvh, 2 << k, true);
+  std::vector<char> bytes;
+  Tree t;
+  tree_pack(bvh, k, &bytes, &t.info);
+  t.blob.reset(new char[bytes.size()]);
+  std::memcpy(t.blob.get(), bytes.data(), bytes.size());
+  return t;
+}
+
+Tree copy(const Tree& t) {
+  Tree c;
+  c.info = t.info;
+  c.blob.reset(new char[t.info.blob_bytes]);
+  std::memcpy(c.blob.get(), t.blob.get(), t.info.blob_bytes);
+  return c;
+}
+
+bool same(const Tree& a, const Tree& b) {
+  return std::memcmp(&a.info, &b.info, sizeof a.info) == 0 && std::memcmp(a.blob.get(), b.blob.get(), a.info.blob_bytes) == 0;
+}
+
+// the restatement: the bodies under a child by recursive descent, their boxes
+// with std::nextafter
+struct Box64 {
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+};
+void bodies_under(const Tree& t, int ref, std::vector<int>* out) {
+  const RfTree v = tree_view(t.blob.get(), t.info);
+  if (ref < 0) {
+    for (int slot = 2 * ~ref; slot < 2 * (~ref + v.leaf_pairs); ++slot)
+      if (rf_body(v, slot) >= 0) out->push_back(rf_body(v, slot));
+    return;
+  }
+  const BvhNode* nd = reinterpret_cast<const BvhNode*>(t.blob.get()) + ref / v.ref_div;
+  bodies_under(t, nd->child[0], out);
+  bodies_under(t, nd->child[1], out);
+}
+
+void check_against_restatement(const Tree& t, const std::vector<float>& sph, const Tree* fresh) {
+  const RfTree v = tree_view(t.blob.get(), t.info);
+  for (int i = 0; i < t.info.n_nodes; ++i) {
+    const BvhNode* nd = reinterpret_cast<const BvhNode*>(t.blob.get()) + i;
+    for (int c = 0; c < 2; ++c) {
+      std::vector<int> under;
+      bodies_under(t, nd->child[c], &under);
+      Box64 b;
+      if (v.empty)
+        for (int k = 0; k < 3; ++k) b.lo[k] = b.hi[k] = 0.0f;
+      for (int body : under) {
+        const float* s = &sph[4 * static_cast<size_t>(body)];
+        const float r = std::fabs(s[3]);
+        for (int k = 0; k < 3; ++k) {
+          b.lo[k] = std::fmin(b.lo[k], std::nextafter(s[k] - r, -INFINITY));
+          b.hi[k] = std::fmax(b.hi[k], std::nextafter(s[k] + r, INFINITY));
+        }
+      }
+      const float* ax[3] = {nd->x, nd->y, nd->z};
+      for (int k = 0; k < 3; ++k) {
+        const float dl = static_cast<float>(double(b.lo[k]) - double(t.info.center[k]));
+        const float dh = static_cast<float>(double(b.hi[k]) - double(t.info.center[k]));
+        if (dl != dl || dh != dh) {   // inf - inf: a NaN either way
+          CHECK(ax[k][c] != ax[k][c] || ax[k][2 + c] != ax[k][2 + c]);
+          continue;
+        }
+        CHECK(same_bits(ax[k][c], std::nextafter(dl, -INFINITY)));
+        CHECK(same_bits(ax[k][2 + c], std::nextafter(dh, INFINITY)));
+        CHECK(same_bits(ax[k][4 + c], ax[k][c]));
+      }
+    }
+  }
+  // the leaf records hold their bodies' centres
+  const float* pairs = reinterpret_cast<const float*>(t.blob.get() + t.info.off_pairs);
+  for (int slot = 0; slot < 2 * v.n_pairs; ++slot) {
+    const int body = rf_body(v, slot);
+    if (body < 0) continue;
+    const float* p = pairs + 8 * (slot >> 1) + (slot & 1);
+    for (int k = 0; k < 3; ++k) CHECK(same_bits(p[2 * k], sph[4 * static_cast<size_t>(body) + k]));
+  }
+  if (fresh) {   // the body set is the same: so are centre, radius and c0
+    CHECK(std::memcmp(fresh->info.center, t.info.center, 12) == 0 || t.info.center[0] != t.info.center[0]);
+    CHECK(same_bits(fresh->info.radius, t.info.radius) && same_bits(fresh->info.c0, t.info.c0));
+  }
+}
+
+std::vector<float> scene(Rng& r, int n, bool never_hit) {
+  std::vector<float> s(4 * static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) {
+    for (int k = 0; k < 3; ++k) s[4 * i + k] = -8.0f + 16.0f * r.uni();
+    s[4 * i + 3] = 0.1f + 0.3f * r.uni();
+  }
+  if (n > 9) {   // something for the big list, a negative radius
+    s[3] = 50.0f;
+    s[7] = -0.25f;
+  }
+  if (never_hit && n >= 16) {
+    s[4 * 3 + 0] = NAN;
+    s[4 * 5 + 2] = INFINITY;
+    s[4 * 7 + 1] = -INFINITY;
+    s[4 * 9 + 3] = NAN;
+    s[4 * 11 + 3] = INFINITY;
+    s[4 * 13 + 3] = 0x1p70f;
+  }
+  return s;
+}
+
+bool in_tree(const float* s) {
+  return std::isfinite(s[0]) && std::isfinite(s[1]) && std::isfinite(s[2]) && std::isfinite(s[3] * s[3]);
+}
+
+std::vector<float> moved(Rng& r, const std::vector<float>& s0, float amp) {
+  std::vector<float> s = s0;
+  for (size_t i = 0; i < s.size() / 4; ++i) {
+    if (!in_tree(&s0[4 * i])) {
+      if (!std::isfinite(s0[4 * i + 3] * s0[4 * i + 3]))   // left out for its radius: any centre
+        s[4 * i] = r.uni() < 0.5f ? NAN : 3.0f;
+      continue;
+    }
+    for (int k = 0; k < 3; ++k) s[4 * i + k] += amp * (2.0f * r.uni() - 1.0f);
+  }
+  return s;
+}
+
+void refit_ok(Tree& t, const std::vector<float>& s0, const std::vector<float>& s1) {
+  const char* why = nullptr;
+  const int rc = tree_refit(t.blob.get(), &t.info, s0.data(), s1.data(), static_cast<int>(s0.size() / 4), &why);
+  CHECK(rc == RT_OK && why == nullptr);
+}
+
+void refit_refused(const Tree& t, const std::vector<float>& s0, const std::vector<float>& s1) {
+  Tree c = copy(t);
+  const char* why = nullptr;
+  const int rc = tree_refit(c.blob.get(), &c.info, s0.data(), s1.data(), static_cast<int>(s0.size() / 4), &why);
+  CHECK(rc == RT_E_ARG && why != nullptr);
+  CHECK(same(c, t));
+}
+
+}  // namespace
+
+int main() {
+  Rng r{0x5eed5eedull};
+  const long rounded = check_rounding();
+  long refits = 0, refused = 0, subnormal_bounds = 0;
+  const int sizes[] = {0, 1, 2, 8, 9, 65};
+  for (int n : sizes)
+    for (int hostile = 0; hostile < (n == 65 ? 2 : 1); ++hostile)
+      for (int k = 0; k < 3; ++k) {
+        const std::vector<float> s0 = scene(r, n, hostile != 0);
+        const Tree up = build(s0, k);
+        const char* why = nullptr;
+        CHECK(tree_check(up.blob.get(), up.info, n, &why) == RT_OK);
+        double cost0 = 0.0;
+        CHECK(tree_cost(up.blob.get(), up.info, &cost0, &why) == RT_OK && cost0 >= 0.0);
+        check_against_restatement(up, s0, nullptr);
+        // identity
+        Tree t = copy(up);
+        refit_ok(t, s0, s0);
+        CHECK(same(t, up));
+        // a motion, then another on top of it: the same bytes as the second alone
+        const std::vector<float> s1 = moved(r, s0, 0.5f), s2 = moved(r, s0, 20.0f);
+        refit_ok(t, s0, s1);
+        const Tree f1 = build(s1, k);
+        check_against_restatement(t, s1, &f1);
+        refit_ok(t, s0, s2);
+        Tree direct = copy(up);
+        refit_ok(direct, s0, s2);
+        CHECK(same(t, direct));
+        const Tree f2 = build(s2, k);
+        check_against_restatement(t, s2, &f2);
+        refits += 4;
+        // centres of +-3e38 and +-FLT_MAX: bounds, radii and centres that overflow
+        if (n > 0) {
+          std::vector<float> s3 = s0;
+          const float big[] = {3e38f, -3e38f, 3.4028234664e38f, -3.4028234664e38f};
+          for (int i = 0; i < n; ++i)
+            if (in_tree(&s0[4 * i]))
+              for (int q = 0; q < 3; ++q)
+                if (r.uni() < 0.5f) s3[4 * i + q] = big[r.next() % (i % 2 ? 4 : 2)];
+          Tree t3 = copy(up);
+          refit_ok(t3, s0, s3);
+          check_against_restatement(t3, s3, nullptr);
+          ++refits;
+        }
+        // refused: a changed radius; a tree body's centre NaN or infinite; a
+        // body left out for its centre given a finite one
+        for (int i = 0; i < n; ++i) {
+          std::vector<float> bad = s1;
+          bad[4 * i + 3] = rf_up(s0[4 * i + 3]);
+          if (!same_bits(bad[4 * i + 3], s0[4 * i + 3])) refit_refused(t, s0, bad), ++refused;
+          if (!std::isfinite(s0[4 * i + 3] * s0[4 * i + 3])) continue;
+          bad = s1;
+          if (in_tree(&s0[4 * i])) bad[4 * i + static_cast<int>(r.next() % 3)] = r.uni() < 0.5f ? NAN : -INFINITY;
+          else bad[4 * i] = bad[4 * i + 1] = bad[4 * i + 2] = 0.5f;
+          refit_refused(t, s0, bad), ++refused;
+        }
+      }
+  // a box plane exactly on the tree centre: bodies at x = 1 and 3 (r = 0.5) put
+  // the centre's x at 2; the boxes of eight more all start there, so the root
+  // child without the body at x = 1 has its min plane on the centre
+  CHECK(rf_bits(rf_down(rf_rel(2.0f, 2.0f))) == 0x80000001u && rf_bits(rf_up(rf_rel(2.0f, 2.0f))) == 1u);
+  for (int k = 0; k < 3; ++k) {
+    std::vector<float> s0 = {1, 0, 0, 0.5f, 3, 0, 0, 0.5f};
+    for (int i = 0; i < 8; ++i) {
+      const float more[4] = {2.5f, static_cast<float>(i % 3) - 1.0f, static_cast<float>(i / 3) - 1.0f, 0.25f};
+      s0.insert(s0.end(), more, more + 4);
+    }
+    Tree t = build(s0, k);
+    CHECK(t.info.center[0] == 2.0f);
+    std::vector<float> s1 = s0;
+    for (int i = 2; i < 10; ++i) s1[4 * i] = rf_up(2.0f) + 0.25f;   // x - r = the float above 2: one step down is 2
+    CHECK(rf_down(s1[8] - 0.25f) == 2.0f);
+    refit_ok(t, s0, s1);
+    CHECK(t.info.center[0] == 2.0f);
+    const Tree f = build(s1, k);
+    check_against_restatement(t, s1, &f);
+    long here = 0;
+    for (int i = 0; i < t.info.n_nodes; ++i) {
+      const BvhNode* nd = reinterpret_cast<const BvhNode*>(t.blob.get()) + i;
+      for (int c = 0; c < 2; ++c) here += rf_bits(nd->x[c]) == 0x80000001u;
+    }
+    CHECK(here >= 1);
+    subnormal_bounds += here;
+    ++refits;
+  }
+  std::printf("{\"ok\": %s, \"failures\": %d, \"rounded\": %ld, \"refits\": %ld, \"refused\": %ld, \"subnormal_bounds\": %ld}\n",
+              g_fail == 0 ? "true" : "false", g_fail, rounded, refits, refused, subnormal_bounds);
+  return g_fail == 0 ? 0 : 1;
+}
