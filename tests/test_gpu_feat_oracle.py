@@ -40,9 +40,11 @@ def _bits(a):
     return a.view(np.uint32)
 
 
-def _check(env, sc, cam, w, h, passes, seed, flags=0, begin=0, rejection=False, label="", **sel):
+def _check(env, sc, cam, w, h, passes, seed, flags=0, begin=0, rejection=False, label="", variants=VARIANTS, **sel):
     """Every variant's rt_feat after `passes` (sample counts, consecutive from
-    `begin`) against the mirror's passes added up -> the mirror's arrays."""
+    `begin`) against the mirror's passes added up -> the mirror's arrays.
+    variants: (selector, the source rt_feat_occupancy must report) pairs; the
+    default is a small scene's, whose tree fits the LDS budget."""
     from rtclj._lib import lib
     want = None
     b = begin
@@ -54,7 +56,7 @@ def _check(env, sc, cam, w, h, passes, seed, flags=0, begin=0, rejection=False, 
     want_frame = F.resolve_np(want["sums"], want["hits"], want["depth"], total)
     ds = _upload(sc)
     try:
-        for v, source in VARIANTS:
+        for v, source in variants:
             def run():
                 assert _source(ds) == source, (label, v)
                 p0 = _params(w, h, total, seed=seed, flags=flags, **sel.get("params", {}))

@@ -7,7 +7,9 @@ from the moved spheres, for every product variant, the feature pass and the
 body ids (those also against ids_host: a witness that is not the device), with
 the frame of the un-updated scene as the control; stream order; the errors;
 and render_animation(refit=True).  Every output buffer is pre-filled (floats
-with NaN, ids with 0x7fffffff).  All inputs are valid: nothing here can fault.
+with NaN, ids with 0x7fffffff).  All inputs are valid: nothing here can fault.  The checks
+are functions (check_*) that tests/test_gpu_scene_sizes.py runs again on the
+scenes above 1024 bodies.
 """
 import ctypes as C
 
@@ -43,19 +45,19 @@ def params(env, w, h, spp=SPP, depth=DEPTH):
     return rt_params(width=w, height=h, row_begin=0, row_end=h, spp=spp, max_depth=depth, seed=3)
 
 
-def enqueue_frame(env, lib, ds, cam, w, h, stream=None):
+def enqueue_frame(env, lib, ds, cam, w, h, stream=None, spp=SPP):
     """rt_launch into a NaN-filled buffer, not waited for."""
     torch = env.torch
     d = torch.full((w * h * 3,), float("nan"), dtype=torch.float32, device="cuda")
     torch.cuda.synchronize()
-    p = params(env, w, h)
+    p = params(env, w, h, spp)
     st = C.c_void_p(stream.cuda_stream) if stream is not None else None
     assert lib.rt_launch(ds, C.byref(cam), C.byref(p), C.c_void_p(d.data_ptr()), None, st) == 0, lib.rt_last_error()
     return d
 
 
-def frame(env, lib, ds, cam, w, h, stream=None):
-    d = enqueue_frame(env, lib, ds, cam, w, h, stream)
+def frame(env, lib, ds, cam, w, h, stream=None, spp=SPP):
+    d = enqueue_frame(env, lib, ds, cam, w, h, stream, spp)
     env.torch.cuda.synchronize()
     got = d.cpu().numpy().reshape(h, w, 3)
     assert not np.isnan(got).any()
@@ -96,8 +98,8 @@ def with_spheres(env, sc, sph):
 
 
 # ---- 1. the device's bytes are the host refit's ------------------------------------------------
-@pytest.mark.parametrize("name", SCENES)
-def test_device_equals_host(env, name):
+def check_device_equals_host(env, name):
+    """-> the three trees (info, blob) as the upload left them on the device."""
     R = env.R
     sc = scene(name)
     own = env.torch.cuda.Stream()
@@ -119,6 +121,12 @@ def test_device_equals_host(env, name):
                 want_info, want = R.tree_refit_host(up[k][0], up[k][1], sc, sph)
                 assert blob.tobytes() == want.tobytes(), (name, motion, k, int((blob != want).sum()))
                 assert bytes(info) == bytes(want_info), (name, motion, k)
+    return up
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_device_equals_host(env, name):
+    check_device_equals_host(env, name)
 
 
 # ---- 2. rendered frames ------------------------------------------------------------------------------
@@ -128,29 +136,38 @@ def moving_pair(env, which):
         return (R.Scene.from_bodies(rising(0, 4)), R.Scene.from_bodies(rising(3, 4)),
                 lambda w, h: R.camera(w, h, **R.REFERENCE_CAMERA))
     sc = scene(which)
-    return sc, with_spheres(env, sc, moved(which, "jitter")), env.scenes.cover_camera
+    return sc, with_spheres(env, sc, moved(which, "jitter")), scene_camera(env, which)
 
 
-def check_frames(env, which, w, h, variants, everything):
+def scene_camera(env, which):
+    """(w, h) -> the camera of a scene of tests/test_refit_host.py: the cover
+    scene's, or for the random field test_max_spheres_and_too_many's."""
+    if which.startswith("field"):
+        return lambda w, h: env.R.camera(w, h, 40.0, (0, 1, 3), (0, 1, -10), (0, 1, 0), 0.0, 10.0)
+    return env.scenes.cover_camera
+
+
+def check_frames(env, which, w, h, variants, everything, spp=SPP):
+    """-> the variants that ran (rt_launch_occupancy), in `variants`' order."""
     R, lib = env.R, env.lib
     sc0, sc1, camera = moving_pair(env, which)
     cam = camera(w, h)
     out4 = (C.c_int * 4)()
     with R.DeviceScene(sc0) as old, R.DeviceScene(sc0) as upd, R.DeviceScene(sc1) as new:
         upd.update(sc1)
-        ran = set()
+        ran = []
         for variant in variants:
             before = lib.rt_set_variant(variant)
             try:
-                p = params(env, w, h)
+                p = params(env, w, h, spp)
                 assert lib.rt_launch_occupancy(upd.handle, C.byref(p), out4) == 0
-                ran.add(out4[3])
-                got = frame(env, lib, upd.handle, cam, w, h)
-                want = frame(env, lib, new.handle, cam, w, h)
+                ran.append(out4[3])
+                got = frame(env, lib, upd.handle, cam, w, h, spp=spp)
+                want = frame(env, lib, new.handle, cam, w, h, spp=spp)
                 assert np.array_equal(bits(got), bits(want)), (which, variant, out4[3], int((got != want).any(axis=-1).sum()))
                 if variant == 0:
                     # the control: the motion shows, so a refit that did nothing would
-                    stale = frame(env, lib, old.handle, cam, w, h)
+                    stale = frame(env, lib, old.handle, cam, w, h, spp=spp)
                     assert int((stale != want).any(axis=-1).sum()) > 20
                 if everything and variant in (0, 5, 12):      # the feature pass and the ids under each source of bodies
                     assert np.array_equal(bits(feat_frame(env, upd.handle, cam, w, h)), bits(feat_frame(env, new.handle, cam, w, h)))
@@ -167,7 +184,7 @@ def check_frames(env, which, w, h, variants, everything):
 
 @pytest.mark.parametrize("which", ("reference", "cover"))
 def test_frames_equal_a_fresh_upload(env, which):
-    ran = check_frames(env, which, W, H, VARIANTS, True)
+    ran = set(check_frames(env, which, W, H, VARIANTS, True))
     # (the policy may run 16 as its compact image 22, and 18 as 24 or 26)
     assert {5, 12} <= ran and ran & {16, 22} and ran & {18, 24, 26}, ran
 
@@ -179,11 +196,15 @@ def test_frames_of_a_larger_scene(env):
 
 
 def test_frames_of_the_diagnostic_library(env):
+    check_diagnostic_frames(env, "cover")
+
+
+def check_diagnostic_frames(env, which):
     """Variant 9 reads the pair-interleaved table (geo2)."""
     from rtclj._lib import diag_lib
     R = env.R
     d = diag_lib()
-    sc0, sc1, camera = moving_pair(env, "cover")
+    sc0, sc1, camera = moving_pair(env, which)
     cam = camera(W, H)
     before = d.rt_set_variant(9)
     assert before >= 0
@@ -200,6 +221,10 @@ def test_frames_of_the_diagnostic_library(env):
 # ---- 3. ordering --------------------------------------------------------------------------------------
 @pytest.mark.parametrize("which", ("reference", "cover"))
 def test_update_is_ordered_on_its_stream(env, which):
+    check_update_is_ordered(env, which)
+
+
+def check_update_is_ordered(env, which):
     """Launch A, the update, launch B on one stream with nothing in between,
     and the caller's array overwritten as soon as the update returns."""
     from rtclj._lib import fptr

@@ -6,7 +6,9 @@ radius against a fresh build, the argument errors, the cost, the outward
 rounding against np.nextafter through the host entry, the stand-alone
 sanitizer program and the presence of the new entries.
 
-The scenes, motions and the restatement are shared with tests/test_gpu_refit.py.
+The scenes, motions and the restatement are shared with tests/test_gpu_refit.py;
+the scenes above 1024 bodies (LARGE) and the sizes each of them is there for
+(EDGES, check_size_edges) also with tests/test_gpu_scene_sizes.py.
 """
 import ctypes as C
 import functools
@@ -31,14 +33,40 @@ COVER_G = 3
 SCENES = ("reference", "cover", "nonfinite_few", "nonfinite_64", "nonfinite_65", "nonfinite_80", "neg_radius_field",
           "bubble_negative_radius")
 MOTIONS = ("jitter", "carried", "plane")
+# Scenes above the 1024 threads of refit_kernel's workgroups (csrc/bvh_refit.h; what each is for is asserted by
+# test_the_large_scenes_reach_the_size_edges): cover(16), 1025 bodies, a second table workgroup of one body;
+# cover(46) cut to 2049, the slot loops of trees 0 and 1 take a second trip; cover(46) cut to RT_MAX_SPHERES
+# with the body order permuted, and test_gpu_parity's random field of as many without big bodies: tree 0's
+# widest level is above 1024 nodes and its boxes need more than 64 KB of LDS
+LARGE = ("cover16", "cover2049", "cover8192", "field8192")
+PERM_SEED = 11
 
 
 # ---- scenes and motions ----------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def scene(name):
-    from rtclj import scenes
+    from rtclj import raytracing as R, scenes
+    from rtclj._lib import RT_MAX_SPHERES
     if name == "reference":
         return scenes.reference()
+    if name == "cover2049":
+        return scenes.cover(46, max_bodies=2049)
+    if name == "cover8192":
+        # every block of 1024 indices spread over the whole field (the ground and the r = 1 bodies among them)
+        sc = scenes.cover(46, max_bodies=RT_MAX_SPHERES)
+        order = np.random.default_rng(PERM_SEED).permutation(len(sc))
+        return R.Scene(sc.sphere[order], sc.kind[order], sc.mat[order])
+    if name == "field8192":           # tests/test_gpu_parity.py::test_max_spheres_and_too_many's, draw for draw
+        rng = np.random.default_rng(0)
+        n = RT_MAX_SPHERES
+        sph = np.zeros((n, 4), F)
+        sph[:, 0] = rng.uniform(-40, 40, n)
+        sph[:, 1] = rng.uniform(-1, 3, n)
+        sph[:, 2] = rng.uniform(-60, -5, n)
+        sph[:, 3] = 0.1
+        kind = rng.integers(0, 3, n).astype(np.int32)
+        mat = np.column_stack([rng.uniform(0, 1, (n, 3)), np.where(kind == 2, 1.5, 0.3)]).astype(F)
+        return R.Scene(sph, kind, mat)
     if name.startswith("cover"):      # "cover": the small one; "cover11": the benchmark's
         return scenes.cover(COVER_G if name == "cover" else int(name[5:]))
     import edge_scenes
@@ -87,6 +115,16 @@ class Tree:
                 if ref >= 0:
                     depth[ref // self.ref_div] = depth[i] + 1
         return int(depth.max()) + 1
+
+    def widest_level(self):
+        """The most nodes at one distance from the root: what one trip of the
+        device's per-level node loop has to cover."""
+        depth = np.zeros(self.info.n_nodes, int)
+        for i in range(self.info.n_nodes):       # (a node's index is above its parent's)
+            for ref in self.child[i]:
+                if ref >= 0:
+                    depth[ref // self.ref_div] = depth[i] + 1
+        return int(np.bincount(depth).max())
 
     def under(self, ref):
         """The bodies under a child ref."""
@@ -198,7 +236,7 @@ def moved(name, motion, seed=7):
 
 # ---- 1. the NumPy restatement -----------------------------------------------------------
 @pytest.mark.parametrize("k", [0, 1, 2])
-@pytest.mark.parametrize("name", SCENES)
+@pytest.mark.parametrize("name", SCENES + LARGE)
 def test_refit_equals_the_numpy_restatement(name, k):
     from rtclj import raytracing as R
     sc = scene(name)
@@ -228,8 +266,75 @@ def test_the_cover_scene_has_levels_and_a_big_body():
     assert ref.info.n_big_leaves == 0 and ref.levels() == 1
 
 
+THREADS = 1024      # csrc/bvh_refit.h: kRefitThreads
+LDS_64K = 65536     # above it rt_scene_update raises the kernel's dynamic-LDS limit
+
+
+def size_edges(trees, n):
+    """What a scene of n bodies with these three Trees (2-, 4-, 8-body leaves)
+    makes refit_kernel do that a scene within one workgroup does not ->
+    a set of names.  The device tests assert the same from rt_scene_tree_info."""
+    edges = set()
+    if n > THREADS:
+        edges.add("table_blocks")                 # more than one table workgroup
+    if n > THREADS and n % THREADS == 1:
+        edges.add("table_last_block_of_one")      # ... the last one holding a single body
+    for k, t in enumerate(trees):
+        if 2 * t.n_pairs > THREADS:
+            edges.add("slot_stride_%d" % k)       # the slot loop's second trip
+        if t.widest_level() > THREADS:
+            edges.add("level_stride_%d" % k)      # the per-level node loop's second trip
+    if 24 * max(t.info.n_nodes for t in trees) > LDS_64K:
+        edges.add("lds_above_64k")
+    return edges
+
+
+# the edges each large scene is there for (both layouts of RT_MAX_SPHERES bodies carry the node loop's stride and
+# the LDS request above 64 KB, on tree 0 alone: the 4- and 8-body trees' widest levels stay below 1024 nodes)
+EDGES = {
+    "cover16": {"table_blocks", "table_last_block_of_one", "slot_stride_0", "slot_stride_1", "slot_stride_2"},
+    "cover2049": {"table_blocks", "table_last_block_of_one", "slot_stride_0", "slot_stride_1", "slot_stride_2"},
+    "cover8192": {"table_blocks", "slot_stride_0", "slot_stride_1", "slot_stride_2", "level_stride_0", "lds_above_64k"},
+    "field8192": {"table_blocks", "slot_stride_0", "slot_stride_1", "slot_stride_2", "level_stride_0", "lds_above_64k"},
+}
+BODIES = {"cover16": 1025, "cover2049": 2049, "cover8192": 8192, "field8192": 8192}
+
+
+def check_size_edges(name, trees):
+    """The trees (three Trees, from the host's build or read back from the
+    device) are those of `name` and reach its edges."""
+    n = BODIES[name]
+    assert len(scene(name)) == n
+    for t in trees:
+        assert t.info.depth + 2 <= 16, (name, t.info.depth)       # bvh.h: kBvhStack
+    assert size_edges(trees, n) >= EDGES[name], (name, size_edges(trees, n))
+    if "lds_above_64k" in EDGES[name]:                            # (on the tree the issue names)
+        assert 24 * trees[0].info.n_nodes > LDS_64K and trees[0].widest_level() > THREADS
+        assert 2 * trees[0].n_pairs > 4 * THREADS                 # several trips of the slot loop
+
+
+def test_the_large_scenes_reach_the_size_edges():
+    """Each large scene has the sizes it is there for, so a later change to the
+    build or to the scenes cannot hollow the tests on them out.  The cover
+    layouts carry the big-body list, the field has none."""
+    from rtclj import raytracing as R
+    from rtclj._lib import RT_MAX_SPHERES
+    assert set(EDGES) == set(LARGE) == set(BODIES) and BODIES["cover8192"] == RT_MAX_SPHERES
+    trees = {name: [Tree(*R.tree_build_host(scene(name), k)) for k in range(3)] for name in ("cover11",) + LARGE}
+    for name in LARGE:
+        check_size_edges(name, trees[name])
+    # where the earlier tests stop, and the mid-size scene: below the 8192-body scenes' edges
+    assert len(scene("cover11")) == 484 and size_edges(trees["cover11"], 484) == set()
+    assert not size_edges(trees["cover2049"], 2049) & {"lds_above_64k", "level_stride_0"}
+    assert all(t.info.n_big_leaves >= 1 for name in ("cover16", "cover2049", "cover8192") for t in trees[name])
+    assert all(t.info.n_big_leaves == 0 for t in trees["field8192"])
+    # the permutation took the ground and the r = 1 bodies off the ends of the array
+    big = np.flatnonzero(np.abs(scene("cover8192").sphere[:, 3]) >= 1)
+    assert len(big) == 4 and 0 < big.min() and big.max() < RT_MAX_SPHERES - 1
+
+
 # ---- 2. identity ---------------------------------------------------------------------------
-@pytest.mark.parametrize("name", SCENES)
+@pytest.mark.parametrize("name", SCENES + LARGE)
 def test_identity_refit_changes_nothing(name):
     from rtclj import raytracing as R
     sc = scene(name)
@@ -240,7 +345,7 @@ def test_identity_refit_changes_nothing(name):
 
 
 # ---- 3. against a rebuild ---------------------------------------------------------------------
-@pytest.mark.parametrize("name", SCENES)
+@pytest.mark.parametrize("name", SCENES + LARGE)
 def test_refit_against_a_rebuild(name):
     from rtclj import raytracing as R
     sc = scene(name)
