@@ -1079,7 +1079,7 @@ int rt_launch_occupancy(const rt_dscene* ds, const rt_params* p, int* out4);
  * same launch shape (width, row selection; camera, spp, seed, flags and the
  * kernel variant may differ) dispatches its tiles in that order, so the slow
  * tiles do not trail the kernel's end.  A launch of another shape runs in
- * plain order and re-keys the record (per scene, up to 8 streams; launches on
+ * plain order and re-keys the record (per scene, up to 16 streams; launches on
  * further streams are unscheduled).  1 = always plain order.  Changes timing
  * only: every pixel is computed the same way in any order (bit-identical
  * output).  Returns the previous value, RT_E_ARG for another mode. */
@@ -1122,6 +1122,52 @@ int rt_steal_stats(const rt_dscene* ds, void* hip_stream, uint64_t* out2);
  * the records the latest of them wrote.  Waits for the stream.  Timing
  * only: the bits never depend on it. */
 int rt_export_stats(const rt_dscene* ds, void* hip_stream, uint64_t* out2);
+
+/* The adaptive order's record of (ds, hip_stream), read out (diagnostic; the
+ * tests of the schedule read it).  exists: the stream owns one of the scene's
+ * 16 entries (0: its launches run unscheduled, every other field is as
+ * below for "none").  n_tiles: the tile count of the launch shape the entry
+ * is keyed to (0 before a launch).  has_record: the cost and order buffers
+ * hold n_tiles entries.  ready: the order is the sort of a record and the next
+ * launch of the shape uses it as it stands.  sort_pending: the last launch
+ * added to the record and its sort runs at the start of the next launch of
+ * the shape.  plan_units: the unit count of the cost-balanced split plan the
+ * last sort made (RTCLJ_SPLIT_PLAN=1; -1: none).  sort_plan: the unit count
+ * the pending sort will plan for (-1: none).  max_streams: the streams a scene
+ * keeps entries for (16), set whether or not this stream owns one. */
+typedef struct rt_schedule_info {
+  int32_t exists;
+  int32_t n_tiles;
+  int32_t has_record;
+  int32_t ready;
+  int32_t sort_pending;
+  int32_t plan_units;
+  int32_t sort_plan;
+  int32_t max_streams;
+} rt_schedule_info;
+
+/* Waits for hip_stream, then copies out the entry's n_tiles per-tile costs
+ * (100 MHz ticks: each launch's workgroup durations added to half the record
+ * before it), its n_tiles order positions as they stand (order[i] = the tile
+ * dispatched i-th) and the plan's plan_units units ({tile, k | s << 8} as two
+ * int32 each; {-1, 0}: unused).  host_cost, host_order and host_units may be
+ * NULL (info only); cap_tiles and cap_units are their capacities in tiles and
+ * in units.  Changes nothing: no pending sort is run, no flag flipped, no
+ * buffer grown.  RT_E_ARG for a NULL ds or info, or a cap smaller than what
+ * the buffer would receive (a cap of 0 for a buffer that is given, always);
+ * nothing is written then.  Timing only: the bits never depend on it. */
+int rt_schedule_read(const rt_dscene* ds, void* hip_stream, rt_schedule_info* info, uint32_t* host_cost,
+                     int32_t* host_order, int32_t* host_units, int cap_tiles, int cap_units);
+
+/* The schedule's sort on the caller's data, without a scene (diagnostic): the
+ * n costs, host_order's n entries and (U > 0) host_units' 2 U int32 go up to
+ * `device` as they are; the sort kernel, and for U > 0 the plan kernel with at
+ * most smax units per tile, run on hip_stream exactly as a launch enqueues
+ * them; then the halved costs, the longest-first order and the U units come
+ * back.  Waits for the stream.  RT_E_ARG for a NULL array, n <= 0, U < 0,
+ * 0 < U < n, or smax outside 1 .. 64; RT_E_NODEV when `device` is not there. */
+int rt_schedule_sort(int device, uint32_t* host_cost_inout, int n, int32_t* host_order, int U, int smax,
+                     int32_t* host_units, void* hip_stream);
 
 /* A device's one-time start-up, done ahead of the first render so that a
  * one-frame process (-main, raytracing.clj:95-177) can overlap it with its

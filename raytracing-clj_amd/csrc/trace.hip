@@ -1177,6 +1177,15 @@ static hipError_t enqueue_fills(const FillSet& fills, hipStream_t stream) {
   return enqueue(fill_set_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, fills);
 }
 
+// The schedule's sort of n costs: order_kernel (longest-first order, each cost
+// halved), and for a plan of U > 0 units plan_kernel behind it.  What
+// Schedule::sort_record and rt_schedule_sort enqueue.
+static hipError_t enqueue_sort(unsigned* cost, int* order, int n, int U, int smax, int2* units, hipStream_t stream) {
+  const hipError_t e = enqueue(order_kernel, dim3(1), dim3(1024), 0, stream, cost, order, n);
+  if (e != hipSuccess || U <= 0) return e;
+  return enqueue(plan_kernel, dim3(1), dim3(1024), 0, stream, cost, order, n, U, smax, units);
+}
+
 // A launch of another shape re-keys the entry: that record was another
 // shape's.  Returns whether it did.
 bool Schedule::rekey(const ScheduleKey& k) {
@@ -1191,16 +1200,13 @@ bool Schedule::rekey(const ScheduleKey& k) {
 // order_kernel, and plan_kernel for a planned split; the order is ready for
 // the next launch of the shape.
 int Schedule::sort_record(int n_tiles, int spp) {
-  HIP_TRY(enqueue(order_kernel, dim3(1), dim3(1024), 0, stream, cost.p, order.p, n_tiles));
+  // the next split launch's cost-balanced units, from this record
+  const bool plan = sort_plan > 0 && units.cap >= static_cast<size_t>(sort_plan);
+  HIP_TRY(enqueue_sort(cost.p, order.p, n_tiles, plan ? sort_plan : 0, std::min(spp, policy::kSplitMax), units.p,
+                       stream));
   ready = true;
   sort_pending = false;
-  plan_units = -1;
-  if (sort_plan > 0 && units.cap >= static_cast<size_t>(sort_plan)) {
-    // the next split launch's cost-balanced units, from this record
-    HIP_TRY(enqueue(plan_kernel, dim3(1), dim3(1024), 0, stream, cost.p, order.p, n_tiles, sort_plan,
-                    std::min(spp, policy::kSplitMax), units.p));
-    plan_units = sort_plan;
-  }
+  plan_units = plan ? sort_plan : -1;
   return RT_OK;
 }
 
@@ -2582,6 +2588,87 @@ extern "C" int rt_export_stats(const rt_dscene* ds, void* hip_stream, uint64_t* 
   out2[0] = e->xq_launches;
   out2[1] = n[0];
   e->xq_launches = 0;
+  return RT_OK;
+}
+
+// The adaptive schedule's entry of (ds, stream), read out (diagnostic): waits
+// for the stream, then copies the per-tile costs, the order as it stands and
+// the planned units.  Changes nothing: a pending sort stays pending.
+extern "C" int rt_schedule_read(const rt_dscene* ds, void* hip_stream, rt_schedule_info* info, uint32_t* host_cost,
+                                int32_t* host_order, int32_t* host_units, int cap_tiles, int cap_units) {
+  clear_error();
+  if (cap_tiles < 0 || cap_units < 0 || ((host_cost || host_order) && cap_tiles == 0) || (host_units && cap_units == 0))
+    return set_error(RT_E_ARG, "rt_schedule_read: a buffer's cap is too small");
+  if (!ds || !info) return set_error(RT_E_ARG, "rt_schedule_read: NULL argument");
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  std::lock_guard<std::mutex> lk(ds->sched.mu);
+  const Schedule* e = ds->sched.find(stream);
+  rt_schedule_info out{};
+  out.plan_units = out.sort_plan = -1;
+  out.max_streams = kSchedStreams;
+  if (!e) {
+    *info = out;
+    return RT_OK;
+  }
+  const int n = e->key.gx * e->key.gy;
+  out.exists = 1;
+  out.n_tiles = n;
+  out.ready = e->ready ? 1 : 0;
+  out.sort_pending = e->sort_pending ? 1 : 0;
+  out.plan_units = e->plan_units;
+  out.sort_plan = e->sort_plan;
+  out.has_record = (n > 0 && e->cost.cap >= static_cast<size_t>(n) && e->order.cap >= static_cast<size_t>(n)) ? 1 : 0;
+  const int n_rec = out.has_record ? n : 0;
+  const int n_units = (e->plan_units > 0 && e->units.cap >= static_cast<size_t>(e->plan_units)) ? e->plan_units : 0;
+  if ((host_cost || host_order) && n_rec > cap_tiles)
+    return set_error(RT_E_ARG, "rt_schedule_read: cap_tiles " + std::to_string(cap_tiles) + " < " +
+                                   std::to_string(n_rec) + " tiles");
+  if (host_units && n_units > cap_units)
+    return set_error(RT_E_ARG, "rt_schedule_read: cap_units " + std::to_string(cap_units) + " < " +
+                                   std::to_string(n_units) + " units");
+  HIP_TRY(hipSetDevice(ds->device));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (host_cost && n_rec) HIP_TRY(hipMemcpy(host_cost, e->cost.p, n_rec * sizeof(unsigned), hipMemcpyDeviceToHost));
+  if (host_order && n_rec) HIP_TRY(hipMemcpy(host_order, e->order.p, n_rec * sizeof(int), hipMemcpyDeviceToHost));
+  if (host_units && n_units) HIP_TRY(hipMemcpy(host_units, e->units.p, n_units * sizeof(int2), hipMemcpyDeviceToHost));
+  *info = out;
+  return RT_OK;
+}
+
+// The schedule's sort on the caller's data (diagnostic; no scene): n costs
+// and the order's and units' initial contents go up, enqueue_sort runs on
+// hip_stream as Schedule::sort_record runs it, and the halved costs, the order
+// and the U units come back.
+extern "C" int rt_schedule_sort(int device, uint32_t* host_cost_inout, int n, int32_t* host_order, int U, int smax,
+                                int32_t* host_units, void* hip_stream) {
+  clear_error();
+  if (!host_cost_inout || !host_order || (U > 0 && !host_units))
+    return set_error(RT_E_ARG, "rt_schedule_sort: NULL argument");
+  if (n <= 0) return set_error(RT_E_ARG, "rt_schedule_sort: n must be positive");
+  if (U < 0 || (U != 0 && U < n)) return set_error(RT_E_ARG, "rt_schedule_sort: U must be 0 or at least n");
+  if (smax < 1 || smax > policy::kSplitMax)
+    return set_error(RT_E_ARG, "rt_schedule_sort: smax must be 1 .. " + std::to_string(policy::kSplitMax));
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return set_error(RT_E_NODEV, "rt_schedule_sort: device " + std::to_string(device) + " not available");
+  HIP_TRY(hipSetDevice(device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  DevBuf<unsigned> cost;
+  DevBuf<int> order;
+  DevBuf<int2> units;
+  HIP_TRY(cost.alloc(n));
+  HIP_TRY(order.alloc(n));
+  if (U > 0) HIP_TRY(units.alloc(U));
+  const size_t nb = static_cast<size_t>(n) * 4, ub = static_cast<size_t>(U) * sizeof(int2);
+  HIP_TRY(hipMemcpy(cost.p, host_cost_inout, nb, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(order.p, host_order, nb, hipMemcpyHostToDevice));
+  if (U > 0) HIP_TRY(hipMemcpy(units.p, host_units, ub, hipMemcpyHostToDevice));
+  HIP_TRY(hipDeviceSynchronize());   // (the copies have landed before hip_stream's kernels start)
+  HIP_TRY(enqueue_sort(cost.p, order.p, n, U, smax, units.p, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipMemcpy(host_cost_inout, cost.p, nb, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(host_order, order.p, nb, hipMemcpyDeviceToHost));
+  if (U > 0) HIP_TRY(hipMemcpy(host_units, units.p, ub, hipMemcpyDeviceToHost));
   return RT_OK;
 }
 

@@ -95,6 +95,15 @@ class rt_tree_info(C.Structure):
         return {f: (tuple(getattr(self, f)) if f == "center" else getattr(self, f)) for f, _ in self._fields_}
 
 
+class rt_schedule_info(C.Structure):
+    _fields_ = [("exists", C.c_int32), ("n_tiles", C.c_int32), ("has_record", C.c_int32), ("ready", C.c_int32),
+                ("sort_pending", C.c_int32), ("plan_units", C.c_int32), ("sort_plan", C.c_int32),
+                ("max_streams", C.c_int32)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 # rt_temporal_step's defaults (include/rt.h)
 TEMPORAL_DEFAULTS = dict(max_history=32, sigma_z=0.1, normal_min=0.9)
 
@@ -213,6 +222,10 @@ SIGNATURES = {
     "rt_debug_waves": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.c_size_t]),
     "rt_steal_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "rt_export_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rt_schedule_read": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(rt_schedule_info), C.POINTER(C.c_uint32),
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int]),
+    "rt_schedule_sort": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                   C.POINTER(C.c_int32), C.c_void_p]),
     "rt_device_count": (C.c_int, []),
     "rt_last_error": (C.c_char_p, []),
     "rt_version": (C.c_char_p, []),
@@ -234,7 +247,7 @@ ADDITIVE = {"rt_prepare", "rt_render_u8", "rt_quantize_device", "rt_render_submi
             "rt_temporal_step", "rt_temporal_read", "rt_temporal_host", "rt_temporal_step_motion",
             "rt_temporal_host_motion", "rt_launch_ids", "rt_ids_host", "rt_ids_occupancy", "rt_body_motion",
             "rt_scene_update", "rt_tree_build_host", "rt_tree_refit_host", "rt_tree_cost_host", "rt_scene_tree_info",
-            "rt_scene_tree_read"}
+            "rt_scene_tree_read", "rt_schedule_read", "rt_schedule_sort"}
 
 RT_FEAT_CHANNELS = 8   # rt_feat_resolve's floats per pixel: albedo rgb, normal xyz, depth, coverage
 

@@ -26,8 +26,8 @@ import numpy as np
 from . import hittable, material
 from ._lib import (DENOISE_DEFAULTS, RT_DIELECTRIC, RT_FEAT_CHANNELS, RT_LAMBERTIAN, RT_METAL, RT_NONE,
                    TEMPORAL_DEFAULTS, RTError, check, dptr, fptr, i64ptr, iptr, lib, rt_adapt_opts, rt_camera,
-                   i32ptr, rt_denoise_opts, rt_params, rt_scene, rt_stats, rt_temporal_opts, rt_tree_info, u8ptr, u32ptr,
-                   u64ptr)
+                   i32ptr, rt_denoise_opts, rt_params, rt_scene, rt_schedule_info, rt_stats, rt_temporal_opts,
+                   rt_tree_info, u8ptr, u32ptr, u64ptr)
 
 # ---- scene (raytracing.clj:63-78) --------------------------------------------
 hittables = [
@@ -899,6 +899,48 @@ def body_motion(cur_scene, prev_scene, library=None) -> np.ndarray:
     if code < 0:
         raise RTError(code, dll.rt_last_error().decode(errors="replace"))
     return out
+
+
+def schedule_read(ds, stream=None, arrays: bool = True, library=None):
+    """rt_schedule_read (include/rt.h): the adaptive tile order's entry of the
+    uploaded scene `ds` (a C.c_void_p) on HIP stream `stream` (an address;
+    None: the NULL stream).  Returns (info dict, cost uint32 (n_tiles,), order
+    int32 (n_tiles,), units int32 (plan_units, 2)); the arrays are empty where
+    the entry holds none, and None with arrays=False (info only).  Waits for
+    the stream; changes nothing."""
+    dll = library if library is not None else lib
+    st = C.c_void_p(stream) if stream else None
+    info = rt_schedule_info()
+
+    def ok(code):
+        if code < 0:
+            raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+
+    ok(dll.rt_schedule_read(ds, st, C.byref(info), None, None, None, 0, 0))
+    if not arrays:
+        return info.as_dict(), None, None, None
+    n = info.n_tiles if info.has_record else 0
+    u = max(info.plan_units, 0)
+    cost, order, units = np.zeros(n, np.uint32), np.zeros(n, np.int32), np.zeros((u, 2), np.int32)
+    ok(dll.rt_schedule_read(ds, st, C.byref(info), u32ptr(cost) if n else None, i32ptr(order) if n else None,
+                            i32ptr(units) if u else None, n, u))
+    return info.as_dict(), cost, order, units
+
+
+def schedule_sort(cost, units: int = 0, smax: int = 1, device: int = 0, stream=None, library=None):
+    """rt_schedule_sort (include/rt.h): the schedule's sort kernel, and for
+    units > 0 its split-plan kernel, on `cost` (uint32, one per tile) as a
+    launch runs them.  The order and the units go up filled with -1.  Returns
+    (halved cost uint32 (n,), order int32 (n,), units int32 (units, 2))."""
+    dll = library if library is not None else lib
+    c = np.array(cost, dtype=np.uint32).reshape(-1)
+    order = np.full(c.size, -1, np.int32)
+    tab = np.full((max(int(units), 0), 2), -1, np.int32)
+    code = dll.rt_schedule_sort(int(device), u32ptr(c), c.size, i32ptr(order), int(units), int(smax),
+                                i32ptr(tab) if tab.size else None, C.c_void_p(stream) if stream else None)
+    if code < 0:
+        raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+    return c, order, tab
 
 
 def _spheres(scene) -> np.ndarray:

@@ -132,6 +132,36 @@ def test_argument_errors():
     assert lib.rt_scene_upload(0, C.byref(bad), C.byref(C.c_void_p())) == -1
     assert lib.rt_last_error() != b""
     assert lib.rt_cache_clear() == 0              # nothing cached without a GPU
+    # the schedule's diagnostics: each refusal leaves its message
+    from rtclj._lib import rt_schedule_info
+    info = rt_schedule_info(n_tiles=-9)
+    u, i = (C.c_uint32 * 4)(7, 7, 7, 7), (C.c_int32 * 8)(*([-7] * 8))
+
+    def refused(code, word, status=-1):
+        return code == status and word in lib.rt_last_error()
+
+    assert refused(lib.rt_schedule_read(None, None, C.byref(info), None, None, None, 0, 0), b"NULL")
+    assert refused(lib.rt_schedule_read(C.c_void_p(1), None, None, None, None, None, 0, 0), b"NULL")
+    # a buffer whose cap is too small for any record (checked before the scene is looked at)
+    assert refused(lib.rt_schedule_read(None, None, C.byref(info), u, None, None, 0, 0), b"cap")
+    assert refused(lib.rt_schedule_read(None, None, C.byref(info), None, i, None, -1, 0), b"cap")
+    assert refused(lib.rt_schedule_read(None, None, C.byref(info), None, None, i, 4, 0), b"cap")
+    assert refused(lib.rt_schedule_read(None, None, C.byref(info), None, None, None, 0, -3), b"cap")
+    assert info.n_tiles == -9 and list(u) == [7] * 4 and list(i) == [-7] * 8
+    assert refused(lib.rt_schedule_sort(0, None, 4, i, 0, 1, None, None), b"NULL")
+    assert refused(lib.rt_schedule_sort(0, u, 4, None, 0, 1, None, None), b"NULL")
+    assert refused(lib.rt_schedule_sort(0, u, 4, i, 4, 1, None, None), b"NULL")      # a plan without a table
+    assert refused(lib.rt_schedule_sort(0, u, 0, i, 0, 1, None, None), b"n must be positive")
+    assert refused(lib.rt_schedule_sort(0, u, -4, i, 0, 1, None, None), b"n must be positive")
+    assert refused(lib.rt_schedule_sort(0, u, 4, i, 3, 1, i, None), b"at least n")
+    assert refused(lib.rt_schedule_sort(0, u, 4, i, -1, 1, i, None), b"at least n")
+    assert refused(lib.rt_schedule_sort(0, u, 4, i, 0, 0, None, None), b"smax")
+    assert refused(lib.rt_schedule_sort(0, u, 4, i, 4, 65, i, None), b"smax")
+    assert list(u) == [7] * 4 and list(i) == [-7] * 8
+    if lib.rt_device_count() == 0:                # this machine: well-formed calls meet no device
+        assert refused(lib.rt_schedule_sort(0, u, 4, i, 4, 64, i, None), b"not available", status=-5)
+        assert list(u) == [7] * 4 and list(i) == [-7] * 8
+    assert refused(lib.rt_schedule_sort(-1, u, 4, i, 0, 1, None, None), b"not available", status=-5)
 
 
 def test_rows_out():

@@ -127,19 +127,36 @@ def test_shape_changes_and_row_shards(env):
 
 def test_streams_keep_separate_records(env):
     """Two streams launching the same scene concurrently: each has its own
-    record, and more streams than the record holds run unscheduled."""
+    record, and more streams than the record holds run unscheduled (a freshly
+    uploaded scene, two streams more than its limit: the first `limit` own
+    entries, the last two none, and every frame is exact)."""
+    from rtclj import raytracing as R
     from rtclj import scenes
+    from rtclj._lib import check, lib, rt_params
     torch = env[2]
     sc = env[0]
     w, h = 240, 135
     cam = scenes.cover_camera(w, h)
     want = _render(sc, cam, w, h, 4)
-    streams = [torch.cuda.Stream() for _ in range(10)]
-    for _ in range(2):
-        for s in streams:
-            assert np.array_equal(_launch(env, cam, w, h, 4, stream=s), want)
+    ds = C.c_void_p()
+    check(lib.rt_scene_upload(0, C.byref(sc.c), C.byref(ds)))
+    try:
+        limit = R.schedule_read(ds, None, arrays=False)[0]["max_streams"]
+        assert limit == 16
+        streams = [torch.cuda.Stream() for _ in range(limit + 2)]
+        assert len({s.cuda_stream for s in streams}) == limit + 2
+        for _ in range(2):
+            for s in streams:
+                assert np.array_equal(_launch(env, cam, w, h, 4, stream=s, ds=ds), want)
+        owns = [R.schedule_read(ds, s.cuda_stream, arrays=False)[0] for s in streams]
+        assert [o["exists"] for o in owns] == [1] * limit + [0, 0], owns
+        assert all(o["n_tiles"] == 30 * 17 and o["has_record"] == 1 for o in owns[:limit]), owns
+        assert all(o["n_tiles"] == 0 and o["has_record"] == 0 for o in owns[limit:]), owns
+    finally:
+        torch.cuda.synchronize()
+        lib.rt_scene_free(ds)
+    streams = streams[:2]
     # concurrent: enqueue on both streams before synchronising either
-    from rtclj._lib import check, lib, rt_params
     _, ds, _ = env
     p = rt_params(width=w, height=h, row_begin=0, row_end=h, spp=4, max_depth=50, seed=1)
     outs = []
