@@ -821,7 +821,8 @@ int rt_denoise_host(const rt_denoise_opts* o, const float* half0, const float* h
  * returns its inputs.
  *
  * To know: glass and mirrors are reprojected as their first surface, so what
- * they show lags the camera; the depth is rt_feat's nearest hit over jittered,
+ * they show lags the camera (rt_temporal_step_clamp, below, bounds that lag by
+ * the current frame's colours); the depth is rt_feat's nearest hit over jittered,
  * defocused rays, used as if through the pinhole pixel centre -- that error is
  * what sigma_z absorbs; colour is accumulated modulated, so texture is
  * bilinearly resampled under motion (the scenes here have one albedo per
@@ -901,7 +902,8 @@ int rt_temporal_host(const rt_temporal_opts* o, const rt_camera* cam, const rt_c
  * gamma > 0, so the pixel has no history; only rigid translation is followed
  * (rotation of a sphere of one albedo is invisible); shadows, reflections and
  * what glass shows of a moving body lag, as they already do under camera
- * motion, bounded by max_history; and the id is the pinhole centre's body
+ * motion, bounded by max_history (rt_temporal_step_clamp, below, clamps such
+ * history to the current frame's colour range); and the id is the pinhole centre's body
  * while the depth is rt_feat's nearest hit over jittered rays, so on a
  * silhouette pixel the two can belong to different bodies -- the depth and
  * normal tests are what catch that.
@@ -923,6 +925,71 @@ int rt_temporal_host_motion(const rt_temporal_opts* o, const rt_camera* cam, con
                             const float* prev_a0, const float* prev_a1, const float* prev_guide, const float* prev_len,
                             const int32_t* ids, const float* motion, int n_bodies, float* out0, float* out1,
                             float* out_len);
+
+/* ---- the colour clamp: stale history held to the current frame's colour range ----
+ * raytracing.clj:141-155's frames when what a surface shows changes while the
+ * surface itself stays: the steps above ask whether the surface under a pixel
+ * is the one the history saw, never whether its shading still is.  Here the
+ * fetched history is clamped to a box of the current frame's colours around
+ * the pixel before the blend (Karis 2014; Salvi 2016, variance clipping).
+ * Options (NULL: the defaults; outside the ranges: RT_E_ARG):
+ *   radius  2    1..3            the window is (2 radius + 1)^2 pixels
+ *   gamma   1.0  > 0, may be +inf   half the box's width in sample deviations
+ *
+ * Colour box, per pixel p = (x, y) of the band, from the current half0, half1
+ * and feat only (z = feat[6], n = feat[3..5]; sigma_z and normal_min are the
+ * step's rt_temporal_opts):
+ *   1. Taps (dy, dx), each -radius..radius, dy outer, at q = p + (dx, dy); a
+ *      tap outside the band is skipped before any load.  The centre tap is
+ *      always valid.  Any other tap is valid iff z_p and z_q are both +inf, or
+ *      both are finite and |z_q - z_p| <= sigma_z * z_p and
+ *      (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z >= normal_min.
+ *   2. Over the valid taps in tap order, for half k = 0 then 1, per channel c,
+ *      from 0: s1_c += v, s2_c += v * v (v = half_k[q].c); once per half,
+ *      cnt += 1 (a float).
+ *   3. mean_c = s1_c / cnt, var_c = s2_c / cnt - mean_c * mean_c,
+ *      var_c = var_c > 0 ? var_c : 0, sd_c = sqrt(var_c), e_c = gamma * sd_c,
+ *      lo_c = mean_c - e_c, hi_c = mean_c + e_c.
+ * Step 6 with the clamp: after h0_c = acc0_c / bsum and h1_c = acc1_c / bsum,
+ *   h0_c = h0_c < lo_c ? lo_c : (h0_c > hi_c ? hi_c : h0_c), the same for h1_c
+ * with the same box; the blend, N and the stored L are unchanged.  Pixels
+ * without accepted history do not read the box.  Every line is one fp32
+ * operation rounded once (no fma; / and sqrt IEEE), as above.
+ * gamma = +inf: e is +inf where sd > 0 and NaN where sd == 0; either way both
+ * comparisons are false, so the step's bits are rt_temporal_step's (d_ids ==
+ * NULL) or rt_temporal_step_motion's for every input.
+ *
+ * To know: both halves are clamped to one box, so on clamped pixels their
+ * difference -- rt_denoise's variance -- is understated; the box is gamma
+ * sample deviations wide, so a change smaller than the frame's own noise (a
+ * soft sky-light shadow at 2 + 2 spp) is not caught; near silhouettes the
+ * window keeps few taps and the box is loose.
+ *
+ * rt_temporal_step_clamp (raytracing.clj:141-155, per frame): with d_ids ==
+ * NULL rt_temporal_step's reprojection, arguments and errors (d_motion and
+ * n_bodies are not read); otherwise rt_temporal_step_motion's; plus RT_E_ARG on
+ * a radius outside 1..3 or a gamma that is NaN or <= 0.  The first clamp step
+ * of an rt_temporal allocates its box scratch, 32 bytes a pixel (RT_E_HIP if
+ * that fails); a step with history enqueues the box kernel and then the step
+ * kernel on hip_stream.  A failed call leaves the history and the previous
+ * camera unchanged.  All three step entries work on one rt_temporal and may
+ * alternate. */
+typedef struct rt_temporal_clamp_opts {
+  int radius;
+  float gamma;
+} rt_temporal_clamp_opts;
+int rt_temporal_step_clamp(rt_temporal* t, const rt_temporal_opts* o, const rt_temporal_clamp_opts* k,
+                           const rt_camera* cam, const float* d_half0, const float* d_half1, const float* d_feat,
+                           const int32_t* d_ids, const float* d_motion, int n_bodies, float* d_out0, float* d_out1,
+                           void* hip_stream);
+/* The same step on the host, in plain C++ (no device; raytracing.clj:141-155):
+ * rt_temporal_host_motion's arguments with k after o; ids == NULL:
+ * rt_temporal_host's reprojection (motion and n_bodies are not read). */
+int rt_temporal_host_clamp(const rt_temporal_opts* o, const rt_temporal_clamp_opts* k, const rt_camera* cam,
+                           const rt_camera* prev_cam, int width, int rows, int row0, const float* half0,
+                           const float* half1, const float* feat, const float* prev_a0, const float* prev_a1,
+                           const float* prev_guide, const float* prev_len, const int32_t* ids, const float* motion,
+                           int n_bodies, float* out0, float* out1, float* out_len);
 
 /* ---- moving bodies: an uploaded scene updated in place --------------------------
  * raytracing.clj:63-78's bodies at new centres, without a new rt_scene_upload:

@@ -329,6 +329,21 @@ extern "C" int rt_temporal_host_motion(const rt_temporal_opts* o, const rt_camer
   return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_temporal_host_motion: ") + (why ? why : "failed"));
 }
 
+// rt_temporal_step_clamp on the host (temporal.h's tp_host_step_clamp: either
+// text above with tp_clamp_box's box held against the history in step 6)
+extern "C" int rt_temporal_host_clamp(const rt_temporal_opts* o, const rt_temporal_clamp_opts* k, const rt_camera* cam,
+                                      const rt_camera* prev_cam, int width, int rows, int row0, const float* half0,
+                                      const float* half1, const float* feat, const float* prev_a0,
+                                      const float* prev_a1, const float* prev_guide, const float* prev_len,
+                                      const int32_t* ids, const float* motion, int n_bodies, float* out0, float* out1,
+                                      float* out_len) {
+  clear_error();
+  const char* why = nullptr;
+  const int rc = tp_host_step_clamp(o, k, cam, prev_cam, width, rows, row0, half0, half1, feat, prev_a0, prev_a1,
+                                    prev_guide, prev_len, ids, motion, n_bodies, out0, out1, out_len, &why);
+  return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_temporal_host_clamp: ") + (why ? why : "failed"));
+}
+
 // rt_launch_ids on the host (body_ids.h's ids_host_pass: the pinhole ray, then
 // first_hit.h's scan over the table rt_scene_upload builds)
 extern "C" int rt_ids_host(const rt_scene* s, const rt_camera* c, int width, int rows, int row0, int32_t* out) {

@@ -29,6 +29,13 @@
 // row of a per-body table, by the pixel's id from body_ids.h) and subtracts it
 // in step 2; the MOTION = false instantiation never reads it and is the text
 // above unchanged.  tp_host_step_any and a second kernel carry both.
+// The colour clamp (rt_temporal_step_clamp): tp_clamp_box is
+// one pixel's box from the current frame, read through a `Cur` -- two accessors
+// -- so that the host's arrays and the box kernel's LDS tile share one text;
+// tp_pixel<MOTION, CLAMP> takes the box as a parameter and clamps the fetched
+// history to it in step 6; the CLAMP = false instantiations never read it and
+// are the texts above unchanged.  The box kernel and a clamped step kernel
+// close the file.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -58,6 +65,19 @@ inline const char* tp_opts_error(const rt_temporal_opts& o) {
   if (o.max_history < 1 || o.max_history > kTpMaxHistory) return "max_history outside 1..65536";
   if (!(o.sigma_z > 0.0f) || !(o.sigma_z < INFINITY)) return "sigma_z is not finite and > 0";
   if (!(o.normal_min >= -1.0f) || !(o.normal_min <= 1.0f)) return "normal_min outside -1..1";
+  return nullptr;
+}
+// rt.h's defaults of the clamp
+constexpr int kTpMaxRadius = 3;
+RT_DN_FN rt_temporal_clamp_opts tp_default_clamp_opts() {
+  rt_temporal_clamp_opts k;
+  k.radius = 2;
+  k.gamma = 1.0f;
+  return k;
+}
+inline const char* tp_clamp_opts_error(const rt_temporal_clamp_opts& k) {
+  if (k.radius < 1 || k.radius > kTpMaxRadius) return "radius outside 1..3";
+  if (!(k.gamma > 0.0f)) return "gamma is not > 0";
   return nullptr;
 }
 // nullptr, or what is wrong with an image of rows x width whose first row is
@@ -150,6 +170,64 @@ RT_DN_FN void tp_split(float f, int* i0, float* t) {
   *t = tt;
 }
 
+// The colour box of pixel (x, y) of a rows x width band (rt.h, the clamp):
+// lo, hi (3 floats each) from the current frame's halves and guides over the
+// (2 radius + 1)^2 window.  Cur:
+//   DnGuide guide(int x, int y)                         feat[3..6]
+//   void halves(int x, int y, float* h0, float* h1)     3 floats each
+// called for pixels inside the band only; a tap's guide is read before, and
+// its halves only after, it has passed the surface tests.
+template <class Cur>
+RT_DN_FN void tp_clamp_box(const Cur& cur, int x, int y, int width, int rows, int radius, float sigma_z,
+                           float normal_min, float gamma, float* lo, float* hi) {
+  const DnGuide gp = cur.guide(x, y);
+  const bool pinf = gp.z == INFINITY, pfin = tp_finite(gp.z);
+  const float tol = sigma_z * gp.z;
+  float s1[3] = {0.0f, 0.0f, 0.0f}, s2[3] = {0.0f, 0.0f, 0.0f}, cnt = 0.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int dy = -radius; dy <= radius; ++dy) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int dx = -radius; dx <= radius; ++dx) {
+      // (|d| <= 3: no overflow for any int x, y inside the band)
+      const int qx = x + dx, qy = y + dy;
+      if (qx < 0 || qx >= width || qy < 0 || qy >= rows) continue;
+      if (dx != 0 || dy != 0) {   // (the centre is always valid)
+        const DnGuide g = cur.guide(qx, qy);
+        if (!(pinf && g.z == INFINITY)) {
+          if (!(pfin && tp_finite(g.z))) continue;
+          if (!(dn_abs(g.z - gp.z) <= tol)) continue;
+          const float dot = (gp.nx * g.nx + gp.ny * g.ny) + gp.nz * g.nz;
+          if (!(dot >= normal_min)) continue;
+        }
+      }
+      float h0[3], h1[3];
+      cur.halves(qx, qy, h0, h1);
+      for (int c = 0; c < 3; ++c) {
+        s1[c] += h0[c];
+        s2[c] += h0[c] * h0[c];
+      }
+      cnt += 1.0f;
+      for (int c = 0; c < 3; ++c) {
+        s1[c] += h1[c];
+        s2[c] += h1[c] * h1[c];
+      }
+      cnt += 1.0f;
+    }
+  }
+  for (int c = 0; c < 3; ++c) {
+    const float mean = s1[c] / cnt;
+    float var = s2[c] / cnt - mean * mean;
+    var = var > 0.0f ? var : 0.0f;
+    const float e = gamma * dn_sqrt(var);
+    lo[c] = mean - e;
+    hi[c] = mean + e;
+  }
+}
+
 // One pixel (x, y) of a step: o0, o1 (3 floats each) and the returned length
 // N from the current halves h0, h1 (3 floats each), the current features feat
 // (8 floats) and the history.  Src:
@@ -160,9 +238,11 @@ RT_DN_FN void tp_split(float f, int* i0, float* t) {
 // MOTION (rt_temporal_step_motion): m (3 floats) is the displacement of the
 // pixel's body since the previous frame (tp_motion), subtracted in step 2;
 // without it m is not read and the text is rt_temporal_step's.
-template <bool MOTION, class Src>
+// CLAMP (rt_temporal_step_clamp): box (6 floats: lo rgb, hi rgb; tp_clamp_box)
+// bounds the fetched history in step 6; without it box is not read.
+template <bool MOTION, bool CLAMP = false, class Src>
 RT_DN_FN float tp_pixel(const Src& src, const TpFrame& f, int x, int y, const float* h0, const float* h1,
-                        const float* feat, const float* m, float* o0, float* o1) {
+                        const float* feat, const float* m, float* o0, float* o1, const float* box = nullptr) {
   bool hist = f.have_prev != 0;
   float fx = 0.0f, fy = 0.0f, zexp = INFINITY;
   if (hist) {
@@ -240,7 +320,12 @@ RT_DN_FN float tp_pixel(const Src& src, const TpFrame& f, int x, int y, const fl
     const float n = dn_min(lh + 1.0f, f.max_history);
     const float k = 1.0f / n;
     for (int c = 0; c < 3; ++c) {
-      const float a = acc0[c] / bsum, b = acc1[c] / bsum;
+      float a = acc0[c] / bsum, b = acc1[c] / bsum;
+      if (CLAMP) {   // (NaN bounds -- gamma = +inf over a constant window -- fail both comparisons)
+        const float lo = box[c], hi = box[3 + c];
+        a = a < lo ? lo : (a > hi ? hi : a);
+        b = b < lo ? lo : (b > hi ? hi : b);
+      }
       o0[c] = a + k * (h0[c] - a);
       o1[c] = b + k * (h1[c] - b);
     }
@@ -252,6 +337,25 @@ RT_DN_FN float tp_pixel(const Src& src, const TpFrame& f, int x, int y, const fl
   }
   return 1.0f;
 }
+
+// The current frame as plain arrays (the host): half0, half1 rows x width x 3,
+// feat rows x width x 8.
+struct TpCurPlain {
+  const float *h0, *h1, *feat;
+  int width;
+  size_t at(int x, int y) const { return static_cast<size_t>(y) * width + x; }
+  DnGuide guide(int x, int y) const {
+    const float* ft = feat + RT_FEAT_CHANNELS * at(x, y);
+    return DnGuide{ft[3], ft[4], ft[5], ft[6]};
+  }
+  void halves(int x, int y, float* a, float* b) const {
+    const size_t i = 3 * at(x, y);
+    for (int c = 0; c < 3; ++c) {
+      a[c] = h0[i + c];
+      b[c] = h1[i + c];
+    }
+  }
+};
 
 // The history as plain arrays (the host): a0, a1 rows x width x 3, guide
 // rows x width x 4, len rows x width.
@@ -290,10 +394,12 @@ inline const char* tp_motion_error(const int32_t* ids, const float* motion, int 
   return nullptr;
 }
 
-// rt_temporal_host and rt_temporal_host_motion (rt.h): the checks, then every
-// pixel.  0, or RT_E_ARG with *why set.
-template <bool MOTION>
-inline int tp_host_step_any(const rt_temporal_opts* o, const rt_camera* cam, const rt_camera* prev_cam, int width,
+// rt_temporal_host, rt_temporal_host_motion and rt_temporal_host_clamp (rt.h):
+// the checks, then every pixel.  0, or RT_E_ARG with *why set.  k is looked at
+// with CLAMP only (nullptr: the defaults).
+template <bool MOTION, bool CLAMP = false>
+inline int tp_host_step_any(const rt_temporal_opts* o, const rt_temporal_clamp_opts* k, const rt_camera* cam,
+                            const rt_camera* prev_cam, int width,
                             int rows, int row0, const float* half0, const float* half1, const float* feat,
                             const float* prev_a0, const float* prev_a1, const float* prev_guide, const float* prev_len,
                             const int32_t* ids, const float* motion, int n_bodies, float* out0, float* out1,
@@ -308,6 +414,8 @@ inline int tp_host_step_any(const rt_temporal_opts* o, const rt_camera* cam, con
   if ((*why = tp_shape_error(width, rows, row0)) != nullptr) return RT_E_ARG;
   const rt_temporal_opts opt = o ? *o : tp_default_opts();
   if ((*why = tp_opts_error(opt)) != nullptr) return RT_E_ARG;
+  const rt_temporal_clamp_opts kopt = CLAMP && k ? *k : tp_default_clamp_opts();
+  if (CLAMP && (*why = tp_clamp_opts_error(kopt)) != nullptr) return RT_E_ARG;
   const size_t n_px = static_cast<size_t>(width) * rows, fb = sizeof(float);
   const void* outs[3] = {out0, out1, out_len};
   const size_t out_b[3] = {n_px * 3 * fb, n_px * 3 * fb, n_px * fb};
@@ -337,13 +445,18 @@ inline int tp_host_step_any(const rt_temporal_opts* o, const rt_camera* cam, con
     f.have_prev = 1;
   }
   const TpPlain src{prev_a0, prev_a1, prev_guide, prev_len};
+  const TpCurPlain cur{half0, half1, feat, width};
+  (void)cur;
   for (int y = 0; y < rows; ++y)
     for (int x = 0; x < width; ++x) {
       const size_t i = static_cast<size_t>(y) * width + x;
       const float* ft = feat + RT_FEAT_CHANNELS * i;
-      float m[3] = {0.0f, 0.0f, 0.0f};
+      float m[3] = {0.0f, 0.0f, 0.0f}, box[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
       if (MOTION && tp_finite(ft[6])) tp_motion(ids[i], motion, n_bodies, m);   // (a sky pixel ignores its id)
-      out_len[i] = tp_pixel<MOTION>(src, f, x, y, half0 + 3 * i, half1 + 3 * i, ft, m, out0 + 3 * i, out1 + 3 * i);
+      if (CLAMP && f.have_prev)   // (without a previous camera no pixel has history to clamp)
+        tp_clamp_box(cur, x, y, width, rows, kopt.radius, f.sigma_z, f.normal_min, kopt.gamma, box, box + 3);
+      out_len[i] = tp_pixel<MOTION, CLAMP>(src, f, x, y, half0 + 3 * i, half1 + 3 * i, ft, m, out0 + 3 * i,
+                                           out1 + 3 * i, box);
     }
   return RT_OK;
 }
@@ -351,16 +464,28 @@ inline int tp_host_step(const rt_temporal_opts* o, const rt_camera* cam, const r
                         int rows, int row0, const float* half0, const float* half1, const float* feat,
                         const float* prev_a0, const float* prev_a1, const float* prev_guide, const float* prev_len,
                         float* out0, float* out1, float* out_len, const char** why) {
-  return tp_host_step_any<false>(o, cam, prev_cam, width, rows, row0, half0, half1, feat, prev_a0, prev_a1, prev_guide,
-                                 prev_len, nullptr, nullptr, 0, out0, out1, out_len, why);
+  return tp_host_step_any<false>(o, nullptr, cam, prev_cam, width, rows, row0, half0, half1, feat, prev_a0, prev_a1,
+                                 prev_guide, prev_len, nullptr, nullptr, 0, out0, out1, out_len, why);
 }
 inline int tp_host_step_motion(const rt_temporal_opts* o, const rt_camera* cam, const rt_camera* prev_cam, int width,
                                int rows, int row0, const float* half0, const float* half1, const float* feat,
                                const float* prev_a0, const float* prev_a1, const float* prev_guide,
                                const float* prev_len, const int32_t* ids, const float* motion, int n_bodies,
                                float* out0, float* out1, float* out_len, const char** why) {
-  return tp_host_step_any<true>(o, cam, prev_cam, width, rows, row0, half0, half1, feat, prev_a0, prev_a1, prev_guide,
-                                prev_len, ids, motion, n_bodies, out0, out1, out_len, why);
+  return tp_host_step_any<true>(o, nullptr, cam, prev_cam, width, rows, row0, half0, half1, feat, prev_a0, prev_a1,
+                                prev_guide, prev_len, ids, motion, n_bodies, out0, out1, out_len, why);
+}
+// ids == nullptr: rt_temporal_host's reprojection (motion and n_bodies are not read)
+inline int tp_host_step_clamp(const rt_temporal_opts* o, const rt_temporal_clamp_opts* k, const rt_camera* cam,
+                              const rt_camera* prev_cam, int width, int rows, int row0, const float* half0,
+                              const float* half1, const float* feat, const float* prev_a0, const float* prev_a1,
+                              const float* prev_guide, const float* prev_len, const int32_t* ids, const float* motion,
+                              int n_bodies, float* out0, float* out1, float* out_len, const char** why) {
+  if (!ids)
+    return tp_host_step_any<false, true>(o, k, cam, prev_cam, width, rows, row0, half0, half1, feat, prev_a0, prev_a1,
+                                         prev_guide, prev_len, nullptr, nullptr, 0, out0, out1, out_len, why);
+  return tp_host_step_any<true, true>(o, k, cam, prev_cam, width, rows, row0, half0, half1, feat, prev_a0, prev_a1,
+                                      prev_guide, prev_len, ids, motion, n_bodies, out0, out1, out_len, why);
 }
 
 #if defined(__HIPCC__) && defined(RT_TEMPORAL_KERNEL)
@@ -437,6 +562,108 @@ __global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_motion_kernel(
   if (tp_finite(ft[6])) tp_motion(ids[i], motion, n_bodies, m);
   const TpPacked src{prev_a0, prev_a1, prev_g};
   const float n = tp_pixel<true>(src, f, x, y, h0, h1, ft, m, o0, o1);
+  new_a0[i] = TpWord{o0[0], o0[1], o0[2], n};
+  new_a1[i] = TpWord{o1[0], o1[1], o1[2], 0.0f};
+  new_g[i] = DnGuide{ft[3], ft[4], ft[5], ft[6]};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    out0[i * 3 + c] = o0[c];
+    out1[i * 3 + c] = o1[c];
+  }
+}
+
+// ---- the clamp (rt_temporal_step_clamp) ----
+// The box kernel: a workgroup of kDnBx x kDnBy pixels first stages its pixels
+// and a halo of R around them -- both halves and the four guide floats, 40
+// bytes a pixel: 15,840 bytes at R = 1, 21,760 at R = 2, 28,000 at R = 3 -- in
+// LDS as three arrays of 16-, 16- and 8-byte words, so that a wave's tap is 64
+// consecutive words of each (ds_read_b128, ds_read_b128, ds_read_b64: every
+// 16-lane group of a b128 read and every half-wave of a b64 read covers each
+// bank once).  Cells of the tile that lie outside the band get a NaN depth
+// and are never read (a tap outside the band is skipped before its load).
+template <int R>
+struct TpBoxTile {
+  static constexpr int kW = kDnBx + 2 * R, kH = kDnBy + 2 * R, kN = kW * kH;
+  const DnGuide* g;
+  const float4* a;   // half0 rgb, half1 r
+  const float2* b;   // half1 g, b
+  int x0, y0;        // the band position of the tile's first cell
+  __device__ __forceinline__ int at(int x, int y) const { return (y - y0) * kW + (x - x0); }
+  __device__ __forceinline__ DnGuide guide(int x, int y) const { return g[at(x, y)]; }
+  __device__ __forceinline__ void halves(int x, int y, float* h0, float* h1) const {
+    const int i = at(x, y);
+    const float4 u = a[i];
+    const float2 v = b[i];
+    h0[0] = u.x, h0[1] = u.y, h0[2] = u.z;
+    h1[0] = u.w, h1[1] = v.x, h1[2] = v.y;
+  }
+};
+// Thread (x, y) owns pixel (x, y) and writes its box as two 16-byte words,
+// (lo rgb, 0) into box_lo and (hi rgb, 0) into box_hi (rt_temporal's scratch).
+template <int R>
+__global__ __launch_bounds__(kDnBx* kDnBy) void temporal_box_kernel(
+    const float* __restrict__ half0, const float* __restrict__ half1, const float* __restrict__ feat, int width,
+    int rows, float sigma_z, float normal_min, float gamma, TpWord* __restrict__ box_lo, TpWord* __restrict__ box_hi) {
+  using T = TpBoxTile<R>;
+  __shared__ DnGuide s_g[T::kN];
+  __shared__ float4 s_a[T::kN];
+  __shared__ float2 s_b[T::kN];
+  const int x0 = static_cast<int>(blockIdx.x) * kDnBx - R, y0 = static_cast<int>(blockIdx.y) * kDnBy - R;
+  for (int i = static_cast<int>(threadIdx.y) * kDnBx + static_cast<int>(threadIdx.x); i < T::kN; i += kDnBx * kDnBy) {
+    const int ly = i / T::kW, gx = x0 + (i - ly * T::kW), gy = y0 + ly;
+    if (gx >= 0 && gx < width && gy >= 0 && gy < rows) {
+      const size_t j = static_cast<size_t>(gy) * width + gx;
+      s_g[i] = DnGuide{feat[j * RT_FEAT_CHANNELS + 3], feat[j * RT_FEAT_CHANNELS + 4], feat[j * RT_FEAT_CHANNELS + 5],
+                       feat[j * RT_FEAT_CHANNELS + 6]};
+      s_a[i] = make_float4(half0[j * 3], half0[j * 3 + 1], half0[j * 3 + 2], half1[j * 3]);
+      s_b[i] = make_float2(half1[j * 3 + 1], half1[j * 3 + 2]);
+    } else {
+      s_g[i] = DnGuide{0.0f, 0.0f, 0.0f, NAN};
+    }
+  }
+  __syncthreads();
+  const int x = x0 + R + static_cast<int>(threadIdx.x), y = y0 + R + static_cast<int>(threadIdx.y);
+  if (x >= width || y >= rows) return;
+  const T tile{s_g, s_a, s_b, x0, y0};
+  float lo[3], hi[3];
+  tp_clamp_box(tile, x, y, width, rows, R, sigma_z, normal_min, gamma, lo, hi);
+  const size_t i = static_cast<size_t>(y) * width + x;
+  box_lo[i] = TpWord{lo[0], lo[1], lo[2], 0.0f};
+  box_hi[i] = TpWord{hi[0], hi[1], hi[2], 0.0f};
+}
+
+// rt_temporal_step_clamp's step kernel: temporal_step_kernel's (MOTION = false;
+// ids, motion and n_bodies are not read) or temporal_step_motion_kernel's
+// thread, loads and stores, plus the pixel's own two box words -- loaded only
+// when there is a previous camera: the first step enqueues no box kernel.
+template <bool MOTION>
+__global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_clamp_kernel(
+    const TpFrame f, const float* __restrict__ half0, const float* __restrict__ half1, const float* __restrict__ feat,
+    const int32_t* __restrict__ ids, const float* __restrict__ motion, const int n_bodies,
+    const TpWord* __restrict__ box_lo, const TpWord* __restrict__ box_hi, const TpWord* __restrict__ prev_a0,
+    const TpWord* __restrict__ prev_a1, const DnGuide* __restrict__ prev_g, TpWord* __restrict__ new_a0,
+    TpWord* __restrict__ new_a1, DnGuide* __restrict__ new_g, float* __restrict__ out0, float* __restrict__ out1) {
+  const int x = static_cast<int>(blockIdx.x) * kDnBx + static_cast<int>(threadIdx.x);
+  const int y = static_cast<int>(blockIdx.y) * kDnBy + static_cast<int>(threadIdx.y);
+  if (x >= f.width || y >= f.rows) return;
+  const size_t i = static_cast<size_t>(y) * f.width + x;
+  float h0[3], h1[3], ft[RT_FEAT_CHANNELS], o0[3], o1[3], m[3] = {0.0f, 0.0f, 0.0f};
+  float box[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    h0[c] = half0[i * 3 + c];
+    h1[c] = half1[i * 3 + c];
+  }
+#pragma unroll
+  for (int c = 0; c < RT_FEAT_CHANNELS; ++c) ft[c] = feat[i * RT_FEAT_CHANNELS + c];
+  if (MOTION && tp_finite(ft[6])) tp_motion(ids[i], motion, n_bodies, m);
+  if (f.have_prev) {
+    const TpWord lo = box_lo[i], hi = box_hi[i];
+    box[0] = lo.r, box[1] = lo.g, box[2] = lo.b;
+    box[3] = hi.r, box[4] = hi.g, box[5] = hi.b;
+  }
+  const TpPacked src{prev_a0, prev_a1, prev_g};
+  const float n = tp_pixel<MOTION, true>(src, f, x, y, h0, h1, ft, m, o0, o1, box);
   new_a0[i] = TpWord{o0[0], o0[1], o0[2], n};
   new_a1[i] = TpWord{o1[0], o1[1], o1[2], 0.0f};
   new_g[i] = DnGuide{ft[3], ft[4], ft[5], ft[6]};

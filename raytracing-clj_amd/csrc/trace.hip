@@ -2312,6 +2312,7 @@ struct rt_temporal {
   mutable std::mutex mu;
   DevBuf<TpWord> a0[2], a1[2];
   DevBuf<DnGuide> guide[2];
+  DevBuf<TpWord> box;   // the clamp's scratch: n_px lo words, then n_px hi words (the first clamp step allocates it)
   int cur = 0;
   bool have_prev = false;
   rt_camera prev{};
@@ -2394,12 +2395,15 @@ extern "C" int64_t rt_temporal_frames(const rt_temporal* t) {
   return t->frames;
 }
 
-// rt_temporal_step (motion == false: d_ids, d_motion and n_bodies are not
-// looked at) and rt_temporal_step_motion: the checks, the set-up, one kernel
-template <bool MOTION>
-static int temporal_step(const std::string& me, rt_temporal* t, const rt_temporal_opts* o, const rt_camera* cam,
-                         const float* d_half0, const float* d_half1, const float* d_feat, const int32_t* d_ids,
-                         const float* d_motion, int n_bodies, float* d_out0, float* d_out1, void* hip_stream) {
+// rt_temporal_step (MOTION == false: d_ids, d_motion and n_bodies are not
+// looked at), rt_temporal_step_motion and rt_temporal_step_clamp (CLAMP; k is
+// looked at with it only): the checks, the set-up, one kernel -- with CLAMP
+// and history, the box kernel before it
+template <bool MOTION, bool CLAMP>
+static int temporal_step(const std::string& me, rt_temporal* t, const rt_temporal_opts* o,
+                         const rt_temporal_clamp_opts* k, const rt_camera* cam, const float* d_half0,
+                         const float* d_half1, const float* d_feat, const int32_t* d_ids, const float* d_motion,
+                         int n_bodies, float* d_out0, float* d_out1, void* hip_stream) {
   clear_error();
   if (!t || !cam || !d_half0 || !d_half1 || !d_feat || !d_out0 || !d_out1)
     return set_error(RT_E_ARG, me + ": NULL argument");
@@ -2409,6 +2413,9 @@ static int temporal_step(const std::string& me, rt_temporal* t, const rt_tempora
   }
   const rt_temporal_opts opt = o ? *o : tp_default_opts();
   if (const char* why = tp_opts_error(opt)) return set_error(RT_E_ARG, me + ": " + why);
+  const rt_temporal_clamp_opts kopt = CLAMP && k ? *k : tp_default_clamp_opts();
+  if (CLAMP)
+    if (const char* why = tp_clamp_opts_error(kopt)) return set_error(RT_E_ARG, me + ": " + why);
   const size_t cb = t->n_px * 3 * sizeof(float), fb = t->n_px * RT_FEAT_CHANNELS * sizeof(float);
   const size_t ib = MOTION ? t->n_px * sizeof(int32_t) : 0, mb = MOTION ? static_cast<size_t>(n_bodies) * 4 * sizeof(float) : 0;
   for (const float* d_out : {d_out0, d_out1})
@@ -2426,11 +2433,24 @@ static int temporal_step(const std::string& me, rt_temporal* t, const rt_tempora
   HIP_TRY(hipSetDevice(t->device));
   const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   if (const int rc = tp_stream_check(me, t, stream)) return rc;
+  if (CLAMP && !t->box) HIP_TRY(t->box.alloc(2 * t->n_px));
   const int src = t->cur, dst = t->cur ^ 1;
   const dim3 grid(static_cast<unsigned>((t->width + kDnBx - 1) / kDnBx),
                   static_cast<unsigned>((t->rows + kDnBy - 1) / kDnBy)),
       block(kDnBx, kDnBy);
-  if (MOTION)
+  if (CLAMP) {
+    TpWord *box_lo = t->box.p, *box_hi = t->box.p + t->n_px;
+    const auto box_fn = kopt.radius == 1   ? temporal_box_kernel<1>
+                        : kopt.radius == 2 ? temporal_box_kernel<2>
+                                           : temporal_box_kernel<3>;
+    if (f.have_prev)   // (the first step after create or reset has no history to clamp)
+      HIP_TRY(enqueue(box_fn, grid, block, 0, stream, d_half0, d_half1, d_feat, t->width, t->rows,
+                      f.sigma_z, f.normal_min, kopt.gamma, box_lo, box_hi));
+    HIP_TRY(enqueue(temporal_step_clamp_kernel<MOTION>, grid, block, 0, stream, f, d_half0, d_half1, d_feat, d_ids,
+                    d_motion, n_bodies, static_cast<const TpWord*>(box_lo), static_cast<const TpWord*>(box_hi),
+                    t->a0[src].p, t->a1[src].p, t->guide[src].p, t->a0[dst].p, t->a1[dst].p, t->guide[dst].p, d_out0,
+                    d_out1));
+  } else if (MOTION)
     HIP_TRY(enqueue(temporal_step_motion_kernel, grid, block, 0, stream, f, d_half0, d_half1, d_feat, d_ids, d_motion,
                     n_bodies, t->a0[src].p, t->a1[src].p, t->guide[src].p, t->a0[dst].p, t->a1[dst].p, t->guide[dst].p,
                     d_out0, d_out1));
@@ -2447,16 +2467,30 @@ static int temporal_step(const std::string& me, rt_temporal* t, const rt_tempora
 extern "C" int rt_temporal_step(rt_temporal* t, const rt_temporal_opts* o, const rt_camera* cam, const float* d_half0,
                                 const float* d_half1, const float* d_feat, float* d_out0, float* d_out1,
                                 void* hip_stream) {
-  return temporal_step<false>("rt_temporal_step", t, o, cam, d_half0, d_half1, d_feat, nullptr, nullptr, 0, d_out0, d_out1,
-                              hip_stream);
+  return temporal_step<false, false>("rt_temporal_step", t, o, nullptr, cam, d_half0, d_half1, d_feat, nullptr, nullptr,
+                                     0, d_out0, d_out1, hip_stream);
 }
 
 extern "C" int rt_temporal_step_motion(rt_temporal* t, const rt_temporal_opts* o, const rt_camera* cam,
                                        const float* d_half0, const float* d_half1, const float* d_feat,
                                        const int32_t* d_ids, const float* d_motion, int n_bodies, float* d_out0,
                                        float* d_out1, void* hip_stream) {
-  return temporal_step<true>("rt_temporal_step_motion", t, o, cam, d_half0, d_half1, d_feat, d_ids, d_motion, n_bodies,
-                             d_out0, d_out1, hip_stream);
+  return temporal_step<true, false>("rt_temporal_step_motion", t, o, nullptr, cam, d_half0, d_half1, d_feat, d_ids,
+                                    d_motion, n_bodies, d_out0, d_out1, hip_stream);
+}
+
+// raytracing.clj:141-155's frames with the fetched history held to the current
+// frame's colour box (rt.h); d_ids == NULL: rt_temporal_step's reprojection
+extern "C" int rt_temporal_step_clamp(rt_temporal* t, const rt_temporal_opts* o, const rt_temporal_clamp_opts* k,
+                                      const rt_camera* cam, const float* d_half0, const float* d_half1,
+                                      const float* d_feat, const int32_t* d_ids, const float* d_motion, int n_bodies,
+                                      float* d_out0, float* d_out1, void* hip_stream) {
+  const std::string me("rt_temporal_step_clamp");
+  if (!d_ids)
+    return temporal_step<false, true>(me, t, o, k, cam, d_half0, d_half1, d_feat, nullptr, nullptr, 0, d_out0, d_out1,
+                                      hip_stream);
+  return temporal_step<true, true>(me, t, o, k, cam, d_half0, d_half1, d_feat, d_ids, d_motion, n_bodies, d_out0,
+                                   d_out1, hip_stream);
 }
 
 extern "C" int rt_temporal_read(const rt_temporal* t, float* host_a0, float* host_a1, float* host_guide,

@@ -86,6 +86,10 @@ class rt_temporal_opts(C.Structure):
     _fields_ = [("max_history", C.c_int), ("sigma_z", C.c_float), ("normal_min", C.c_float)]
 
 
+class rt_temporal_clamp_opts(C.Structure):
+    _fields_ = [("radius", C.c_int), ("gamma", C.c_float)]
+
+
 class rt_tree_info(C.Structure):
     _fields_ = [("n_nodes", C.c_int), ("off_pairs", C.c_int), ("off_pidx", C.c_int), ("blob_bytes", C.c_int),
                 ("big_pair0", C.c_int), ("n_big_leaves", C.c_int), ("depth", C.c_int), ("leaf_size", C.c_int),
@@ -106,6 +110,8 @@ class rt_schedule_info(C.Structure):
 
 # rt_temporal_step's defaults (include/rt.h)
 TEMPORAL_DEFAULTS = dict(max_history=32, sigma_z=0.1, normal_min=0.9)
+# rt_temporal_step_clamp's defaults (include/rt.h)
+TEMPORAL_CLAMP_DEFAULTS = dict(radius=2, gamma=1.0)
 
 
 # symbol -> (restype, argtypes); every function include/rt.h declares
@@ -200,6 +206,13 @@ SIGNATURES = {
     "rt_temporal_host_motion": (C.c_int, [C.POINTER(rt_temporal_opts), C.POINTER(rt_camera), C.POINTER(rt_camera),
                                           C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 7 +
                                 [C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int] + [C.POINTER(C.c_float)] * 3),
+    "rt_temporal_step_clamp": (C.c_int, [C.c_void_p, C.POINTER(rt_temporal_opts), C.POINTER(rt_temporal_clamp_opts),
+                                         C.POINTER(rt_camera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_temporal_host_clamp": (C.c_int, [C.POINTER(rt_temporal_opts), C.POINTER(rt_temporal_clamp_opts),
+                                         C.POINTER(rt_camera), C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int] +
+                               [C.POINTER(C.c_float)] * 7 + [C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int] +
+                               [C.POINTER(C.c_float)] * 3),
     "rt_launch_ids": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rt_ids_host": (C.c_int, [C.POINTER(rt_scene), C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int,
                               C.POINTER(C.c_int32)]),
@@ -245,7 +258,7 @@ ADDITIVE = {"rt_prepare", "rt_render_u8", "rt_quantize_device", "rt_render_submi
             "rt_denoiser_create", "rt_denoiser_free", "rt_denoise", "rt_denoise_profile",
             "rt_denoise_host", "rt_temporal_create", "rt_temporal_free", "rt_temporal_reset", "rt_temporal_frames",
             "rt_temporal_step", "rt_temporal_read", "rt_temporal_host", "rt_temporal_step_motion",
-            "rt_temporal_host_motion", "rt_launch_ids", "rt_ids_host", "rt_ids_occupancy", "rt_body_motion",
+            "rt_temporal_host_motion", "rt_temporal_step_clamp", "rt_temporal_host_clamp", "rt_launch_ids", "rt_ids_host", "rt_ids_occupancy", "rt_body_motion",
             "rt_scene_update", "rt_tree_build_host", "rt_tree_refit_host", "rt_tree_cost_host", "rt_scene_tree_info",
             "rt_scene_tree_read", "rt_schedule_read", "rt_schedule_sort"}
 

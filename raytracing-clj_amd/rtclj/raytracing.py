@@ -25,9 +25,9 @@ import numpy as np
 
 from . import hittable, material
 from ._lib import (DENOISE_DEFAULTS, RT_DIELECTRIC, RT_FEAT_CHANNELS, RT_LAMBERTIAN, RT_METAL, RT_NONE,
-                   TEMPORAL_DEFAULTS, RTError, check, dptr, fptr, i64ptr, iptr, lib, rt_adapt_opts, rt_camera,
-                   i32ptr, rt_denoise_opts, rt_params, rt_scene, rt_schedule_info, rt_stats, rt_temporal_opts,
-                   rt_tree_info, u8ptr, u32ptr, u64ptr)
+                   TEMPORAL_CLAMP_DEFAULTS, TEMPORAL_DEFAULTS, RTError, check, dptr, fptr, i64ptr, iptr, lib,
+                   rt_adapt_opts, rt_camera, i32ptr, rt_denoise_opts, rt_params, rt_scene, rt_schedule_info, rt_stats,
+                   rt_temporal_clamp_opts, rt_temporal_opts, rt_tree_info, u8ptr, u32ptr, u64ptr)
 
 # ---- scene (raytracing.clj:63-78) --------------------------------------------
 hittables = [
@@ -641,8 +641,16 @@ def _temporal_opts(opts: dict) -> rt_temporal_opts:
                             normal_min=float(o["normal_min"]))
 
 
+def _temporal_clamp_opts(clamp: dict) -> rt_temporal_clamp_opts:
+    unknown = set(clamp) - set(TEMPORAL_CLAMP_DEFAULTS)
+    if unknown:
+        raise TypeError(f"temporal clamp: unknown option(s) {sorted(unknown)}")
+    k = {**TEMPORAL_CLAMP_DEFAULTS, **clamp}
+    return rt_temporal_clamp_opts(radius=int(k["radius"]), gamma=float(k["gamma"]))
+
+
 def temporal_host(cam: rt_camera, prev_cam, half0, half1, feat, prev=None, row0: int = 0, library=None, ids=None,
-                  motion=None, **opts):
+                  motion=None, clamp=None, **opts):
     """rt_temporal_host (include/rt.h): one step of temporal accumulation on the
     host, in plain C++ -- the bits Temporal.step gives on the device.  half0,
     half1: float32 (rows, width, 3); feat: float32 (rows, width, 8); cam: the
@@ -652,7 +660,10 @@ def temporal_host(cam: rt_camera, prev_cam, half0, half1, feat, prev=None, row0:
     history.  Options: max_history, sigma_z, normal_min.  With `ids` (int32
     (rows, width), as ids_host gives them) it is rt_temporal_host_motion:
     `motion` (float32 (n_bodies, 4), as body_motion gives it; None: no body
-    moved) is subtracted for the pixel's body.  Returns (out0, out1, length):
+    moved) is subtracted for the pixel's body.  With `clamp` (a dict of radius
+    and gamma; {}: the defaults) it is rt_temporal_host_clamp: the fetched
+    history is held to the current frame's colour box, with or without ids.
+    Returns (out0, out1, length):
     the new history's halves and its length; its guides are feat[..., 3:7]."""
     dll = library if library is not None else lib
     half0 = np.ascontiguousarray(half0, np.float32)
@@ -674,10 +685,15 @@ def temporal_host(cam: rt_camera, prev_cam, half0, half1, feat, prev=None, row0:
     o = _temporal_opts(opts)
     head = (C.byref(o), C.byref(cam), C.byref(prev_cam) if prev_cam is not None else None, width, rows, int(row0),
             fptr(half0), fptr(half1), fptr(feat), *(fptr(a) if a is not None else None for a in hist))
+    k = None if clamp is None else _temporal_clamp_opts(clamp)
+    outs = (fptr(out0), fptr(out1), fptr(length))
     if ids is None:
         if motion is not None:
             raise ValueError("temporal_host: motion comes with ids")
-        code = dll.rt_temporal_host(*head, fptr(out0), fptr(out1), fptr(length))
+        if k is None:
+            code = dll.rt_temporal_host(*head, *outs)
+        else:
+            code = dll.rt_temporal_host_clamp(head[0], C.byref(k), *head[1:], None, None, 0, *outs)
     else:
         ids = np.ascontiguousarray(ids, np.int32)
         if ids.shape != (rows, width):
@@ -685,8 +701,11 @@ def temporal_host(cam: rt_camera, prev_cam, half0, half1, feat, prev=None, row0:
         motion = np.zeros((0, 4), np.float32) if motion is None else np.ascontiguousarray(motion, np.float32)
         if motion.ndim != 2 or motion.shape[1] != 4:
             raise ValueError("temporal_host: motion must be float32 (n_bodies, 4)")
-        code = dll.rt_temporal_host_motion(*head, i32ptr(ids), fptr(motion) if len(motion) else None, len(motion),
-                                           fptr(out0), fptr(out1), fptr(length))
+        tail = (i32ptr(ids), fptr(motion) if len(motion) else None, len(motion), *outs)
+        if k is None:
+            code = dll.rt_temporal_host_motion(*head, *tail)
+        else:
+            code = dll.rt_temporal_host_clamp(head[0], C.byref(k), *head[1:], *tail)
     if code < 0:
         raise RTError(code, dll.rt_last_error().decode(errors="replace"))
     return out0, out1, length
@@ -726,17 +745,25 @@ class Temporal:
         return int(self._dll.rt_temporal_frames(self._tp))
 
     def step(self, cam: rt_camera, d_half0: int, d_half1: int, d_feat: int, d_out0: int, d_out1: int, stream=None,
-             d_ids=None, d_motion=None, n_bodies: int = 0, **opts) -> None:
+             d_ids=None, d_motion=None, n_bodies: int = 0, clamp=None, **opts) -> None:
         """Enqueue one step (rt_temporal_step) on device addresses; options as
         temporal_host.  With `d_ids` (int32 (rows, width) on the device, as
         body_ids_into writes them) it is rt_temporal_step_motion: `d_motion`
         is body_motion's table on the device (n_bodies x 4 float32, 16-byte
-        aligned).  Both kinds of step may alternate on one object."""
+        aligned).  With `clamp` (a dict of radius and gamma; {}: the defaults)
+        it is rt_temporal_step_clamp, with or without d_ids.  All kinds of step
+        may alternate on one object."""
         o = _temporal_opts(opts)
         st = C.c_void_p(stream) if stream else None
-        if d_ids is None:
-            if d_motion is not None or n_bodies:
-                raise ValueError("Temporal.step: d_motion and n_bodies come with d_ids")
+        if d_ids is None and (d_motion is not None or n_bodies):
+            raise ValueError("Temporal.step: d_motion and n_bodies come with d_ids")
+        if clamp is not None:
+            k = _temporal_clamp_opts(clamp)
+            self._check(self._dll.rt_temporal_step_clamp(
+                self._tp, C.byref(o), C.byref(k), C.byref(cam), C.c_void_p(d_half0), C.c_void_p(d_half1),
+                C.c_void_p(d_feat), C.c_void_p(d_ids) if d_ids is not None else None,
+                C.c_void_p(d_motion) if d_motion else None, int(n_bodies), C.c_void_p(d_out0), C.c_void_p(d_out1), st))
+        elif d_ids is None:
             self._check(self._dll.rt_temporal_step(self._tp, C.byref(o), C.byref(cam), C.c_void_p(d_half0),
                                                    C.c_void_p(d_half1), C.c_void_p(d_feat), C.c_void_p(d_out0),
                                                    C.c_void_p(d_out1), st))
@@ -776,7 +803,7 @@ class Temporal:
 
 
 def render_sequence(scene, cameras, width: int, height: int, spp: int = 4, max_depth: int = 50, seed: int = 1,
-                    flags: int = 0, library=None, temporal=None, stages: bool = False, **opts):
+                    flags: int = 0, library=None, temporal=None, stages: bool = False, clamp=None, **opts):
     """A sequence of low-sample frames of a static scene, one per camera of
     `cameras`, each temporally accumulated and then denoised, on device 0: a
     generator that yields float32 (height, width, 3) per camera.  Per frame f:
@@ -784,7 +811,9 @@ def render_sequence(scene, cameras, width: int, height: int, spp: int = 4, max_d
     that no frame repeats another's samples), the first-hit features of all
     spp, everything resolved on the device, Temporal.step, Denoiser.run on the
     accumulated halves.  `spp` must be even.  `temporal`: options of the step
-    (max_history, sigma_z, normal_min); further keywords: the denoiser's.  With
+    (max_history, sigma_z, normal_min); `clamp`: None, or the colour clamp's
+    options (radius, gamma; {}: the defaults) for rt_temporal_step_clamp;
+    further keywords: the denoiser's.  With
     `stages` it yields (denoised, half0, half1, feat, acc0, acc1) instead: the
     resolves and the step's outputs beside the frame.  The device buffers are
     torch's (import torch before rtclj, as render_denoised)."""
@@ -793,6 +822,9 @@ def render_sequence(scene, cameras, width: int, height: int, spp: int = 4, max_d
     _denoise_opts(opts)
     topts = dict(temporal or {})
     _temporal_opts(topts)
+    if clamp is not None:
+        _temporal_clamp_opts(clamp)
+        topts["clamp"] = dict(clamp)
     import torch
     if not torch.cuda.is_available():
         raise RTError(-5, "render_sequence: torch sees no GPU (import torch before rtclj)")
@@ -1086,7 +1118,8 @@ def _same_but_centres(a: Scene, b: Scene) -> bool:
 
 
 def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max_depth: int = 50, seed: int = 1,
-                     flags: int = 0, library=None, temporal=None, stages: bool = False, refit: bool = False, **opts):
+                     flags: int = 0, library=None, temporal=None, stages: bool = False, refit: bool = False, clamp=None,
+                     **opts):
     """render_sequence for bodies that move: one Scene per frame (all with the
     same body count), zipped with `cameras`; a generator that yields float32
     (height, width, 3) per frame, on device 0.  Per frame f: the scene's upload
@@ -1099,7 +1132,8 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
     first-hit features of all spp, the body ids (rt_launch_ids), body_motion
     against the previous frame's scene (frame 0: no displacement), the
     motion-aware step (rt_temporal_step_motion) and Denoiser.run.  `spp` must be
-    even; `temporal` and further keywords as render_sequence.  With `stages` it
+    even; `temporal`, `clamp` (with it the step is rt_temporal_step_clamp with
+    the ids) and further keywords as render_sequence.  With `stages` it
     yields (denoised, half0, half1, feat, acc0, acc1, ids).  With identical
     scenes it gives render_sequence's bits."""
     if spp <= 0 or spp % 2:
@@ -1107,6 +1141,9 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
     _denoise_opts(opts)
     topts = dict(temporal or {})
     _temporal_opts(topts)
+    if clamp is not None:
+        _temporal_clamp_opts(clamp)
+        topts["clamp"] = dict(clamp)
     import torch
     if not torch.cuda.is_available():
         raise RTError(-5, "render_animation: torch sees no GPU (import torch before rtclj)")
