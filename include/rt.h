@@ -991,6 +991,149 @@ int rt_temporal_host_clamp(const rt_temporal_opts* o, const rt_temporal_clamp_op
                            const float* prev_guide, const float* prev_len, const int32_t* ids, const float* motion,
                            int n_bodies, float* out0, float* out1, float* out_len);
 
+/* ---- the sample budget: samples where the temporal history is short ---------------
+ * raytracing.clj:141-155's frames when the samples of a frame are not spread
+ * evenly: a pixel that carries 32 frames of history gains little from the
+ * samples a pixel disoccluded this frame needs badly.  Four parts: the probe
+ * asks, before anything is traced, how much history the coming step will
+ * accept per pixel; the plan turns that into a sample multiplier per 8 x 8 tile;
+ * rt_budget traces the plan into two half accumulators with one read-back per
+ * frame; and the weighted step tells the history that a tile's halves hold
+ * `mult` frames' worth of samples, so that the next blend weights them so.
+ *
+ * 1. The probe.  Per pixel, from the *coming* frame's features, ids and motion,
+ * the camera that drew them, and t's current history and previous camera:
+ * steps 1-5 of the step above (2' when d_ids != NULL, the plain step 2
+ * otherwise; sigma_z and normal_min from the same rt_temporal_opts), then
+ *   len = accL / bsum if the pixel has history and bsum >= 0.25, else 0.
+ * With no previous camera (the first step after create or reset) len = 0
+ * everywhere.  Colours are never loaded: of the history only L and the guides
+ * of the taps with L >= 1 are read.  It is the step's own text, so for any
+ * later step on the same inputs the stored length is min(len + wt,
+ * max_history) bit for bit (wt = 1: N).  Nothing is modified.
+ *
+ * rt_temporal_probe (raytracing.clj:141-155, before a frame): asynchronous, on
+ * hip_stream of t's device; d_len (device, rows x width floats) is written,
+ * every element.  rt_temporal_step_motion's errors: a NULL argument (d_ids may
+ * be NULL: then d_motion and n_bodies are not read), bad options, n_bodies < 0,
+ * a NULL or not 16-byte aligned d_motion with n_bodies > 0, d_len overlapping
+ * an input, a stream of another device, a degenerate previous camera.  A
+ * failed call changes nothing. */
+int rt_temporal_probe(const rt_temporal* t, const rt_temporal_opts* o, const rt_camera* cam, const float* d_feat,
+                      const int32_t* d_ids, const float* d_motion, int n_bodies, float* d_len, void* hip_stream);
+/* The same on the host, in plain C++ (no device; raytracing.clj:141-155):
+ * rt_temporal_host_motion's arguments without the halves, prev_a0, prev_a1 and
+ * the colour outputs.  prev_cam == NULL: out_len = 0 (prev_guide and prev_len
+ * are not read).  ids == NULL: the plain reprojection. */
+int rt_temporal_host_probe(const rt_temporal_opts* o, const rt_camera* cam, const rt_camera* prev_cam, int width,
+                           int rows, int row0, const float* feat, const float* prev_guide, const float* prev_len,
+                           const int32_t* ids, const float* motion, int n_bodies, float* out_len);
+
+/* 2. The plan.  From any rows x width float length image, a multiplier
+ * mult[ty * gx + tx] in 1 .. max_mult per 8 x 8 tile of the band; tiles as
+ * rt_adapt's: gx = ceil(width / 8), gy = ceil(rows / 8), row-major; a tile's
+ * pixels are those inside the band, npx of them.
+ * Options (no defaults for half_spp; outside the ranges: RT_E_ARG):
+ *   half_spp     -    >= 1     samples of one block: a tile gets 2 mult blocks
+ *   target       8    1..32    frames of history a tile is brought up to
+ *   max_mult     8    1..16    cap on the multiplier
+ *   quantile_64  16   1..64    the share of a tile's pixels, in 64ths, that decides
+ * and 2 * max_mult * half_spp <= RT_MAX_SPP.
+ * Rule, all in integers: for j = 1 .. target, c_j = the number of the tile's
+ * pixels with !(len >= float(j)) (a NaN counts as short); j* = the smallest j
+ * with c_j * 64 >= quantile_64 * npx; mult = min(max(target - (j* - 1), 1),
+ * max_mult); if no j qualifies, mult = 1.  In words: a tile gets what brings
+ * the shortest quantile_64 / 64 of its pixels up to `target` frames.
+ * rt_budget_plan_host (raytracing.clj:141-155, before a frame; plain C++, no
+ * device): mult (gy x gx) from len.  RT_E_ARG on a NULL argument, bad options,
+ * width or rows <= 0. */
+typedef struct rt_budget_opts {
+  int half_spp, target, max_mult, quantile_64;
+} rt_budget_opts;
+int rt_budget_plan_host(const rt_budget_opts* o, const float* len, int width, int rows, uint32_t* mult);
+
+/* 3. The budgeted frame.  An rt_budget owns two u64 sum buffers H0 and H1 in
+ * rt_adapt's layout, the per-tile mult and counts (= 2 mult half_spp), one
+ * device list of all tiles by descending mult (the order among equal
+ * multipliers is unspecified: no bit depends on it) and, in page-locked host
+ * memory, the prefix counts n_j = #{tiles with mult > j}, j = 0 .. max_mult - 1
+ * (n_0 = every tile), the frame's only read-back.
+ * Contract: after rt_budget_trace every tile of H0 + H1 equals, integer for
+ * integer, that tile of one rt_launch_accum at spp = 2 mult half_spp from
+ * p->sample_begin, and H_h is the sum of that tile's sample blocks 2 j + h
+ * (block b: indices sample_begin + b half_spp ...), j = 0 .. mult - 1.
+ * max_mult = 1 gives two uniform accumulators of half_spp each.
+ * To know: the first frame of a sequence has no history and is planned at
+ * min(target, max_mult) everywhere -- plan it with rt_budget_plan_mult and ones
+ * to avoid that; successive frames must advance sample_begin by 2 max_mult
+ * half_spp.
+ *
+ * rt_budget_create (raytracing.clj:141-155, the loop's state): for frames of
+ * `shape` (read and checked as rt_accum_create does) on ds's device; it holds
+ * no reference to ds.  RT_E_ARG on a NULL argument, bad options, a tile_step
+ * other than 0 (the band must be contiguous) or more than 65535 rows. */
+typedef struct rt_budget rt_budget;
+int rt_budget_create(const rt_dscene* ds, const rt_params* shape, const rt_budget_opts* opts, rt_budget** out);
+int rt_budget_free(rt_budget* bd);   /* NULL: 0 */
+/* raytracing.clj:141-155, a frame's start: on hip_stream, H0 = H1 = 0, the plan
+ * kernels on d_len (device, rows x width floats, as rt_temporal_probe writes
+ * them) and the read-back of the n_j.  Asynchronous. */
+int rt_budget_plan(rt_budget* bd, const float* d_len, void* hip_stream);
+/* The same from the caller's own gy x gx uint32 multipliers on the device (an
+ * importance or foveation map): the values are clamped to 1 .. max_mult on the
+ * device before anything indexes by them. */
+int rt_budget_plan_mult(rt_budget* bd, const uint32_t* d_mult, void* hip_stream);
+/* raytracing.clj:141-155's samples, as planned: waits for the plan's read-back,
+ * then for pass j = 0 .. max_mult - 1 with n_j > 0 and half h = 0, 1 enqueues
+ * rt_adapt_step's kind of pass over the list's first n_j tiles into H_h, with
+ * spp = half_spp and sample indices p->sample_begin + (2 j + h) half_spp ...;
+ * p->spp is ignored.  Returns the number of launches.  RT_E_ARG without a
+ * fresh plan (one trace per plan), when ds's device or p's shape differ from
+ * bd's, when p->sample_begin + 2 max_mult half_spp would pass 2^31 - 1, or when
+ * the variant has no 8 x 8 tiles (rt_adapt_step's rule); the frame and the plan
+ * are unchanged then.  The stream's tile-cost record (rt_set_schedule) is
+ * neither read nor written.  d_counters as rt_launch_accum's. */
+int rt_budget_trace(const rt_dscene* ds, const rt_camera* c, const rt_params* p, rt_budget* bd, uint64_t* d_counters,
+                    void* hip_stream);
+/* compute-pixel's accum / spp per tile (raytracing.clj:155): rt_adapt_resolve's
+ * and rt_adapt_resolve_half's conversions with this frame's counts. */
+int rt_budget_resolve(const rt_budget* bd, int flags, float* d_out, void* hip_stream);
+int rt_budget_resolve_half(const rt_budget* bd, int half, int flags, float* d_out, void* hip_stream);
+/* raytracing.clj:141-155's accum, both halves, as rt_adapt_read; the gy x gx
+ * multipliers of the current plan copied to host_mult; and where they lie on
+ * the device (for rt_temporal_step_budget; valid until rt_budget_free, rewritten
+ * by the next plan).  The reads return when the data is there. */
+int rt_budget_read(const rt_budget* bd, uint64_t* host_sums0, uint64_t* host_sums1, void* hip_stream);
+int rt_budget_mult_read(const rt_budget* bd, uint32_t* host_mult, void* hip_stream);
+int rt_budget_device_mult(const rt_budget* bd, const uint32_t** d_mult);
+/* raytracing.clj:141-155's counter: the sum over the tiles of npx * 2 * mult *
+ * half_spp of the current plan (waits for its read-back); 0 before a plan. */
+int64_t rt_budget_samples(rt_budget* bd);
+
+/* 4. The weighted step.  rt_temporal_step_clamp with d_mult (device, gy x gx
+ * uint32: the tiles of the band as above) after n_bodies.  Per pixel (x, y),
+ *   wt = float(min(max(mult[(y / 8) * gx + x / 8], 1), 16)),
+ * and step 6 becomes: with history N = min(Lh + wt, float(max_history)),
+ * k = wt / N; without history out = half and N = min(wt, float(max_history)).
+ * Everything else is unchanged: steps 1-5, the clamp, 2' with ids, and what is
+ * stored.  With every multiplier 1 the bits are rt_temporal_step_clamp's:
+ * 1.0f / N and Lh + 1.0f are the same operations.  With gamma = +inf no box
+ * kernel is enqueued (the bits are equal, as shown above).  L now counts
+ * base-frame equivalents, which is what the plan's `target` is measured in.
+ * rt_temporal_step_clamp's errors, plus RT_E_ARG on a NULL d_mult or an output
+ * overlapping it (raytracing.clj:141-155, per frame). */
+int rt_temporal_step_budget(rt_temporal* t, const rt_temporal_opts* o, const rt_temporal_clamp_opts* k,
+                            const rt_camera* cam, const float* d_half0, const float* d_half1, const float* d_feat,
+                            const int32_t* d_ids, const float* d_motion, int n_bodies, const uint32_t* d_mult,
+                            float* d_out0, float* d_out1, void* hip_stream);
+/* The same step on the host, in plain C++ (no device; raytracing.clj:141-155):
+ * rt_temporal_host_clamp's arguments with mult (gy x gx) after n_bodies. */
+int rt_temporal_host_budget(const rt_temporal_opts* o, const rt_temporal_clamp_opts* k, const rt_camera* cam,
+                            const rt_camera* prev_cam, int width, int rows, int row0, const float* half0,
+                            const float* half1, const float* feat, const float* prev_a0, const float* prev_a1,
+                            const float* prev_guide, const float* prev_len, const int32_t* ids, const float* motion,
+                            int n_bodies, const uint32_t* mult, float* out0, float* out1, float* out_len);
+
 /* ---- moving bodies: an uploaded scene updated in place --------------------------
  * raytracing.clj:63-78's bodies at new centres, without a new rt_scene_upload:
  * the scene's trees keep their topology and are refitted on the device.

@@ -36,6 +36,7 @@
 #include "first_hit.h"
 #include "rt_internal.h"
 #include "temporal.h"
+#include "budget.h"
 
 namespace rtclj {
 
@@ -342,6 +343,43 @@ extern "C" int rt_temporal_host_clamp(const rt_temporal_opts* o, const rt_tempor
   const int rc = tp_host_step_clamp(o, k, cam, prev_cam, width, rows, row0, half0, half1, feat, prev_a0, prev_a1,
                                     prev_guide, prev_len, ids, motion, n_bodies, out0, out1, out_len, &why);
   return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_temporal_host_clamp: ") + (why ? why : "failed"));
+}
+
+// rt_temporal_probe on the host (temporal.h's tp_host_probe: steps 1-5 of
+// tp_pixel, the text the probe kernel runs)
+extern "C" int rt_temporal_host_probe(const rt_temporal_opts* o, const rt_camera* cam, const rt_camera* prev_cam,
+                                      int width, int rows, int row0, const float* feat, const float* prev_guide,
+                                      const float* prev_len, const int32_t* ids, const float* motion, int n_bodies,
+                                      float* out_len) {
+  clear_error();
+  const char* why = nullptr;
+  const int rc = tp_host_probe(o, cam, prev_cam, width, rows, row0, feat, prev_guide, prev_len, ids, motion, n_bodies,
+                               out_len, &why);
+  return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_temporal_host_probe: ") + (why ? why : "failed"));
+}
+
+// rt_temporal_step_budget on the host (temporal.h's tp_host_step_budget: the
+// clamped step with the tiles' weights in step 6)
+extern "C" int rt_temporal_host_budget(const rt_temporal_opts* o, const rt_temporal_clamp_opts* k, const rt_camera* cam,
+                                       const rt_camera* prev_cam, int width, int rows, int row0, const float* half0,
+                                       const float* half1, const float* feat, const float* prev_a0,
+                                       const float* prev_a1, const float* prev_guide, const float* prev_len,
+                                       const int32_t* ids, const float* motion, int n_bodies, const uint32_t* mult,
+                                       float* out0, float* out1, float* out_len) {
+  clear_error();
+  const char* why = nullptr;
+  const int rc = tp_host_step_budget(o, k, cam, prev_cam, width, rows, row0, half0, half1, feat, prev_a0, prev_a1,
+                                     prev_guide, prev_len, ids, motion, n_bodies, mult, out0, out1, out_len, &why);
+  return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_temporal_host_budget: ") + (why ? why : "failed"));
+}
+
+// rt_budget_plan on the host (budget.h's bd_host_plan: bd_tile_mult, the text
+// the plan kernel runs)
+extern "C" int rt_budget_plan_host(const rt_budget_opts* o, const float* len, int width, int rows, uint32_t* mult) {
+  clear_error();
+  const char* why = nullptr;
+  const int rc = bd_host_plan(o, len, width, rows, mult, &why);
+  return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_budget_plan_host: ") + (why ? why : "failed"));
 }
 
 // rt_launch_ids on the host (body_ids.h's ids_host_pass: the pinhole ray, then

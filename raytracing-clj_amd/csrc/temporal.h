@@ -36,6 +36,13 @@
 // history to it in step 6; the CLAMP = false instantiations never read it and
 // are the texts above unchanged.  The box kernel and a clamped step kernel
 // close the file.
+// The budget (rt_temporal_probe, rt_temporal_step_budget):
+// tp_pixel<.., WEIGHT> takes the frame's weight wt (tp_weight of the tile's
+// sample multiplier) into step 6, and tp_pixel<.., PROBE> is steps 1-5 alone --
+// no colour is read or written, the returned float is the history length the
+// step would accept.  The WEIGHT = PROBE = false instantiations are the texts
+// above unchanged.  tp_host_probe, the probe kernel and the weighted step
+// kernel carry them.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -240,9 +247,17 @@ RT_DN_FN void tp_clamp_box(const Cur& cur, int x, int y, int width, int rows, in
 // without it m is not read and the text is rt_temporal_step's.
 // CLAMP (rt_temporal_step_clamp): box (6 floats: lo rgb, hi rgb; tp_clamp_box)
 // bounds the fetched history in step 6; without it box is not read.
-template <bool MOTION, bool CLAMP = false, class Src>
+// WEIGHT (rt_temporal_step_budget): the current halves stand for wt frames'
+// worth of samples (tp_weight), so step 6 adds wt to the length and blends with
+// k = wt / N; without it wt is not read.
+// PROBE (rt_temporal_probe): steps 1-5 only -- h0, h1, o0, o1 and box are not
+// touched; of the history only Src's hist_len(i) and the guides of the taps
+// with L >= 1 are read -- and the return is Lh = accL / bsum where the step
+// would accept the history, else 0.
+template <bool MOTION, bool CLAMP = false, bool WEIGHT = false, bool PROBE = false, class Src>
 RT_DN_FN float tp_pixel(const Src& src, const TpFrame& f, int x, int y, const float* h0, const float* h1,
-                        const float* feat, const float* m, float* o0, float* o1, const float* box = nullptr) {
+                        const float* feat, const float* m, float* o0, float* o1, const float* box = nullptr,
+                        float wt = 1.0f) {
   bool hist = f.have_prev != 0;
   float fx = 0.0f, fy = 0.0f, zexp = INFINITY;
   if (hist) {
@@ -293,7 +308,9 @@ RT_DN_FN float tp_pixel(const Src& src, const TpFrame& f, int x, int y, const fl
         const int qx = x0 + dx, qy = y0 + dy;
         if (b == 0.0f || qx < 0 || qx >= f.width || qy < 0 || qy >= f.rows) continue;
         const size_t q = static_cast<size_t>(qy) * f.width + qx;
-        const TpWord a = src.w0(q);
+        TpWord a{0.0f, 0.0f, 0.0f, 0.0f};
+        if (PROBE) a.l = src.hist_len(q);
+        else a = src.w0(q);
         if (!(a.l >= 1.0f)) continue;
         const DnGuide g = src.guide(q);
         if (!(pinf && g.z == INFINITY)) {
@@ -302,23 +319,26 @@ RT_DN_FN float tp_pixel(const Src& src, const TpFrame& f, int x, int y, const fl
           const float dot = (feat[3] * g.nx + feat[4] * g.ny) + feat[5] * g.nz;
           if (!(dot >= f.normal_min)) continue;
         }
-        const TpWord a1 = src.w1(q);
-        acc0[0] += b * a.r;
-        acc0[1] += b * a.g;
-        acc0[2] += b * a.b;
-        acc1[0] += b * a1.r;
-        acc1[1] += b * a1.g;
-        acc1[2] += b * a1.b;
+        if (!PROBE) {
+          const TpWord a1 = src.w1(q);
+          acc0[0] += b * a.r;
+          acc0[1] += b * a.g;
+          acc0[2] += b * a.b;
+          acc1[0] += b * a1.r;
+          acc1[1] += b * a1.g;
+          acc1[2] += b * a1.b;
+        }
         accl += b * a.l;
         bsum += b;
       }
     }
   }
+  if (PROBE) return (hist && bsum >= 0.25f) ? accl / bsum : 0.0f;
   // 6. the blend
   if (hist && bsum >= 0.25f) {
     const float lh = accl / bsum;
-    const float n = dn_min(lh + 1.0f, f.max_history);
-    const float k = 1.0f / n;
+    const float n = dn_min(WEIGHT ? lh + wt : lh + 1.0f, f.max_history);
+    const float k = WEIGHT ? wt / n : 1.0f / n;
     for (int c = 0; c < 3; ++c) {
       float a = acc0[c] / bsum, b = acc1[c] / bsum;
       if (CLAMP) {   // (NaN bounds -- gamma = +inf over a constant window -- fail both comparisons)
@@ -335,7 +355,20 @@ RT_DN_FN float tp_pixel(const Src& src, const TpFrame& f, int x, int y, const fl
     o0[c] = h0[c];
     o1[c] = h1[c];
   }
-  return 1.0f;
+  return WEIGHT ? dn_min(wt, f.max_history) : 1.0f;
+}
+
+// The weight of a frame whose tile was traced at `mult` times the base rate
+// (rt.h, the weighted step): float(min(max(mult, 1), 16)).
+constexpr uint32_t kTpMaxWeight = 16u;
+RT_DN_FN float tp_weight(uint32_t mult) {
+  return static_cast<float>(mult < 1u ? 1u : (mult > kTpMaxWeight ? kTpMaxWeight : mult));
+}
+// ... of pixel (x, y) of the band: its 8 x 8 tile's entry of the gy x gx table
+constexpr int kTpTile = 8;
+RT_DN_FN float tp_weight_at(const uint32_t* mult, int width, int x, int y) {
+  const int gx = (width + kTpTile - 1) / kTpTile;
+  return tp_weight(mult[static_cast<size_t>(y / kTpTile) * gx + x / kTpTile]);
 }
 
 // The current frame as plain arrays (the host): half0, half1 rows x width x 3,
@@ -363,6 +396,7 @@ struct TpPlain {
   const float *a0, *a1, *g, *len;
   TpWord w0(size_t i) const { return TpWord{a0[3 * i], a0[3 * i + 1], a0[3 * i + 2], len[i]}; }
   TpWord w1(size_t i) const { return TpWord{a1[3 * i], a1[3 * i + 1], a1[3 * i + 2], 0.0f}; }
+  float hist_len(size_t i) const { return len[i]; }   // (the probe: a0 and a1 may be nullptr)
   DnGuide guide(size_t i) const { return DnGuide{g[4 * i], g[4 * i + 1], g[4 * i + 2], g[4 * i + 3]}; }
 };
 
@@ -396,16 +430,18 @@ inline const char* tp_motion_error(const int32_t* ids, const float* motion, int 
 
 // rt_temporal_host, rt_temporal_host_motion and rt_temporal_host_clamp (rt.h):
 // the checks, then every pixel.  0, or RT_E_ARG with *why set.  k is looked at
-// with CLAMP only (nullptr: the defaults).
-template <bool MOTION, bool CLAMP = false>
+// with CLAMP only (nullptr: the defaults).  WEIGHT (rt_temporal_host_budget):
+// mult is the band's gy x gx table of sample multipliers; without it mult is
+// not looked at.
+template <bool MOTION, bool CLAMP = false, bool WEIGHT = false>
 inline int tp_host_step_any(const rt_temporal_opts* o, const rt_temporal_clamp_opts* k, const rt_camera* cam,
                             const rt_camera* prev_cam, int width,
                             int rows, int row0, const float* half0, const float* half1, const float* feat,
                             const float* prev_a0, const float* prev_a1, const float* prev_guide, const float* prev_len,
                             const int32_t* ids, const float* motion, int n_bodies, float* out0, float* out1,
-                            float* out_len, const char** why) {
+                            float* out_len, const char** why, const uint32_t* mult = nullptr) {
   *why = nullptr;
-  if (!cam || !half0 || !half1 || !feat || !out0 || !out1 || !out_len ||
+  if (!cam || !half0 || !half1 || !feat || !out0 || !out1 || !out_len || (WEIGHT && !mult) ||
       (prev_cam && (!prev_a0 || !prev_a1 || !prev_guide || !prev_len))) {
     *why = "NULL argument";
     return RT_E_ARG;
@@ -419,13 +455,16 @@ inline int tp_host_step_any(const rt_temporal_opts* o, const rt_temporal_clamp_o
   const size_t n_px = static_cast<size_t>(width) * rows, fb = sizeof(float);
   const void* outs[3] = {out0, out1, out_len};
   const size_t out_b[3] = {n_px * 3 * fb, n_px * 3 * fb, n_px * fb};
-  const void* ins[9] = {half0,      half1,    feat, prev_a0, prev_a1,
-                        prev_guide, prev_len, MOTION ? ids : nullptr, MOTION ? motion : nullptr};
-  const size_t in_b[9] = {n_px * 3 * fb, n_px * 3 * fb, n_px * RT_FEAT_CHANNELS * fb,
-                          n_px * 3 * fb, n_px * 3 * fb, n_px * 4 * fb,
-                          n_px * fb,     n_px * sizeof(int32_t), static_cast<size_t>(MOTION ? n_bodies : 0) * 4 * fb};
+  const size_t n_tiles = static_cast<size_t>((width + kTpTile - 1) / kTpTile) * ((rows + kTpTile - 1) / kTpTile);
+  const void* ins[10] = {half0,      half1,    feat, prev_a0, prev_a1,
+                         prev_guide, prev_len, MOTION ? ids : nullptr, MOTION ? motion : nullptr,
+                         WEIGHT ? mult : nullptr};
+  const size_t in_b[10] = {n_px * 3 * fb, n_px * 3 * fb, n_px * RT_FEAT_CHANNELS * fb,
+                           n_px * 3 * fb, n_px * 3 * fb, n_px * 4 * fb,
+                           n_px * fb,     n_px * sizeof(int32_t), static_cast<size_t>(MOTION ? n_bodies : 0) * 4 * fb,
+                           n_tiles * sizeof(uint32_t)};
   for (int a = 0; a < 3; ++a) {
-    for (int b = 0; b < 9; ++b)
+    for (int b = 0; b < 10; ++b)
       if ((b < 3 || b > 6 || prev_cam) && tp_overlap(outs[a], out_b[a], ins[b], in_b[b])) {
         *why = "an output overlaps an input";
         return RT_E_ARG;
@@ -455,8 +494,8 @@ inline int tp_host_step_any(const rt_temporal_opts* o, const rt_temporal_clamp_o
       if (MOTION && tp_finite(ft[6])) tp_motion(ids[i], motion, n_bodies, m);   // (a sky pixel ignores its id)
       if (CLAMP && f.have_prev)   // (without a previous camera no pixel has history to clamp)
         tp_clamp_box(cur, x, y, width, rows, kopt.radius, f.sigma_z, f.normal_min, kopt.gamma, box, box + 3);
-      out_len[i] = tp_pixel<MOTION, CLAMP>(src, f, x, y, half0 + 3 * i, half1 + 3 * i, ft, m, out0 + 3 * i,
-                                           out1 + 3 * i, box);
+      out_len[i] = tp_pixel<MOTION, CLAMP, WEIGHT>(src, f, x, y, half0 + 3 * i, half1 + 3 * i, ft, m, out0 + 3 * i,
+                                                   out1 + 3 * i, box, WEIGHT ? tp_weight_at(mult, width, x, y) : 1.0f);
     }
   return RT_OK;
 }
@@ -487,6 +526,78 @@ inline int tp_host_step_clamp(const rt_temporal_opts* o, const rt_temporal_clamp
   return tp_host_step_any<true, true>(o, k, cam, prev_cam, width, rows, row0, half0, half1, feat, prev_a0, prev_a1,
                                       prev_guide, prev_len, ids, motion, n_bodies, out0, out1, out_len, why);
 }
+// rt_temporal_host_budget (rt.h): rt_temporal_host_clamp's step with the tiles'
+// weights in step 6.  gamma = +inf clamps nothing (rt.h), so the box is not
+// built then.
+inline int tp_host_step_budget(const rt_temporal_opts* o, const rt_temporal_clamp_opts* k, const rt_camera* cam,
+                               const rt_camera* prev_cam, int width, int rows, int row0, const float* half0,
+                               const float* half1, const float* feat, const float* prev_a0, const float* prev_a1,
+                               const float* prev_guide, const float* prev_len, const int32_t* ids, const float* motion,
+                               int n_bodies, const uint32_t* mult, float* out0, float* out1, float* out_len,
+                               const char** why) {
+  if (k && (*why = tp_clamp_opts_error(*k)) != nullptr) return RT_E_ARG;
+  const bool box = !(k && k->gamma == INFINITY);
+#define RT_TP_BUDGET(MOTION, CLAMP, IDS, MOT, NB)                                                                     \
+  tp_host_step_any<MOTION, CLAMP, true>(o, k, cam, prev_cam, width, rows, row0, half0, half1, feat, prev_a0, prev_a1, \
+                                        prev_guide, prev_len, IDS, MOT, NB, out0, out1, out_len, why, mult)
+  if (!ids) return box ? RT_TP_BUDGET(false, true, nullptr, nullptr, 0) : RT_TP_BUDGET(false, false, nullptr, nullptr, 0);
+  return box ? RT_TP_BUDGET(true, true, ids, motion, n_bodies) : RT_TP_BUDGET(true, false, ids, motion, n_bodies);
+#undef RT_TP_BUDGET
+}
+
+// rt_temporal_host_probe (rt.h): the checks, then steps 1-5 of every pixel.
+// ids == nullptr: the plain step 2 (motion and n_bodies are not read).
+template <bool MOTION>
+inline int tp_host_probe_any(const rt_temporal_opts* o, const rt_camera* cam, const rt_camera* prev_cam, int width,
+                             int rows, int row0, const float* feat, const float* prev_guide, const float* prev_len,
+                             const int32_t* ids, const float* motion, int n_bodies, float* out_len, const char** why) {
+  *why = nullptr;
+  if (!cam || !feat || !out_len || (prev_cam && (!prev_guide || !prev_len))) {
+    *why = "NULL argument";
+    return RT_E_ARG;
+  }
+  if (MOTION && (*why = tp_motion_error(ids, motion, n_bodies)) != nullptr) return RT_E_ARG;
+  if ((*why = tp_shape_error(width, rows, row0)) != nullptr) return RT_E_ARG;
+  const rt_temporal_opts opt = o ? *o : tp_default_opts();
+  if ((*why = tp_opts_error(opt)) != nullptr) return RT_E_ARG;
+  const size_t n_px = static_cast<size_t>(width) * rows, fb = sizeof(float);
+  const void* ins[5] = {feat, prev_cam ? prev_guide : nullptr, prev_cam ? prev_len : nullptr, MOTION ? ids : nullptr,
+                        MOTION ? motion : nullptr};
+  const size_t in_b[5] = {n_px * RT_FEAT_CHANNELS * fb, n_px * 4 * fb, n_px * fb, n_px * sizeof(int32_t),
+                          static_cast<size_t>(MOTION ? n_bodies : 0) * 4 * fb};
+  for (int b = 0; b < 5; ++b)
+    if (tp_overlap(out_len, n_px * fb, ins[b], in_b[b])) {
+      *why = "the output overlaps an input";
+      return RT_E_ARG;
+    }
+  TpFrame f = tp_frame(opt, *cam, width, rows, row0);
+  if (prev_cam) {
+    if (!tp_setup(*cam, *prev_cam, f.R, f.dc)) {
+      *why = "the previous camera is degenerate (det is 0 or not finite)";
+      return RT_E_ARG;
+    }
+    f.have_prev = 1;
+  }
+  const TpPlain src{nullptr, nullptr, prev_guide, prev_len};
+  for (int y = 0; y < rows; ++y)
+    for (int x = 0; x < width; ++x) {
+      const size_t i = static_cast<size_t>(y) * width + x;
+      const float* ft = feat + RT_FEAT_CHANNELS * i;
+      float m[3] = {0.0f, 0.0f, 0.0f};
+      if (MOTION && tp_finite(ft[6])) tp_motion(ids[i], motion, n_bodies, m);
+      out_len[i] = tp_pixel<MOTION, false, false, true>(src, f, x, y, nullptr, nullptr, ft, m, nullptr, nullptr);
+    }
+  return RT_OK;
+}
+inline int tp_host_probe(const rt_temporal_opts* o, const rt_camera* cam, const rt_camera* prev_cam, int width,
+                         int rows, int row0, const float* feat, const float* prev_guide, const float* prev_len,
+                         const int32_t* ids, const float* motion, int n_bodies, float* out_len, const char** why) {
+  if (!ids)
+    return tp_host_probe_any<false>(o, cam, prev_cam, width, rows, row0, feat, prev_guide, prev_len, nullptr, nullptr, 0,
+                                    out_len, why);
+  return tp_host_probe_any<true>(o, cam, prev_cam, width, rows, row0, feat, prev_guide, prev_len, ids, motion, n_bodies,
+                                 out_len, why);
+}
 
 #if defined(__HIPCC__) && defined(RT_TEMPORAL_KERNEL)
 // -------------------------------------------------------------- the kernel ----
@@ -497,6 +608,7 @@ struct TpPacked {
   const DnGuide* g;
   __device__ __forceinline__ TpWord w0(size_t i) const { return a0[i]; }
   __device__ __forceinline__ TpWord w1(size_t i) const { return a1[i]; }
+  __device__ __forceinline__ float hist_len(size_t i) const { return a0[i].l; }   // (one dword of the word)
   __device__ __forceinline__ DnGuide guide(size_t i) const { return g[i]; }
 };
 
@@ -664,6 +776,79 @@ __global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_clamp_kernel(
   }
   const TpPacked src{prev_a0, prev_a1, prev_g};
   const float n = tp_pixel<MOTION, true>(src, f, x, y, h0, h1, ft, m, o0, o1, box);
+  new_a0[i] = TpWord{o0[0], o0[1], o0[2], n};
+  new_a1[i] = TpWord{o1[0], o1[1], o1[2], 0.0f};
+  new_g[i] = DnGuide{ft[3], ft[4], ft[5], ft[6]};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    out0[i * 3 + c] = o0[c];
+    out1[i * 3 + c] = o1[c];
+  }
+}
+
+// ---- the budget (rt_temporal_probe, rt_temporal_step_budget) ----
+// rt_temporal_probe's kernel: the step kernels' thread and workgroup shape;
+// a thread loads its pixel's four guide floats of the current features (the
+// albedo and the coverage are not read), its body id and table row as the
+// motion kernel does, and of the history the lengths of its taps (the .l dword
+// of the a0 word) and, for the taps with L >= 1, their guides as 16-byte words
+// -- the gather of the step without its two colour words a tap -- and stores
+// one float.
+template <bool MOTION>
+__global__ __launch_bounds__(kDnBx* kDnBy) void temporal_probe_kernel(
+    const TpFrame f, const float* __restrict__ feat, const int32_t* __restrict__ ids, const float* __restrict__ motion,
+    const int n_bodies, const TpWord* __restrict__ prev_a0, const DnGuide* __restrict__ prev_g,
+    float* __restrict__ out_len) {
+  const int x = static_cast<int>(blockIdx.x) * kDnBx + static_cast<int>(threadIdx.x);
+  const int y = static_cast<int>(blockIdx.y) * kDnBy + static_cast<int>(threadIdx.y);
+  if (x >= f.width || y >= f.rows) return;
+  const size_t i = static_cast<size_t>(y) * f.width + x;
+  if (!f.have_prev) {   // (uniform: the first step after create or reset)
+    out_len[i] = 0.0f;
+    return;
+  }
+  float ft[RT_FEAT_CHANNELS] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, m[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int c = 3; c < 7; ++c) ft[c] = feat[i * RT_FEAT_CHANNELS + c];
+  if (MOTION && tp_finite(ft[6])) tp_motion(ids[i], motion, n_bodies, m);
+  const TpPacked src{prev_a0, nullptr, prev_g};
+  out_len[i] = tp_pixel<MOTION, false, false, true>(src, f, x, y, nullptr, nullptr, ft, m, nullptr, nullptr);
+}
+
+// rt_temporal_step_budget's step kernel: temporal_step_clamp_kernel's thread,
+// loads and stores, plus one dword of the tile's multiplier (a wave's 64
+// pixels lie in eight tiles of one tile row: eight dwords, one cache line).
+// BOX = false (gamma = +inf, which clamps nothing: rt.h): no box is read.
+template <bool MOTION, bool BOX>
+__global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_budget_kernel(
+    const TpFrame f, const float* __restrict__ half0, const float* __restrict__ half1, const float* __restrict__ feat,
+    const int32_t* __restrict__ ids, const float* __restrict__ motion, const int n_bodies,
+    const uint32_t* __restrict__ mult, const TpWord* __restrict__ box_lo, const TpWord* __restrict__ box_hi,
+    const TpWord* __restrict__ prev_a0, const TpWord* __restrict__ prev_a1, const DnGuide* __restrict__ prev_g,
+    TpWord* __restrict__ new_a0, TpWord* __restrict__ new_a1, DnGuide* __restrict__ new_g, float* __restrict__ out0,
+    float* __restrict__ out1) {
+  const int x = static_cast<int>(blockIdx.x) * kDnBx + static_cast<int>(threadIdx.x);
+  const int y = static_cast<int>(blockIdx.y) * kDnBy + static_cast<int>(threadIdx.y);
+  if (x >= f.width || y >= f.rows) return;
+  const size_t i = static_cast<size_t>(y) * f.width + x;
+  float h0[3], h1[3], ft[RT_FEAT_CHANNELS], o0[3], o1[3], m[3] = {0.0f, 0.0f, 0.0f};
+  float box[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    h0[c] = half0[i * 3 + c];
+    h1[c] = half1[i * 3 + c];
+  }
+#pragma unroll
+  for (int c = 0; c < RT_FEAT_CHANNELS; ++c) ft[c] = feat[i * RT_FEAT_CHANNELS + c];
+  if (MOTION && tp_finite(ft[6])) tp_motion(ids[i], motion, n_bodies, m);
+  if (BOX && f.have_prev) {
+    const TpWord lo = box_lo[i], hi = box_hi[i];
+    box[0] = lo.r, box[1] = lo.g, box[2] = lo.b;
+    box[3] = hi.r, box[4] = hi.g, box[5] = hi.b;
+  }
+  const float wt = tp_weight_at(mult, f.width, x, y);
+  const TpPacked src{prev_a0, prev_a1, prev_g};
+  const float n = tp_pixel<MOTION, BOX, true>(src, f, x, y, h0, h1, ft, m, o0, o1, box, wt);
   new_a0[i] = TpWord{o0[0], o0[1], o0[2], n};
   new_a1[i] = TpWord{o1[0], o1[1], o1[2], 0.0f};
   new_g[i] = DnGuide{ft[3], ft[4], ft[5], ft[6]};

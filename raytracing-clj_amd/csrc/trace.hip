@@ -15,7 +15,9 @@
 // the body-id pass (body_ids.h, rt_launch_ids) stands behind the feature pass
 // and the motion-aware step beside rt_temporal_step;
 // rt_scene_update and the refit kernel (bvh_refit.h) are the last section
-// (DESIGN.md §3.11).
+// (DESIGN.md §3.11).  The sample budget (budget.h's plan kernels, the rt_budget
+// entries, rt_temporal_probe and rt_temporal_step_budget) stands behind the
+// rt_temporal entries.
 #include "trace_kernel.h"
 #define RT_FIRST_HIT_KERNEL
 #include "first_hit.h"
@@ -23,6 +25,8 @@
 #include "denoise.h"
 #define RT_TEMPORAL_KERNEL
 #include "temporal.h"
+#define RT_BUDGET_KERNEL
+#include "budget.h"
 #define RT_BODY_IDS_KERNEL
 #include "body_ids.h"
 #define RT_REFIT_KERNEL
@@ -2398,14 +2402,17 @@ extern "C" int64_t rt_temporal_frames(const rt_temporal* t) {
 // rt_temporal_step (MOTION == false: d_ids, d_motion and n_bodies are not
 // looked at), rt_temporal_step_motion and rt_temporal_step_clamp (CLAMP; k is
 // looked at with it only): the checks, the set-up, one kernel -- with CLAMP
-// and history, the box kernel before it
-template <bool MOTION, bool CLAMP>
+// and history, the box kernel before it.  WEIGHT (rt_temporal_step_budget):
+// d_mult is the band's gy x gx multipliers, and CLAMP then says whether the
+// box is built (k is checked either way); without it d_mult is not looked at.
+template <bool MOTION, bool CLAMP, bool WEIGHT = false>
 static int temporal_step(const std::string& me, rt_temporal* t, const rt_temporal_opts* o,
                          const rt_temporal_clamp_opts* k, const rt_camera* cam, const float* d_half0,
                          const float* d_half1, const float* d_feat, const int32_t* d_ids, const float* d_motion,
-                         int n_bodies, float* d_out0, float* d_out1, void* hip_stream) {
+                         int n_bodies, float* d_out0, float* d_out1, void* hip_stream,
+                         const uint32_t* d_mult = nullptr) {
   clear_error();
-  if (!t || !cam || !d_half0 || !d_half1 || !d_feat || !d_out0 || !d_out1)
+  if (!t || !cam || !d_half0 || !d_half1 || !d_feat || !d_out0 || !d_out1 || (WEIGHT && !d_mult))
     return set_error(RT_E_ARG, me + ": NULL argument");
   if (MOTION) {
     if (const char* why = tp_motion_error(d_ids, d_motion, n_bodies)) return set_error(RT_E_ARG, me + ": " + why);
@@ -2413,14 +2420,17 @@ static int temporal_step(const std::string& me, rt_temporal* t, const rt_tempora
   }
   const rt_temporal_opts opt = o ? *o : tp_default_opts();
   if (const char* why = tp_opts_error(opt)) return set_error(RT_E_ARG, me + ": " + why);
-  const rt_temporal_clamp_opts kopt = CLAMP && k ? *k : tp_default_clamp_opts();
-  if (CLAMP)
+  const rt_temporal_clamp_opts kopt = (CLAMP || WEIGHT) && k ? *k : tp_default_clamp_opts();
+  if (CLAMP || WEIGHT)
     if (const char* why = tp_clamp_opts_error(kopt)) return set_error(RT_E_ARG, me + ": " + why);
   const size_t cb = t->n_px * 3 * sizeof(float), fb = t->n_px * RT_FEAT_CHANNELS * sizeof(float);
+  const size_t wb = !WEIGHT ? 0
+                            : static_cast<size_t>((t->width + kTpTile - 1) / kTpTile) * ((t->rows + kTpTile - 1) / kTpTile) *
+                                  sizeof(uint32_t);
   const size_t ib = MOTION ? t->n_px * sizeof(int32_t) : 0, mb = MOTION ? static_cast<size_t>(n_bodies) * 4 * sizeof(float) : 0;
   for (const float* d_out : {d_out0, d_out1})
     if (tp_overlap(d_out, cb, d_half0, cb) || tp_overlap(d_out, cb, d_half1, cb) || tp_overlap(d_out, cb, d_feat, fb) ||
-        tp_overlap(d_out, cb, d_ids, ib) || tp_overlap(d_out, cb, d_motion, mb))
+        tp_overlap(d_out, cb, d_ids, ib) || tp_overlap(d_out, cb, d_motion, mb) || tp_overlap(d_out, cb, d_mult, wb))
       return set_error(RT_E_ARG, me + ": an output overlaps an input");
   if (tp_overlap(d_out0, cb, d_out1, cb)) return set_error(RT_E_ARG, me + ": the outputs overlap");
   std::lock_guard<std::mutex> lk(t->mu);
@@ -2446,11 +2456,22 @@ static int temporal_step(const std::string& me, rt_temporal* t, const rt_tempora
     if (f.have_prev)   // (the first step after create or reset has no history to clamp)
       HIP_TRY(enqueue(box_fn, grid, block, 0, stream, d_half0, d_half1, d_feat, t->width, t->rows,
                       f.sigma_z, f.normal_min, kopt.gamma, box_lo, box_hi));
-    HIP_TRY(enqueue(temporal_step_clamp_kernel<MOTION>, grid, block, 0, stream, f, d_half0, d_half1, d_feat, d_ids,
-                    d_motion, n_bodies, static_cast<const TpWord*>(box_lo), static_cast<const TpWord*>(box_hi),
-                    t->a0[src].p, t->a1[src].p, t->guide[src].p, t->a0[dst].p, t->a1[dst].p, t->guide[dst].p, d_out0,
-                    d_out1));
-  } else if (MOTION)
+    if (WEIGHT)
+      HIP_TRY(enqueue(temporal_step_budget_kernel<MOTION, true>, grid, block, 0, stream, f, d_half0, d_half1, d_feat,
+                      d_ids, d_motion, n_bodies, d_mult, static_cast<const TpWord*>(box_lo),
+                      static_cast<const TpWord*>(box_hi), t->a0[src].p, t->a1[src].p, t->guide[src].p, t->a0[dst].p,
+                      t->a1[dst].p, t->guide[dst].p, d_out0, d_out1));
+    else
+      HIP_TRY(enqueue(temporal_step_clamp_kernel<MOTION>, grid, block, 0, stream, f, d_half0, d_half1, d_feat, d_ids,
+                      d_motion, n_bodies, static_cast<const TpWord*>(box_lo), static_cast<const TpWord*>(box_hi),
+                      t->a0[src].p, t->a1[src].p, t->guide[src].p, t->a0[dst].p, t->a1[dst].p, t->guide[dst].p, d_out0,
+                      d_out1));
+  } else if (WEIGHT)
+    HIP_TRY(enqueue(temporal_step_budget_kernel<MOTION, false>, grid, block, 0, stream, f, d_half0, d_half1, d_feat,
+                    d_ids, d_motion, n_bodies, d_mult, static_cast<const TpWord*>(nullptr),
+                    static_cast<const TpWord*>(nullptr), t->a0[src].p, t->a1[src].p, t->guide[src].p, t->a0[dst].p,
+                    t->a1[dst].p, t->guide[dst].p, d_out0, d_out1));
+  else if (MOTION)
     HIP_TRY(enqueue(temporal_step_motion_kernel, grid, block, 0, stream, f, d_half0, d_half1, d_feat, d_ids, d_motion,
                     n_bodies, t->a0[src].p, t->a1[src].p, t->guide[src].p, t->a0[dst].p, t->a1[dst].p, t->guide[dst].p,
                     d_out0, d_out1));
@@ -2527,6 +2548,291 @@ extern "C" int rt_temporal_read(const rt_temporal* t, float* host_a0, float* hos
     }
   }
   return RT_OK;
+}
+
+static int stream_on_device(const std::string& me, hipStream_t stream, int device);   // (below)
+
+// ---- the sample budget (rt.h, budget.h, temporal.h) ----------
+// rt_temporal_step_budget: rt_temporal_step_clamp's step with the tiles'
+// weights; gamma = +inf clamps nothing (rt.h), so no box is built then.
+extern "C" int rt_temporal_step_budget(rt_temporal* t, const rt_temporal_opts* o, const rt_temporal_clamp_opts* k,
+                                       const rt_camera* cam, const float* d_half0, const float* d_half1,
+                                       const float* d_feat, const int32_t* d_ids, const float* d_motion, int n_bodies,
+                                       const uint32_t* d_mult, float* d_out0, float* d_out1, void* hip_stream) {
+  const std::string me("rt_temporal_step_budget");
+  const bool box = !(k && k->gamma == INFINITY);
+  if (!d_ids)
+    return box ? temporal_step<false, true, true>(me, t, o, k, cam, d_half0, d_half1, d_feat, nullptr, nullptr, 0, d_out0,
+                                                  d_out1, hip_stream, d_mult)
+               : temporal_step<false, false, true>(me, t, o, k, cam, d_half0, d_half1, d_feat, nullptr, nullptr, 0,
+                                                   d_out0, d_out1, hip_stream, d_mult);
+  return box ? temporal_step<true, true, true>(me, t, o, k, cam, d_half0, d_half1, d_feat, d_ids, d_motion, n_bodies,
+                                               d_out0, d_out1, hip_stream, d_mult)
+             : temporal_step<true, false, true>(me, t, o, k, cam, d_half0, d_half1, d_feat, d_ids, d_motion, n_bodies,
+                                                d_out0, d_out1, hip_stream, d_mult);
+}
+
+// rt_temporal_probe: the step's checks and set-up, one kernel, no state touched
+extern "C" int rt_temporal_probe(const rt_temporal* t, const rt_temporal_opts* o, const rt_camera* cam,
+                                 const float* d_feat, const int32_t* d_ids, const float* d_motion, int n_bodies,
+                                 float* d_len, void* hip_stream) {
+  clear_error();
+  const std::string me("rt_temporal_probe");
+  if (!t || !cam || !d_feat || !d_len) return set_error(RT_E_ARG, me + ": NULL argument");
+  if (d_ids) {
+    if (const char* why = tp_motion_error(d_ids, d_motion, n_bodies)) return set_error(RT_E_ARG, me + ": " + why);
+    if (reinterpret_cast<uintptr_t>(d_motion) % 16 != 0) return set_error(RT_E_ARG, me + ": d_motion is not 16-byte aligned");
+  }
+  const rt_temporal_opts opt = o ? *o : tp_default_opts();
+  if (const char* why = tp_opts_error(opt)) return set_error(RT_E_ARG, me + ": " + why);
+  const size_t lb = t->n_px * sizeof(float), fb = t->n_px * RT_FEAT_CHANNELS * sizeof(float);
+  const size_t ib = d_ids ? t->n_px * sizeof(int32_t) : 0, mb = d_ids ? static_cast<size_t>(n_bodies) * 4 * sizeof(float) : 0;
+  if (tp_overlap(d_len, lb, d_feat, fb) || tp_overlap(d_len, lb, d_ids, ib) || tp_overlap(d_len, lb, d_motion, mb))
+    return set_error(RT_E_ARG, me + ": the output overlaps an input");
+  std::lock_guard<std::mutex> lk(t->mu);
+  TpFrame f = tp_frame(opt, *cam, t->width, t->rows, t->row0);
+  if (t->have_prev) {
+    if (!tp_setup(*cam, t->prev, f.R, f.dc))
+      return set_error(RT_E_ARG, me + ": the previous camera is degenerate (det is 0 or not finite)");
+    f.have_prev = 1;
+  }
+  HIP_TRY(hipSetDevice(t->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (const int rc = tp_stream_check(me, t, stream)) return rc;
+  const dim3 grid(static_cast<unsigned>((t->width + kDnBx - 1) / kDnBx),
+                  static_cast<unsigned>((t->rows + kDnBy - 1) / kDnBy)),
+      block(kDnBx, kDnBy);
+  const TpWord* a0 = t->a0[t->cur].p;
+  const DnGuide* g = t->guide[t->cur].p;
+  if (d_ids)
+    HIP_TRY(enqueue(temporal_probe_kernel<true>, grid, block, 0, stream, f, d_feat, d_ids, d_motion, n_bodies, a0, g,
+                    d_len));
+  else
+    HIP_TRY(enqueue(temporal_probe_kernel<false>, grid, block, 0, stream, f, d_feat, static_cast<const int32_t*>(nullptr),
+                    static_cast<const float*>(nullptr), 0, a0, g, d_len));
+  return RT_OK;
+}
+
+// The budgeted frame: h[0], h[1] the sums of the even and the odd sample
+// blocks in the accumulator's layout; mult and counts per 8 x 8 tile of the
+// output rows; list: every tile, by descending mult; state: the plan kernels'
+// scratch; back: what the list kernel leaves for the host (n_j, px_j), copied
+// to `pinned` behind it -- rt_budget_trace waits for `ev` and takes the grids
+// of its launches from there.
+struct rt_budget : FrameBuf {
+  rt_budget_opts opts{};
+  int rows = 0, gx = 0, gy = 0, n_tiles = 0;
+  size_t n = 0;   // sums per half: rows x width x 3
+  DevBuf<unsigned long long> h[2];
+  DevBuf<uint32_t> mult, counts;
+  DevBuf<int> list;
+  DevBuf<unsigned> state, back;   // device u32[kBdState], u32[kBdBack]
+  unsigned* pinned = nullptr;     // host u32[kBdBack]
+  hipEvent_t ev = nullptr;
+  bool pending = false;   // a plan's read-back is in flight
+  bool planned = false;   // a plan no trace has used yet
+  bool have = false;      // nj, px hold a plan's numbers
+  unsigned nj[kBdMaxMult] = {}, px[kBdMaxMult] = {};
+  ~rt_budget() {
+    if (pinned) (void)hipHostFree(pinned);
+    if (ev) (void)hipEventDestroy(ev);
+  }
+};
+
+extern "C" int rt_budget_create(const rt_dscene* ds, const rt_params* shape, const rt_budget_opts* opts,
+                                rt_budget** out) {
+  clear_error();
+  if (out) *out = nullptr;
+  if (!ds || !shape || !opts || !out) return set_error(RT_E_ARG, "rt_budget_create: NULL argument");
+  if (const char* why = bd_opts_error(*opts)) return set_error(RT_E_ARG, std::string("rt_budget_create: ") + why);
+  if (shape->tile_step != 0) return set_error(RT_E_ARG, "rt_budget_create: tile_step must be 0 (a contiguous band)");
+  int rows = 0;
+  if (const int rc = frame_rows("rt_budget_create", *shape, &rows)) return rc;
+  const int64_t tiles = static_cast<int64_t>((shape->width + kTile - 1) / kTile) * ((rows + kTile - 1) / kTile);
+  // (the resolve's grid has a block row per frame row; the pixel counts are u32)
+  if (rows > 65535 || tiles > INT_MAX / policy::kSplitMax || static_cast<int64_t>(rows) * shape->width > 0xffffffffll)
+    return set_error(RT_E_ARG, "rt_budget_create: frame too large (more than 65535 rows)");
+  rt_budget* bd = nullptr;
+  if (const int rc = frame_new(*ds, *shape, &bd)) return rc;
+  bd->opts = *opts;
+  bd->rows = rows;
+  bd->gx = (shape->width + kTile - 1) / kTile;
+  bd->gy = (rows + kTile - 1) / kTile;
+  bd->n_tiles = static_cast<int>(tiles);
+  bd->n = static_cast<size_t>(rows) * shape->width * 3;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+    e = bd->h[k].alloc(bd->n);
+    if (e == hipSuccess) e = fill_zero(bd->h[k], bd->n, nullptr);
+  }
+  if (e == hipSuccess) e = bd->mult.alloc(bd->n_tiles);
+  if (e == hipSuccess) e = bd->counts.alloc(bd->n_tiles);
+  if (e == hipSuccess) e = bd->list.alloc(bd->n_tiles);
+  if (e == hipSuccess) e = bd->state.alloc(kBdState);
+  if (e == hipSuccess) e = bd->back.alloc(kBdBack);
+  if (e == hipSuccess) e = fill_zero(bd->mult, bd->n_tiles, nullptr);
+  if (e == hipSuccess) e = fill_zero(bd->counts, bd->n_tiles, nullptr);
+  if (e == hipSuccess) e = fill_zero(bd->list, bd->n_tiles, nullptr);   // (every entry a tile of the frame, always)
+  if (e == hipSuccess) e = hipHostMalloc(&bd->pinned, kBdBack * sizeof(unsigned));
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&bd->ev, hipEventDisableTiming);
+  return frame_created("rt_budget_create", bd, e, out);
+}
+
+extern "C" int rt_budget_free(rt_budget* bd) {
+  if (bd && bd->pending) (void)hipEventSynchronize(bd->ev);   // (the copy into `pinned`)
+  return frame_free(bd);
+}
+
+// the read-back in flight, if any: wait for it and take its numbers (the caller holds bd->mu)
+static int budget_settle(rt_budget* bd) {
+  if (!bd->pending) return RT_OK;
+  HIP_TRY(hipEventSynchronize(bd->ev));
+  bd->pending = false;
+  for (int j = 0; j < kBdMaxMult; ++j) {
+    bd->nj[j] = bd->pinned[j];
+    bd->px[j] = bd->pinned[kBdMaxMult + j];
+  }
+  bd->have = true;
+  return RT_OK;
+}
+
+// rt_budget_plan (d_len) and rt_budget_plan_mult (d_mult): the zeroing, the
+// plan or the clamp kernel, the list kernel, the read-back
+static int budget_plan(const char* who, rt_budget* bd, const float* d_len, const uint32_t* d_mult, void* hip_stream) {
+  clear_error();
+  if (!bd || (!d_len && !d_mult)) return set_error(RT_E_ARG, std::string(who) + ": NULL argument");
+  std::lock_guard<std::mutex> lk(bd->mu);
+  HIP_TRY(hipSetDevice(bd->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (const int rc = stream_on_device(who, stream, bd->device)) return rc;
+  if (bd->pending) HIP_TRY(hipEventSynchronize(bd->ev));   // (`pinned` is about to be written again)
+  bd->pending = bd->planned = bd->have = false;
+  for (int k = 0; k < 2; ++k) HIP_TRY(fill_zero(bd->h[k], bd->n, stream));
+  HIP_TRY(fill_zero(bd->state, kBdState, stream));
+  const rt_budget_opts& o = bd->opts;
+  const int width = bd->shape.width, nt = bd->n_tiles;
+  if (d_len)
+    HIP_TRY(enqueue(budget_plan_kernel, dim3(static_cast<unsigned>((nt + kBdPlanWaves - 1) / kBdPlanWaves)),
+                    dim3(64 * kBdPlanWaves), 0, stream, d_len, width, bd->rows, bd->gx, nt, o.target, o.max_mult,
+                    o.quantile_64, bd->mult.p, bd->state.p));
+  else
+    HIP_TRY(enqueue(budget_clamp_kernel, dim3(static_cast<unsigned>((nt + 255) / 256)), dim3(256), 0, stream, d_mult,
+                    width, bd->rows, bd->gx, nt, o.max_mult, bd->mult.p, bd->state.p));
+  HIP_TRY(enqueue(budget_list_kernel, dim3(static_cast<unsigned>((nt + 255) / 256)), dim3(256), 0, stream,
+                  static_cast<const uint32_t*>(bd->mult.p), nt, o.half_spp, bd->state.p, bd->list.p, bd->counts.p,
+                  bd->back.p));
+  HIP_TRY(hipMemcpyAsync(bd->pinned, bd->back.p, kBdBack * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipEventRecord(bd->ev, stream));
+  bd->pending = bd->planned = true;
+  return RT_OK;
+}
+
+extern "C" int rt_budget_plan(rt_budget* bd, const float* d_len, void* hip_stream) {
+  if (!d_len) {
+    clear_error();
+    return set_error(RT_E_ARG, "rt_budget_plan: NULL argument");
+  }
+  return budget_plan("rt_budget_plan", bd, d_len, nullptr, hip_stream);
+}
+
+extern "C" int rt_budget_plan_mult(rt_budget* bd, const uint32_t* d_mult, void* hip_stream) {
+  return budget_plan("rt_budget_plan_mult", bd, nullptr, d_mult, hip_stream);
+}
+
+extern "C" int rt_budget_trace(const rt_dscene* ds, const rt_camera* c, const rt_params* p, rt_budget* bd,
+                               uint64_t* d_counters, void* hip_stream) {
+  clear_error();
+  if (!ds || !c || !p || !bd) return set_error(RT_E_ARG, "rt_budget_trace: NULL argument");
+  if (const int rc = check_match("rt_budget_trace", "the budgeted frame", *bd, *ds, *p)) return rc;
+  std::lock_guard<std::mutex> lk(bd->mu);
+  if (!bd->planned) return set_error(RT_E_ARG, "rt_budget_trace: no fresh plan (rt_budget_plan comes first)");
+  const rt_budget_opts& o = bd->opts;
+  if (p->sample_begin < 0 || static_cast<int64_t>(p->sample_begin) + 2ll * o.max_mult * o.half_spp > INT_MAX)
+    return set_error(RT_E_ARG, "rt_budget_trace: sample_begin + 2 * max_mult * half_spp passes 2^31 - 1");
+  HIP_TRY(hipSetDevice(bd->device));
+  if (const int rc = budget_settle(bd)) return rc;
+  int launches = 0;
+  for (int j = 0; j < o.max_mult; ++j) {
+    const int n_j = static_cast<int>(std::min<unsigned>(bd->nj[j], static_cast<unsigned>(bd->n_tiles)));
+    if (n_j <= 0) break;   // (the n_j do not grow)
+    for (int h = 0; h < 2; ++h) {
+      rt_params q = *p;
+      q.spp = o.half_spp;
+      q.sample_begin = p->sample_begin + (2 * j + h) * o.half_spp;
+      // (a refusal comes from the first launch, before anything is enqueued: the variant's tiles)
+      if (const int rc = launch_impl(ds, c, &q, nullptr, d_counters, hip_stream, bd->h[h].p, "rt_budget_trace",
+                                     bd->list.p, n_j))
+        return rc;
+      ++launches;
+    }
+  }
+  bd->planned = false;
+  return launches;
+}
+
+extern "C" int rt_budget_resolve(const rt_budget* bd, int flags, float* d_out, void* hip_stream) {
+  clear_error();
+  if (!bd || !d_out) return set_error(RT_E_ARG, "rt_budget_resolve: NULL argument");
+  if (const int rc = check_resolve_flags("rt_budget_resolve", flags)) return rc;
+  HIP_TRY(hipSetDevice(bd->device));
+  const int width = bd->shape.width;
+  const unsigned bx = static_cast<unsigned>(std::max(1, std::min((width * 3 / 2 + 255) / 256, 64)));
+  // (the rows are the grid's y: rt_budget_create admits at most 65535)
+  HIP_TRY(enqueue(adapt_resolve_kernel, dim3(bx, static_cast<unsigned>(bd->rows)), dim3(256), 0,
+                  static_cast<hipStream_t>(hip_stream), bd->h[0].p, bd->h[1].p, bd->counts.p, width, bd->gx,
+                  (flags & RT_FLAG_REALM) ? 1 : 0, d_out, static_cast<uint8_t*>(nullptr), quantize_table()));
+  return RT_OK;
+}
+
+extern "C" int rt_budget_resolve_half(const rt_budget* bd, int half, int flags, float* d_out, void* hip_stream) {
+  clear_error();
+  if (!bd || !d_out) return set_error(RT_E_ARG, "rt_budget_resolve_half: NULL argument");
+  if (half != 0 && half != 1) return set_error(RT_E_ARG, "rt_budget_resolve_half: half is neither 0 nor 1");
+  if (const int rc = check_resolve_flags("rt_budget_resolve_half", flags)) return rc;
+  HIP_TRY(hipSetDevice(bd->device));
+  const size_t blocks = std::max<size_t>(1, std::min<size_t>((bd->n + 255) / 256, 4096));
+  HIP_TRY(enqueue(adapt_half_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
+                  static_cast<hipStream_t>(hip_stream), bd->h[half].p, bd->counts.p, bd->shape.width, bd->gx, bd->n,
+                  (flags & RT_FLAG_REALM) ? 1 : 0, d_out));
+  return RT_OK;
+}
+
+extern "C" int rt_budget_read(const rt_budget* bd, uint64_t* host_sums0, uint64_t* host_sums1, void* hip_stream) {
+  clear_error();
+  if (!bd || !host_sums0 || !host_sums1) return set_error(RT_E_ARG, "rt_budget_read: NULL argument");
+  HIP_TRY(hipSetDevice(bd->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  HIP_TRY(hipMemcpyAsync(host_sums0, bd->h[0].p, bd->n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(host_sums1, bd->h[1].p, bd->n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return RT_OK;
+}
+
+extern "C" int rt_budget_mult_read(const rt_budget* bd, uint32_t* host_mult, void* hip_stream) {
+  clear_error();
+  if (!bd || !host_mult) return set_error(RT_E_ARG, "rt_budget_mult_read: NULL argument");
+  HIP_TRY(hipSetDevice(bd->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  HIP_TRY(hipMemcpyAsync(host_mult, bd->mult.p, bd->n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return RT_OK;
+}
+
+extern "C" int rt_budget_device_mult(const rt_budget* bd, const uint32_t** d_mult) {
+  clear_error();
+  if (!bd || !d_mult) return set_error(RT_E_ARG, "rt_budget_device_mult: NULL argument");
+  *d_mult = bd->mult.p;
+  return RT_OK;
+}
+
+extern "C" int64_t rt_budget_samples(rt_budget* bd) {
+  if (!bd) return 0;
+  std::lock_guard<std::mutex> lk(bd->mu);
+  (void)hipSetDevice(bd->device);
+  if (budget_settle(bd) != RT_OK || !bd->have) return 0;
+  int64_t px = 0;   // sum over j of the pixels of the tiles with mult > j = sum over tiles of npx * mult
+  for (int j = 0; j < bd->opts.max_mult; ++j) px += bd->px[j];
+  return px * 2 * bd->opts.half_spp;
 }
 
 // A device's start-up ahead of the first render (rt.h): the context, the

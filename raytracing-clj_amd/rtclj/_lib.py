@@ -90,6 +90,10 @@ class rt_temporal_clamp_opts(C.Structure):
     _fields_ = [("radius", C.c_int), ("gamma", C.c_float)]
 
 
+class rt_budget_opts(C.Structure):
+    _fields_ = [("half_spp", C.c_int), ("target", C.c_int), ("max_mult", C.c_int), ("quantile_64", C.c_int)]
+
+
 class rt_tree_info(C.Structure):
     _fields_ = [("n_nodes", C.c_int), ("off_pairs", C.c_int), ("off_pidx", C.c_int), ("blob_bytes", C.c_int),
                 ("big_pair0", C.c_int), ("n_big_leaves", C.c_int), ("depth", C.c_int), ("leaf_size", C.c_int),
@@ -112,6 +116,8 @@ class rt_schedule_info(C.Structure):
 TEMPORAL_DEFAULTS = dict(max_history=32, sigma_z=0.1, normal_min=0.9)
 # rt_temporal_step_clamp's defaults (include/rt.h)
 TEMPORAL_CLAMP_DEFAULTS = dict(radius=2, gamma=1.0)
+# rt_budget_opts' defaults (include/rt.h); half_spp has none
+BUDGET_DEFAULTS = dict(target=8, max_mult=8, quantile_64=16)
 
 
 # symbol -> (restype, argtypes); every function include/rt.h declares
@@ -213,6 +219,33 @@ SIGNATURES = {
                                          C.POINTER(rt_camera), C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int] +
                                [C.POINTER(C.c_float)] * 7 + [C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int] +
                                [C.POINTER(C.c_float)] * 3),
+    "rt_temporal_probe": (C.c_int, [C.c_void_p, C.POINTER(rt_temporal_opts), C.POINTER(rt_camera), C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_temporal_host_probe": (C.c_int, [C.POINTER(rt_temporal_opts), C.POINTER(rt_camera), C.POINTER(rt_camera),
+                                         C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 3 +
+                               [C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float)]),
+    "rt_budget_plan_host": (C.c_int, [C.POINTER(rt_budget_opts), C.POINTER(C.c_float), C.c_int, C.c_int,
+                                      C.POINTER(C.c_uint32)]),
+    "rt_budget_create": (C.c_int, [C.c_void_p, C.POINTER(rt_params), C.POINTER(rt_budget_opts),
+                                   C.POINTER(C.c_void_p)]),
+    "rt_budget_free": (C.c_int, [C.c_void_p]),
+    "rt_budget_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_budget_plan_mult": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_budget_trace": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+    "rt_budget_resolve": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_budget_resolve_half": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rt_budget_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
+    "rt_budget_mult_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),
+    "rt_budget_device_mult": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "rt_budget_samples": (C.c_int64, [C.c_void_p]),
+    "rt_temporal_step_budget": (C.c_int, [C.c_void_p, C.POINTER(rt_temporal_opts), C.POINTER(rt_temporal_clamp_opts),
+                                          C.POINTER(rt_camera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_temporal_host_budget": (C.c_int, [C.POINTER(rt_temporal_opts), C.POINTER(rt_temporal_clamp_opts),
+                                          C.POINTER(rt_camera), C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int] +
+                                [C.POINTER(C.c_float)] * 7 + [C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int,
+                                                              C.POINTER(C.c_uint32)] + [C.POINTER(C.c_float)] * 3),
     "rt_launch_ids": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rt_ids_host": (C.c_int, [C.POINTER(rt_scene), C.POINTER(rt_camera), C.c_int, C.c_int, C.c_int,
                               C.POINTER(C.c_int32)]),
@@ -258,7 +291,11 @@ ADDITIVE = {"rt_prepare", "rt_render_u8", "rt_quantize_device", "rt_render_submi
             "rt_denoiser_create", "rt_denoiser_free", "rt_denoise", "rt_denoise_profile",
             "rt_denoise_host", "rt_temporal_create", "rt_temporal_free", "rt_temporal_reset", "rt_temporal_frames",
             "rt_temporal_step", "rt_temporal_read", "rt_temporal_host", "rt_temporal_step_motion",
-            "rt_temporal_host_motion", "rt_temporal_step_clamp", "rt_temporal_host_clamp", "rt_launch_ids", "rt_ids_host", "rt_ids_occupancy", "rt_body_motion",
+            "rt_temporal_host_motion", "rt_temporal_step_clamp", "rt_temporal_host_clamp", "rt_temporal_probe",
+            "rt_temporal_host_probe", "rt_budget_plan_host", "rt_budget_create", "rt_budget_free", "rt_budget_plan",
+            "rt_budget_plan_mult", "rt_budget_trace", "rt_budget_resolve", "rt_budget_resolve_half", "rt_budget_read",
+            "rt_budget_mult_read", "rt_budget_device_mult", "rt_budget_samples", "rt_temporal_step_budget",
+            "rt_temporal_host_budget", "rt_launch_ids", "rt_ids_host", "rt_ids_occupancy", "rt_body_motion",
             "rt_scene_update", "rt_tree_build_host", "rt_tree_refit_host", "rt_tree_cost_host", "rt_scene_tree_info",
             "rt_scene_tree_read", "rt_schedule_read", "rt_schedule_sort"}
 

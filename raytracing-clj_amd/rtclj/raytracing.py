@@ -24,9 +24,9 @@ from fractions import Fraction
 import numpy as np
 
 from . import hittable, material
-from ._lib import (DENOISE_DEFAULTS, RT_DIELECTRIC, RT_FEAT_CHANNELS, RT_LAMBERTIAN, RT_METAL, RT_NONE,
+from ._lib import (BUDGET_DEFAULTS, DENOISE_DEFAULTS, RT_DIELECTRIC, RT_FEAT_CHANNELS, RT_LAMBERTIAN, RT_METAL, RT_NONE,
                    TEMPORAL_CLAMP_DEFAULTS, TEMPORAL_DEFAULTS, RTError, check, dptr, fptr, i64ptr, iptr, lib,
-                   rt_adapt_opts, rt_camera, i32ptr, rt_denoise_opts, rt_params, rt_scene, rt_schedule_info, rt_stats,
+                   rt_adapt_opts, rt_budget_opts, rt_camera, i32ptr, rt_denoise_opts, rt_params, rt_scene, rt_schedule_info, rt_stats,
                    rt_temporal_clamp_opts, rt_temporal_opts, rt_tree_info, u8ptr, u32ptr, u64ptr)
 
 # ---- scene (raytracing.clj:63-78) --------------------------------------------
@@ -650,7 +650,7 @@ def _temporal_clamp_opts(clamp: dict) -> rt_temporal_clamp_opts:
 
 
 def temporal_host(cam: rt_camera, prev_cam, half0, half1, feat, prev=None, row0: int = 0, library=None, ids=None,
-                  motion=None, clamp=None, **opts):
+                  motion=None, clamp=None, mult=None, **opts):
     """rt_temporal_host (include/rt.h): one step of temporal accumulation on the
     host, in plain C++ -- the bits Temporal.step gives on the device.  half0,
     half1: float32 (rows, width, 3); feat: float32 (rows, width, 8); cam: the
@@ -663,6 +663,10 @@ def temporal_host(cam: rt_camera, prev_cam, half0, half1, feat, prev=None, row0:
     moved) is subtracted for the pixel's body.  With `clamp` (a dict of radius
     and gamma; {}: the defaults) it is rt_temporal_host_clamp: the fetched
     history is held to the current frame's colour box, with or without ids.
+    With `mult` (uint32 (ceil(rows / 8), ceil(width / 8)): the sample multiplier
+    of every 8 x 8 tile, as budget_plan_host gives them) it is
+    rt_temporal_host_budget: the clamped step (clamp None: the defaults) whose
+    blend weights the halves as `mult` frames' worth of samples.
     Returns (out0, out1, length):
     the new history's halves and its length; its guides are feat[..., 3:7]."""
     dll = library if library is not None else lib
@@ -687,7 +691,24 @@ def temporal_host(cam: rt_camera, prev_cam, half0, half1, feat, prev=None, row0:
             fptr(half0), fptr(half1), fptr(feat), *(fptr(a) if a is not None else None for a in hist))
     k = None if clamp is None else _temporal_clamp_opts(clamp)
     outs = (fptr(out0), fptr(out1), fptr(length))
-    if ids is None:
+    if mult is not None:
+        mult = np.ascontiguousarray(mult, np.uint32)
+        if mult.shape != ((rows + 7) // 8, (width + 7) // 8):
+            raise ValueError("temporal_host: mult must be uint32 (ceil(rows / 8), ceil(width / 8))")
+        if ids is None and motion is not None:
+            raise ValueError("temporal_host: motion comes with ids")
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, np.int32)
+            if ids.shape != (rows, width):
+                raise ValueError("temporal_host: ids must be int32 (rows, width)")
+            motion = np.zeros((0, 4), np.float32) if motion is None else np.ascontiguousarray(motion, np.float32)
+            if motion.ndim != 2 or motion.shape[1] != 4:
+                raise ValueError("temporal_host: motion must be float32 (n_bodies, 4)")
+        nb = 0 if ids is None else len(motion)
+        code = dll.rt_temporal_host_budget(head[0], C.byref(k) if k is not None else None, *head[1:],
+                                           i32ptr(ids) if ids is not None else None, fptr(motion) if nb else None, nb,
+                                           u32ptr(mult), *outs)
+    elif ids is None:
         if motion is not None:
             raise ValueError("temporal_host: motion comes with ids")
         if k is None:
@@ -709,6 +730,177 @@ def temporal_host(cam: rt_camera, prev_cam, half0, half1, feat, prev=None, row0:
     if code < 0:
         raise RTError(code, dll.rt_last_error().decode(errors="replace"))
     return out0, out1, length
+
+
+def temporal_probe_host(cam: rt_camera, prev_cam, feat, prev=None, row0: int = 0, library=None, ids=None, motion=None,
+                        **opts) -> np.ndarray:
+    """rt_temporal_host_probe (include/rt.h): per pixel, the history length the
+    next step on these inputs would accept -- steps 1-5 of temporal_host, no
+    colour involved -- as float32 (rows, width); 0 where it would find none,
+    and everywhere without a previous camera.  feat, prev_cam, prev = (a0, a1,
+    guide, length) (a0 and a1 are not read and may be None), ids, motion and
+    the options as temporal_host."""
+    dll = library if library is not None else lib
+    feat = np.ascontiguousarray(feat, np.float32)
+    if feat.ndim != 3 or feat.shape[2] != RT_FEAT_CHANNELS:
+        raise ValueError("temporal_probe_host: feat must be (rows, width, 8)")
+    rows, width = feat.shape[:2]
+    if (prev_cam is None) != (prev is None):
+        raise ValueError("temporal_probe_host: prev_cam and prev come together")
+    guide = length = None
+    if prev is not None:
+        guide, length = np.ascontiguousarray(prev[2], np.float32), np.ascontiguousarray(prev[3], np.float32)
+        if guide.shape != (rows, width, 4) or length.shape != (rows, width):
+            raise ValueError("temporal_probe_host: prev must be (a0, a1, guide, length) of the frame's size")
+    if ids is None and motion is not None:
+        raise ValueError("temporal_probe_host: motion comes with ids")
+    nb = 0
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, np.int32)
+        if ids.shape != (rows, width):
+            raise ValueError("temporal_probe_host: ids must be int32 (rows, width)")
+        motion = np.zeros((0, 4), np.float32) if motion is None else np.ascontiguousarray(motion, np.float32)
+        if motion.ndim != 2 or motion.shape[1] != 4:
+            raise ValueError("temporal_probe_host: motion must be float32 (n_bodies, 4)")
+        nb = len(motion)
+    out = np.empty((rows, width), np.float32)
+    o = _temporal_opts(opts)
+    code = dll.rt_temporal_host_probe(C.byref(o), C.byref(cam), C.byref(prev_cam) if prev_cam is not None else None,
+                                      width, rows, int(row0), fptr(feat), fptr(guide) if guide is not None else None,
+                                      fptr(length) if length is not None else None,
+                                      i32ptr(ids) if ids is not None else None, fptr(motion) if nb else None, nb,
+                                      fptr(out))
+    if code < 0:
+        raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+    return out
+
+
+def _budget_opts(opts: dict) -> rt_budget_opts:
+    unknown = set(opts) - set(BUDGET_DEFAULTS) - {"half_spp"}
+    if unknown:
+        raise TypeError(f"budget: unknown option(s) {sorted(unknown)}")
+    if "half_spp" not in opts:
+        raise TypeError("budget: half_spp is required")
+    b = {**BUDGET_DEFAULTS, **opts}
+    return rt_budget_opts(half_spp=int(b["half_spp"]), target=int(b["target"]), max_mult=int(b["max_mult"]),
+                          quantile_64=int(b["quantile_64"]))
+
+
+def budget_plan_host(length, library=None, **opts) -> np.ndarray:
+    """rt_budget_plan_host (include/rt.h): the sample multiplier of every 8 x 8
+    tile, uint32 (ceil(rows / 8), ceil(width / 8)), from a float32 (rows, width)
+    history length image (temporal_probe_host's).  Options: half_spp
+    (required), target, max_mult, quantile_64."""
+    dll = library if library is not None else lib
+    length = np.ascontiguousarray(length, np.float32)
+    if length.ndim != 2:
+        raise ValueError("budget_plan_host: length must be (rows, width)")
+    rows, width = length.shape
+    o = _budget_opts(opts)
+    mult = np.empty(((rows + 7) // 8, (width + 7) // 8), np.uint32)
+    code = dll.rt_budget_plan_host(C.byref(o), fptr(length), width, rows, u32ptr(mult))
+    if code < 0:
+        raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+    return mult
+
+
+class Budget:
+    """A budgeted frame on an uploaded scene's device (rt_budget, include/rt.h):
+    two half accumulators traced at a per-tile multiple of half_spp samples.
+
+        bd = Budget(ds, width, height, half_spp=1, max_depth=50)
+        tp.probe(cam, d_feat, d_len)              # how much history per pixel
+        bd.plan(d_len)                            # -> a multiplier per 8 x 8 tile
+        bd.trace(ds, cam, sample_begin)           # the frame's one host sync
+        bd.resolve_half_into(d_h0, 0); bd.resolve_half_into(d_h1, 1)
+        tp.step(cam, d_h0, d_h1, d_feat, d_o0, d_o1, clamp={}, d_mult=bd.d_mult)
+
+    `ds` is an rt_dscene handle (DeviceScene.handle or rt_scene_upload's);
+    the object holds no reference to it.  Successive frames advance
+    sample_begin by 2 * max_mult * half_spp."""
+
+    def __init__(self, ds, width: int, height: int, max_depth: int = 50, seed: int = 1, flags: int = 0, rows=None,
+                 library=None, **opts):
+        self._dll = library if library is not None else lib
+        self.opts = _budget_opts(opts)
+        self.width, self.height, self.flags = int(width), int(height), int(flags)
+        r0, r1 = rows if rows is not None else (0, height)
+        self.rows = r1 - r0
+        self.tiles = ((self.rows + 7) // 8, (self.width + 7) // 8)
+        self._p = rt_params(width=width, height=height, row_begin=r0, row_end=r1, spp=0, max_depth=max_depth, seed=seed,
+                            flags=flags)
+        self._bd = C.c_void_p()
+        self._check(self._dll.rt_budget_create(ds, C.byref(self._p), C.byref(self.opts), C.byref(self._bd)))
+
+    def _check(self, code):
+        if code < 0:
+            raise RTError(code, self._dll.rt_last_error().decode(errors="replace"))
+        return code
+
+    def plan(self, d_len: int, stream=None) -> None:
+        """Start a frame from a device history-length image (rt_budget_plan)."""
+        self._check(self._dll.rt_budget_plan(self._bd, C.c_void_p(d_len), C.c_void_p(stream) if stream else None))
+
+    def plan_mult(self, d_mult: int, stream=None) -> None:
+        """Start a frame from the caller's uint32 multipliers on the device,
+        one per tile (rt_budget_plan_mult); clamped to 1 .. max_mult."""
+        self._check(self._dll.rt_budget_plan_mult(self._bd, C.c_void_p(d_mult), C.c_void_p(stream) if stream else None))
+
+    def trace(self, ds, cam: rt_camera, sample_begin: int = 0, stream=None, d_counters=None) -> int:
+        """Trace the plan (rt_budget_trace); returns the number of launches."""
+        p = rt_params.from_buffer_copy(self._p)
+        p.spp, p.sample_begin = self.opts.half_spp, int(sample_begin)
+        return self._check(self._dll.rt_budget_trace(ds, C.byref(cam), C.byref(p), self._bd,
+                                                     C.c_void_p(d_counters) if d_counters else None,
+                                                     C.c_void_p(stream) if stream else None))
+
+    @property
+    def samples(self) -> int:
+        """Samples of the current plan over all pixels (rt_budget_samples)."""
+        return int(self._dll.rt_budget_samples(self._bd))
+
+    @property
+    def d_mult(self) -> int:
+        """The device address of the plan's multipliers (rt_budget_device_mult)."""
+        out = C.c_void_p()
+        self._check(self._dll.rt_budget_device_mult(self._bd, C.byref(out)))
+        return int(out.value)
+
+    def mult(self, stream=None) -> np.ndarray:
+        """The plan's multipliers, uint32 (gy, gx) (rt_budget_mult_read)."""
+        m = np.empty(self.tiles, np.uint32)
+        self._check(self._dll.rt_budget_mult_read(self._bd, u32ptr(m), C.c_void_p(stream) if stream else None))
+        return m
+
+    def halves(self, stream=None):
+        """(sums0, sums1): both halves' integer sums, uint64 (rows, width, 3) each (rt_budget_read)."""
+        s0, s1 = (np.empty((self.rows, self.width, 3), np.uint64) for _ in range(2))
+        self._check(self._dll.rt_budget_read(self._bd, u64ptr(s0), u64ptr(s1), C.c_void_p(stream) if stream else None))
+        return s0, s1
+
+    def resolve_into(self, d_out: int, stream=None) -> None:
+        """Enqueue the whole frame's resolve into device floats (rt_budget_resolve)."""
+        self._check(self._dll.rt_budget_resolve(self._bd, self.flags, C.c_void_p(d_out),
+                                                C.c_void_p(stream) if stream else None))
+
+    def resolve_half_into(self, d_out: int, half: int, stream=None) -> None:
+        """Enqueue one half's resolve into device floats (rt_budget_resolve_half)."""
+        self._check(self._dll.rt_budget_resolve_half(self._bd, int(half), self.flags, C.c_void_p(d_out),
+                                                     C.c_void_p(stream) if stream else None))
+
+    def close(self) -> None:
+        if getattr(self, "_bd", None):
+            self._dll.rt_budget_free(self._bd)
+            self._bd = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
 
 
 class Temporal:
@@ -745,19 +937,29 @@ class Temporal:
         return int(self._dll.rt_temporal_frames(self._tp))
 
     def step(self, cam: rt_camera, d_half0: int, d_half1: int, d_feat: int, d_out0: int, d_out1: int, stream=None,
-             d_ids=None, d_motion=None, n_bodies: int = 0, clamp=None, **opts) -> None:
+             d_ids=None, d_motion=None, n_bodies: int = 0, clamp=None, d_mult=None, **opts) -> None:
         """Enqueue one step (rt_temporal_step) on device addresses; options as
         temporal_host.  With `d_ids` (int32 (rows, width) on the device, as
         body_ids_into writes them) it is rt_temporal_step_motion: `d_motion`
         is body_motion's table on the device (n_bodies x 4 float32, 16-byte
         aligned).  With `clamp` (a dict of radius and gamma; {}: the defaults)
-        it is rt_temporal_step_clamp, with or without d_ids.  All kinds of step
-        may alternate on one object."""
+        it is rt_temporal_step_clamp, with or without d_ids.  With `d_mult`
+        (uint32, one per 8 x 8 tile, on the device: Budget.d_mult) it is
+        rt_temporal_step_budget: the clamped step (clamp None: the defaults)
+        weighted by the tiles' sample multipliers.  All kinds of step may
+        alternate on one object."""
         o = _temporal_opts(opts)
         st = C.c_void_p(stream) if stream else None
         if d_ids is None and (d_motion is not None or n_bodies):
             raise ValueError("Temporal.step: d_motion and n_bodies come with d_ids")
-        if clamp is not None:
+        if d_mult is not None:
+            k = _temporal_clamp_opts(clamp) if clamp is not None else None
+            self._check(self._dll.rt_temporal_step_budget(
+                self._tp, C.byref(o), C.byref(k) if k is not None else None, C.byref(cam), C.c_void_p(d_half0),
+                C.c_void_p(d_half1), C.c_void_p(d_feat), C.c_void_p(d_ids) if d_ids is not None else None,
+                C.c_void_p(d_motion) if d_motion else None, int(n_bodies), C.c_void_p(d_mult), C.c_void_p(d_out0),
+                C.c_void_p(d_out1), st))
+        elif clamp is not None:
             k = _temporal_clamp_opts(clamp)
             self._check(self._dll.rt_temporal_step_clamp(
                 self._tp, C.byref(o), C.byref(k), C.byref(cam), C.c_void_p(d_half0), C.c_void_p(d_half1),
@@ -772,6 +974,19 @@ class Temporal:
                 self._tp, C.byref(o), C.byref(cam), C.c_void_p(d_half0), C.c_void_p(d_half1), C.c_void_p(d_feat),
                 C.c_void_p(d_ids), C.c_void_p(d_motion) if d_motion else None, int(n_bodies), C.c_void_p(d_out0),
                 C.c_void_p(d_out1), st))
+
+    def probe(self, cam: rt_camera, d_feat: int, d_len: int, stream=None, d_ids=None, d_motion=None, n_bodies: int = 0,
+              **opts) -> None:
+        """Enqueue rt_temporal_probe: d_len (float32 (rows, width) on the device)
+        = the history length the next step on these inputs would accept.
+        Arguments as step's; nothing of the object changes."""
+        o = _temporal_opts(opts)
+        if d_ids is None and (d_motion is not None or n_bodies):
+            raise ValueError("Temporal.probe: d_motion and n_bodies come with d_ids")
+        self._check(self._dll.rt_temporal_probe(
+            self._tp, C.byref(o), C.byref(cam), C.c_void_p(d_feat), C.c_void_p(d_ids) if d_ids is not None else None,
+            C.c_void_p(d_motion) if d_motion else None, int(n_bodies), C.c_void_p(d_len),
+            C.c_void_p(stream) if stream else None))
 
     def read(self, stream=None):
         """(a0, a1, guide, length): the current history copied out behind the
@@ -1119,7 +1334,7 @@ def _same_but_centres(a: Scene, b: Scene) -> bool:
 
 def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max_depth: int = 50, seed: int = 1,
                      flags: int = 0, library=None, temporal=None, stages: bool = False, refit: bool = False, clamp=None,
-                     **opts):
+                     budget=None, **opts):
     """render_sequence for bodies that move: one Scene per frame (all with the
     same body count), zipped with `cameras`; a generator that yields float32
     (height, width, 3) per frame, on device 0.  Per frame f: the scene's upload
@@ -1135,7 +1350,20 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
     even; `temporal`, `clamp` (with it the step is rt_temporal_step_clamp with
     the ids) and further keywords as render_sequence.  With `stages` it
     yields (denoised, half0, half1, feat, acc0, acc1, ids).  With identical
-    scenes it gives render_sequence's bits."""
+    scenes it gives render_sequence's bits.
+    With `budget` (a dict of half_spp, target, max_mult, quantile_64: rt_budget_opts)
+    the samples go where the history is short, and `spp` is not read: per frame
+    the features (a uniform 2 * half_spp, from sample index f * 2 * max_mult *
+    half_spp) and the ids come first, then Temporal.probe, Budget.plan,
+    Budget.trace from the same index, the two halves' resolves, the weighted
+    step (rt_temporal_step_budget with the ids; without `clamp` with gamma =
+    +inf, which clamps nothing) and Denoiser.run.  Frame 0 has no history and is
+    traced at min(target, max_mult) everywhere.  `stages` then yields the
+    tiles' multipliers, uint32 (ceil(height / 8), ceil(width / 8)), as an
+    eighth item.  Without `budget` nothing changes."""
+    if budget is not None:
+        bopt = _budget_opts(dict(budget))
+        spp = 2 * bopt.half_spp
     if spp <= 0 or spp % 2:
         raise ValueError("render_animation: spp must be even and positive")
     _denoise_opts(opts)
@@ -1162,6 +1390,11 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
     d_ids = torch.empty(n_px, dtype=torch.int32, device=dev)
     d_out = torch.empty(n_px * 3, dtype=torch.float32, device=dev)
     d_motion = None
+    d_len = torch.empty(n_px, dtype=torch.float32, device=dev) if budget is not None else None
+    stride = spp if budget is None else 2 * bopt.max_mult * bopt.half_spp   # sample indices per frame
+    bd = None
+    if budget is not None and clamp is None:
+        topts["clamp"] = dict(gamma=float("inf"))
     torch.cuda.synchronize(dev)   # (the passes below run on the NULL stream)
     shape = rt_params(width=width, height=height, row_begin=0, row_end=height, spp=0, max_depth=max_depth, seed=seed,
                       flags=flags)
@@ -1183,30 +1416,45 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
                     ok(dll.rt_scene_upload(0, C.byref(sc.c), C.byref(ds)))
                     first_sc = sc
                 if f == 0:
-                    for a in acc:
-                        ok(dll.rt_accum_create(ds, C.byref(shape), C.byref(a)))
+                    if budget is None:
+                        for a in acc:
+                            ok(dll.rt_accum_create(ds, C.byref(shape), C.byref(a)))
+                    else:
+                        bd = Budget(ds, width, height, max_depth=max_depth, seed=seed, flags=flags, library=library,
+                                    **dict(budget))
                     ok(dll.rt_feat_create(ds, C.byref(shape), C.byref(ft)))
                     motion = np.zeros((len(sc), 4), np.float32)
                 else:
-                    for a in acc:
-                        ok(dll.rt_accum_clear(a, None))
+                    if budget is None:
+                        for a in acc:
+                            ok(dll.rt_accum_clear(a, None))
                     ok(dll.rt_feat_clear(ft, None))
                     motion = body_motion(sc, prev_sc, library=library)
-                for a, begin, n in ((acc[0], f * spp, half), (acc[1], f * spp + half, half)):
-                    p = rt_params.from_buffer_copy(shape)
-                    p.spp, p.sample_begin = n, begin
-                    ok(dll.rt_launch_accum(ds, C.byref(cam), C.byref(p), a, None, None))
+                if budget is None:
+                    for a, begin, n in ((acc[0], f * spp, half), (acc[1], f * spp + half, half)):
+                        p = rt_params.from_buffer_copy(shape)
+                        p.spp, p.sample_begin = n, begin
+                        ok(dll.rt_launch_accum(ds, C.byref(cam), C.byref(p), a, None, None))
                 p = rt_params.from_buffer_copy(shape)
-                p.spp, p.sample_begin, p.max_depth = spp, f * spp, 1
+                p.spp, p.sample_begin, p.max_depth = spp, f * stride, 1
                 ok(dll.rt_launch_feat(ds, C.byref(cam), C.byref(p), ft, None, None))
                 ok(dll.rt_launch_ids(ds, C.byref(cam), width, height, 0, C.c_void_p(d_ids.data_ptr()), None))
-                ok(dll.rt_accum_resolve(acc[0], flags, C.c_void_p(d_h[0].data_ptr()), None))
-                ok(dll.rt_accum_resolve(acc[1], flags, C.c_void_p(d_h[1].data_ptr()), None))
+                if budget is None:
+                    ok(dll.rt_accum_resolve(acc[0], flags, C.c_void_p(d_h[0].data_ptr()), None))
+                    ok(dll.rt_accum_resolve(acc[1], flags, C.c_void_p(d_h[1].data_ptr()), None))
                 ok(dll.rt_feat_resolve(ft, C.c_void_p(d_feat.data_ptr()), None))
                 d_motion = torch.from_numpy(motion.reshape(-1)).to(dev)   # (torch's allocations are 256-byte aligned)
+                moved = dict(d_ids=d_ids.data_ptr(), d_motion=d_motion.data_ptr() if len(sc) else None, n_bodies=len(sc))
+                if budget is not None:
+                    tp.probe(cam, d_feat.data_ptr(), d_len.data_ptr(), **moved,
+                             **{k: v for k, v in topts.items() if k != "clamp"})
+                    bd.plan(d_len.data_ptr())
+                    bd.trace(ds, cam, sample_begin=f * stride)
+                    bd.resolve_half_into(d_h[0].data_ptr(), 0)
+                    bd.resolve_half_into(d_h[1].data_ptr(), 1)
+                    moved["d_mult"] = bd.d_mult
                 tp.step(cam, d_h[0].data_ptr(), d_h[1].data_ptr(), d_feat.data_ptr(), d_acc[0].data_ptr(),
-                        d_acc[1].data_ptr(), d_ids=d_ids.data_ptr(), d_motion=d_motion.data_ptr() if len(sc) else None,
-                        n_bodies=len(sc), **topts)
+                        d_acc[1].data_ptr(), **moved, **topts)
                 dn.run(d_acc[0].data_ptr(), d_acc[1].data_ptr(), d_feat.data_ptr(), d_out.data_ptr(), **opts)
                 torch.cuda.synchronize(dev)
                 if not refit:
@@ -1218,10 +1466,12 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
                     yield (out,) + tuple(d.cpu().numpy().reshape(height, width, 3) for d in d_h) + \
                         (d_feat.cpu().numpy().reshape(height, width, RT_FEAT_CHANNELS),) + \
                         tuple(d.cpu().numpy().reshape(height, width, 3) for d in d_acc) + \
-                        (d_ids.cpu().numpy().reshape(height, width),)
+                        (d_ids.cpu().numpy().reshape(height, width),) + ((bd.mult(),) if bd is not None else ())
                 else:
                     yield out
     finally:
+        if bd is not None:
+            bd.close()
         if ds:
             dll.rt_scene_free(ds)
         for a in acc:
@@ -1406,4 +1656,4 @@ if __name__ == "__main__":  # python -m rtclj.raytracing [spp] [depth]
 
 
 __all__ = ["hittables", "REFERENCE_CAMERA", "image_height", "flatten", "flatten64", "Scene", "camera", "render", "Progressive", "Adaptive", "pass_sizes",
-           "Features", "denoise_host", "Denoiser", "render_denoised", "temporal_host", "Temporal", "render_sequence", "ids_host", "body_ids_into", "body_motion", "tree_build_host", "tree_refit_host", "tree_cost", "DeviceScene", "render_animation", "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]
+           "Features", "denoise_host", "Denoiser", "render_denoised", "temporal_host", "Temporal", "temporal_probe_host", "budget_plan_host", "Budget", "render_sequence", "ids_host", "body_ids_into", "body_motion", "tree_build_host", "tree_refit_host", "tree_cost", "DeviceScene", "render_animation", "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]
