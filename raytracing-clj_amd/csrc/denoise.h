@@ -232,11 +232,13 @@ RT_DN_FN void dn_finish(const DnTexel& t, const float* feat, float* out) {
   out[2] = t.b * dn_albedo(feat[2]);
 }
 
+// A workgroup of the image kernels (here, temporal.h, body_ids.h) is kDnBx x
+// kDnBy pixels, a wave one row of 64: a tap of a wave is 64 consecutive
+// 16-byte words, 1 KiB per load instruction.
+constexpr int kDnBx = 64, kDnBy = 4;
+
 #if defined(__HIPCC__) && defined(RT_DENOISE_KERNEL)
 // ------------------------------------------------------------ the kernels ----
-// A workgroup is kDnBx x kDnBy pixels, a wave one row of 64: a tap of a wave
-// is 64 consecutive 16-byte words, 1 KiB per load instruction.
-constexpr int kDnBx = 64, kDnBy = 4;
 
 // The prep: a thread per pixel, grid-stride.  The caller's arrays are read as
 // single floats (they need no more than a float's alignment), the packed

@@ -1,5 +1,5 @@
 // dev_buf.h — an owning device buffer: a pointer and its capacity, move-only,
-// freed by its destructor.  Included behind the HIP runtime header (trace.hip);
+// freed by its destructor.  Included behind the HIP runtime header (launch.h);
 // the host check of its move logic includes it behind counting stand-ins for
 // hipMalloc / hipFree / hipStreamSynchronize.
 #pragma once

@@ -204,8 +204,8 @@ RT_FH_FN void fh_resolve(const long long* sums, unsigned hits, float depth, floa
 }  // namespace rtclj
 
 // ---------------------------------------------------------- the kernel ----
-// (for the one translation unit that holds the library's code object:
-// trace.hip defines RT_FIRST_HIT_KERNEL before it includes this file)
+// (for the unit that launches it: first_hit.hip defines RT_FIRST_HIT_KERNEL
+// before it includes this file)
 #if defined(__HIPCC__) && defined(RT_FIRST_HIT_KERNEL)
 #include "trace_kernel.h"
 

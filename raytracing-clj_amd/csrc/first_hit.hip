@@ -1,0 +1,244 @@
+// first_hit.hip — the passes that stop at a camera ray's first hit: the feature
+// buffers (rt_feat, rt_launch_feat; first_hit.h's feat_kernel) and the body-id
+// pass (rt_launch_ids; body_ids.h's ids_kernel), with their occupancy entries.
+// Both follow the trace unit's selector (dscene.h).  DESIGN.md §3.7, §3.10.
+#include "trace_kernel.h"
+#define RT_FIRST_HIT_KERNEL
+#include "first_hit.h"
+#define RT_BODY_IDS_KERNEL
+#include "body_ids.h"
+#include "dscene.h"
+
+using namespace rtclj;
+
+// the policy's copies of the feature kernels' shapes
+static_assert(policy::kFeatThreads == kFeatThreads && static_cast<int>(policy::FEAT_LDS) == FEAT_LDS &&
+                  static_cast<int>(policy::FEAT_GLOBAL) == FEAT_GLOBAL && static_cast<int>(policy::FEAT_SCAN) == FEAT_SCAN,
+              "variant_policy.h: the kernels' shapes");
+
+// ---- first-hit features: albedo, normal, depth, coverage (rt.h, first_hit.h) ----
+// Per pixel six 64-bit sums (albedo rgb, normal xyz, 2^-24 units), a u32 hit
+// count and the nearest hit distance as float bits, on the scene's device; the
+// samples per pixel they hold on the host side, as rt_accum keeps them.
+struct rt_feat : FrameBuf {
+  size_t n_px = 0;                   // rows_out x width
+  DevBuf<unsigned long long> sums;   // n_px x 6
+  DevBuf<unsigned> hits;             // n_px
+  DevBuf<unsigned> depth;            // n_px, float bits (+inf: no hit yet)
+};
+
+// the feature kernel for a source of bodies (policy::feat_source)
+static const void* feat_fn(int src) {
+  return src == FEAT_LDS      ? reinterpret_cast<const void*>(&feat_kernel<FEAT_LDS>)
+         : src == FEAT_GLOBAL ? reinterpret_cast<const void*>(&feat_kernel<FEAT_GLOBAL>)
+                              : reinterpret_cast<const void*>(&feat_kernel<FEAT_SCAN>);
+}
+
+static hipError_t feat_reset(rt_feat* f, hipStream_t stream) {
+  hipError_t e = fill_zero(f->sums, f->n_px * 6, stream);
+  if (e == hipSuccess) e = fill_zero(f->hits, f->n_px, stream);
+  if (e == hipSuccess) e = fill_words(f->depth.p, 0x7f800000u, f->n_px, stream);
+  return e;
+}
+
+extern "C" int rt_feat_create(const rt_dscene* ds, const rt_params* shape, rt_feat** out) {
+  clear_error();
+  if (!ds || !shape || !out) return set_error(RT_E_ARG, "rt_feat_create: NULL argument");
+  *out = nullptr;
+  int rows = 0;
+  if (const int rc = frame_rows("rt_feat_create", *shape, &rows)) return rc;
+  rt_feat* f = nullptr;
+  if (const int rc = frame_new(*ds, *shape, &f)) return rc;
+  f->n_px = static_cast<size_t>(rows) * shape->width;
+  hipError_t e = f->sums.alloc(f->n_px * 6);
+  if (e == hipSuccess) e = f->hits.alloc(f->n_px);
+  if (e == hipSuccess) e = f->depth.alloc(f->n_px);
+  if (e == hipSuccess) e = feat_reset(f, nullptr);
+  return frame_created("rt_feat_create", f, e, out);
+}
+
+extern "C" int rt_feat_free(rt_feat* f) { return frame_free(f); }
+
+extern "C" int rt_feat_clear(rt_feat* f, void* hip_stream) {
+  clear_error();
+  if (!f) return set_error(RT_E_ARG, "rt_feat_clear: NULL argument");
+  std::lock_guard<std::mutex> lk(f->mu);
+  HIP_TRY(hipSetDevice(f->device));
+  HIP_TRY(feat_reset(f, static_cast<hipStream_t>(hip_stream)));
+  f->samples = 0;
+  return RT_OK;
+}
+
+extern "C" int64_t rt_feat_samples(const rt_feat* f) { return frame_samples(f); }
+
+extern "C" int rt_launch_feat(const rt_dscene* ds, const rt_camera* c, const rt_params* p, rt_feat* f,
+                              uint64_t* d_counters, void* hip_stream) {
+  clear_error();
+  if (!ds || !c || !p || !f) return set_error(RT_E_ARG, "rt_launch_feat: NULL argument");
+  if (const int rc = check_frame_args("rt_launch_feat", *p)) return rc;
+  std::lock_guard<std::mutex> lk(f->mu);
+  if (const int rc = check_pass("rt_launch_feat", "the feature buffers", *f, *ds, *p)) return rc;
+  if (p->spp == 0) return RT_OK;
+  const int rows = rows_out(*p);
+  HIP_TRY(hipSetDevice(ds->device));
+  const policy::Scene si = scene_info(*ds);
+  const int src = policy::feat_source(si, selected_variant(), diag_build());
+  const DTree& tr = ds->tree[1];
+  FeatArgs a{};
+  a.geo = ds->geo;
+  a.sph = ds->sph;
+  a.mat = ds->mat;
+  a.kind = ds->kind;
+  a.blob = tr.blob;
+  a.blob_f4 = tr.blob_f4;
+  a.off_pairs = tr.off_pairs;
+  a.off_pidx = tr.off_pidx;
+  a.leaf_pairs = 2;
+  a.big_pair0 = tr.big_pair0;
+  a.n_big_leaves = tr.n_big_leaves;
+  a.ref_mul = 1;   // (rt_scene_upload made the 4-body tree's inner refs byte offsets)
+  for (int k = 0; k < 3; ++k) a.bvh_c[k] = tr.c[k];
+  a.bvh_r = tr.r;
+  a.bvh_c0 = tr.c0;
+  pack_frame(a, *c, *p, rows);
+  a.n = ds->n;
+  a.tiles_x = (p->width + kTile - 1) / kTile;
+  a.sums = f->sums.p;
+  a.hits = f->hits.p;
+  a.depth = f->depth.p;
+  a.counters = reinterpret_cast<unsigned long long*>(d_counters);
+  const int gy = (rows + kTile - 1) / kTile;
+  HIP_TRY(enqueue(feat_fn(src), dim3(static_cast<unsigned>(a.tiles_x * gy)), dim3(kFeatThreads), policy::feat_lds(si, src),
+                  static_cast<hipStream_t>(hip_stream), a));
+  f->samples += p->spp;
+  return RT_OK;
+}
+
+extern "C" int rt_feat_resolve(const rt_feat* f, float* d_out, void* hip_stream) {
+  clear_error();
+  if (!f || !d_out) return set_error(RT_E_ARG, "rt_feat_resolve: NULL argument");
+  const int64_t count = frame_samples(f);
+  HIP_TRY(hipSetDevice(f->device));
+  const float nf = static_cast<float>(count > 0 ? count : 1);   // RN(float(n))
+  const size_t blocks = std::max<size_t>(1, std::min<size_t>((f->n_px + 255) / 256, 4096));
+  HIP_TRY(enqueue(feat_resolve_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, static_cast<hipStream_t>(hip_stream),
+                  f->sums.p, f->hits.p, f->depth.p, f->n_px, nf, d_out));
+  return RT_OK;
+}
+
+extern "C" int rt_feat_read(const rt_feat* f, int64_t* host_sums, uint32_t* host_hits, float* host_depth,
+                            void* hip_stream) {
+  clear_error();
+  if (!f || !host_sums || !host_hits || !host_depth) return set_error(RT_E_ARG, "rt_feat_read: NULL argument");
+  HIP_TRY(hipSetDevice(f->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  HIP_TRY(hipMemcpyAsync(host_sums, f->sums.p, f->n_px * 6 * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(host_hits, f->hits.p, f->n_px * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(host_depth, f->depth.p, f->n_px * sizeof(float), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return RT_OK;
+}
+
+extern "C" int rt_feat_add(rt_feat* f, const int64_t* host_sums, const uint32_t* host_hits, const float* host_depth,
+                           int64_t samples, void* hip_stream) {
+  clear_error();
+  if (!f || !host_sums || !host_hits || !host_depth) return set_error(RT_E_ARG, "rt_feat_add: NULL argument");
+  std::lock_guard<std::mutex> lk(f->mu);
+  if (const int rc = check_add("rt_feat_add", *f, samples)) return rc;
+  for (size_t i = 0; i < f->n_px; ++i)   // (a depth is a positive distance or +inf: the minimum runs on the bits)
+    if (!(host_depth[i] > 0.0f)) return set_error(RT_E_ARG, "rt_feat_add: a depth is not a positive distance or +inf");
+  HIP_TRY(hipSetDevice(f->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  // one staging block: sums | hits | depth (freed when the call returns)
+  const size_t sb = f->n_px * 6 * sizeof(uint64_t), wb = f->n_px * sizeof(uint32_t);
+  DevBuf<char> stage;
+  HIP_TRY(stage.alloc(sb + 2 * wb));
+  hipError_t e = hipMemcpyAsync(stage.p, host_sums, sb, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(stage.p + sb, host_hits, wb, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(stage.p + sb + wb, host_depth, wb, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) {
+    const size_t blocks = std::max<size_t>(1, std::min<size_t>((f->n_px + 255) / 256, 4096));
+    e = enqueue(feat_add_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, f->sums.p, f->hits.p,
+                f->depth.p, reinterpret_cast<const unsigned long long*>(stage.p),
+                reinterpret_cast<const unsigned*>(stage.p + sb), reinterpret_cast<const unsigned*>(stage.p + sb + wb),
+                f->n_px);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return hip_fail(e, "rt_feat_add");
+  f->samples += samples;
+  return RT_OK;
+}
+
+// The feature kernel a launch on ds would run under the current selector
+// (diagnostic, tools/feat_time.py): out4 = {workgroups per CU, VGPRs per lane,
+// LDS bytes per workgroup, the bodies' source: 0 tree in LDS, 1 tree in global
+// memory, 2 linear scan}.
+extern "C" int rt_feat_occupancy(const rt_dscene* ds, int* out4) {
+  clear_error();
+  if (!ds || !out4) return set_error(RT_E_ARG, "rt_feat_occupancy: NULL argument");
+  HIP_TRY(hipSetDevice(ds->device));
+  const policy::Scene si = scene_info(*ds);
+  const int src = policy::feat_source(si, selected_variant(), diag_build());
+  if (const int rc = occupancy_report(feat_fn(src), kFeatThreads, policy::feat_lds(si, src), out4)) return rc;
+  out4[3] = src;
+  return RT_OK;
+}
+
+// ---- the body-id pass (rt.h, body_ids.h) --------------------------------------
+static const void* ids_fn(int src) {
+  return src == FEAT_LDS      ? reinterpret_cast<const void*>(&ids_kernel<FEAT_LDS>)
+         : src == FEAT_GLOBAL ? reinterpret_cast<const void*>(&ids_kernel<FEAT_GLOBAL>)
+                              : reinterpret_cast<const void*>(&ids_kernel<FEAT_SCAN>);
+}
+
+extern "C" int rt_launch_ids(const rt_dscene* ds, const rt_camera* c, int width, int rows, int row0, int32_t* d_ids,
+                             void* hip_stream) {
+  clear_error();
+  const std::string me("rt_launch_ids");
+  if (!ds || !c || !d_ids) return set_error(RT_E_ARG, me + ": NULL argument");
+  if (const char* why = tp_shape_error(width, rows, row0)) return set_error(RT_E_ARG, me + ": " + why);
+  // (the kernel's grid has a block row per kDnBy image rows)
+  if ((rows + kDnBy - 1) / kDnBy > 65535) return set_error(RT_E_ARG, me + ": bad width/rows");
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (const int rc = stream_on_device(me, stream, ds->device, "the scene")) return rc;
+  HIP_TRY(hipSetDevice(ds->device));
+  const policy::Scene si = scene_info(*ds);
+  const int src = policy::ids_source(si, selected_variant(), diag_build());
+  const DTree& tr = ds->tree[1];
+  IdsArgs a{};
+  a.geo = ds->geo;
+  a.blob = tr.blob;
+  a.blob_f4 = tr.blob_f4;
+  a.off_pairs = tr.off_pairs;
+  a.off_pidx = tr.off_pidx;
+  a.leaf_pairs = 2;
+  a.big_pair0 = tr.big_pair0;
+  a.n_big_leaves = tr.n_big_leaves;
+  a.ref_mul = 1;   // (rt_scene_upload made the 4-body tree's inner refs byte offsets)
+  for (int k = 0; k < 3; ++k) a.bvh_c[k] = tr.c[k];
+  a.bvh_r = tr.r;
+  a.bvh_c0 = tr.c0;
+  ids_cam12(*c, a.cam);
+  a.n = ds->n;
+  a.width = width;
+  a.rows = rows;
+  a.row0 = row0;
+  a.ids = d_ids;
+  const dim3 grid(static_cast<unsigned>((width + kDnBx - 1) / kDnBx), static_cast<unsigned>((rows + kDnBy - 1) / kDnBy)),
+      block(kDnBx, kDnBy);
+  HIP_TRY(enqueue(ids_fn(src), grid, block, policy::feat_lds(si, src), stream, a));
+  return RT_OK;
+}
+
+// The body-id kernel a launch on ds would run under the current selector
+// (diagnostic, tools/motion_time.py): out4 as rt_feat_occupancy's.
+extern "C" int rt_ids_occupancy(const rt_dscene* ds, int* out4) {
+  clear_error();
+  if (!ds || !out4) return set_error(RT_E_ARG, "rt_ids_occupancy: NULL argument");
+  HIP_TRY(hipSetDevice(ds->device));
+  const policy::Scene si = scene_info(*ds);
+  const int src = policy::ids_source(si, selected_variant(), diag_build());
+  if (const int rc = occupancy_report(ids_fn(src), kFeatThreads, policy::feat_lds(si, src), out4)) return rc;
+  out4[3] = src;
+  return RT_OK;
+}

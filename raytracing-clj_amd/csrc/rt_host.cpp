@@ -179,7 +179,7 @@ extern "C" int rt_quantize(const float* lin, uint8_t* out, size_t n) {
   return RT_OK;
 }
 
-// rt_accum_resolve's conversion on the host (trace.hip's resolve_kernel and
+// rt_accum_resolve's conversion on the host (frames.hip's resolve_kernel and
 // finalize_kernel, the kernel's write_mean): RN(float(sum)) * 2^-24, then
 // / RN(float(n)) (realm: * (1 / RN(float(n)))), every step one IEEE fp32
 // operation (the library is built with -ffp-contract=off)
@@ -198,7 +198,7 @@ extern "C" int rt_resolve_sums(const uint64_t* sums, size_t n, int64_t samples, 
   return RT_OK;
 }
 
-// The adaptive sampler's rule on the host (trace.hip's adapt_eval_kernel):
+// The adaptive sampler's rule on the host (frames.hip's adapt_eval_kernel):
 // per 8 x 8 tile, over its pixels inside the frame, D = sum |h0 - h1| and
 // S = sum (h0 + h1) (192 terms below 2^56 each: below 2^64), converged iff
 // D * 2^16 <= tol * S, the products in 128 bits.
@@ -227,7 +227,7 @@ extern "C" int rt_adapt_eval_host(const uint64_t* sums0, const uint64_t* sums1, 
   return RT_OK;
 }
 
-// rt_adapt_resolve's conversion on the host (trace.hip's
+// rt_adapt_resolve's conversion on the host (frames.hip's
 // adapt_resolve_kernel): rt_resolve_sums of h0 + h1 with the count of the
 // element's tile
 extern "C" int rt_adapt_resolve_host(const uint64_t* sums0, const uint64_t* sums1, const uint32_t* counts,

@@ -1,4 +1,4 @@
-// Internal helpers shared by trace.hip and rt_host.cpp (not part of the ABI).
+// Internal helpers shared by the .hip units and rt_host.cpp (not part of the ABI).
 #pragma once
 #include <cstdint>
 #include <string>
@@ -11,7 +11,7 @@ namespace rtclj {
 int set_error(int code, const std::string& msg);
 void clear_error();
 
-// RNG keying shared by host and device (see trace.hip, "RNG").
+// RNG keying shared by host and device (see trace_kernel.h, "RNG").
 //   lowbias32 integer hash (C. Wellons' hash-prospector result).
 #if defined(__HIPCC__)
 __host__ __device__

@@ -620,8 +620,19 @@ struct TpPacked {
 // motion and meet in the vector L1 and the L2 -- and the three new history
 // words and both outputs are written by the owning thread.  The old and the
 // new history are different buffers (rt_temporal's two sets).
-__global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_kernel(
-    const TpFrame f, const float* __restrict__ half0, const float* __restrict__ half1, const float* __restrict__ feat,
+// The four step kernels' thread.  MOTION adds the pixel's body id (one dword)
+// and, for an id inside the table, that body's row (one 16-byte word;
+// neighbouring pixels mostly share a body, and the whole table -- 16 bytes a
+// body -- stays in the caches; a sky pixel loads neither); BOX the pixel's own
+// two box words -- loaded only when there is a previous camera: the first step
+// enqueues no box kernel; WEIGHT one dword of the tile's multiplier (a wave's
+// 64 pixels lie in eight tiles of one tile row: eight dwords, one cache line).
+// What a kernel's switches leave out is not read.
+template <bool MOTION, bool BOX, bool WEIGHT>
+__device__ __forceinline__ void tp_step_thread(
+    const TpFrame& f, const float* __restrict__ half0, const float* __restrict__ half1, const float* __restrict__ feat,
+    const int32_t* __restrict__ ids, const float* __restrict__ motion, const int n_bodies,
+    const uint32_t* __restrict__ mult, const TpWord* __restrict__ box_lo, const TpWord* __restrict__ box_hi,
     const TpWord* __restrict__ prev_a0, const TpWord* __restrict__ prev_a1, const DnGuide* __restrict__ prev_g,
     TpWord* __restrict__ new_a0, TpWord* __restrict__ new_a1, DnGuide* __restrict__ new_g, float* __restrict__ out0,
     float* __restrict__ out1) {
@@ -629,7 +640,8 @@ __global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_kernel(
   const int y = static_cast<int>(blockIdx.y) * kDnBy + static_cast<int>(threadIdx.y);
   if (x >= f.width || y >= f.rows) return;
   const size_t i = static_cast<size_t>(y) * f.width + x;
-  float h0[3], h1[3], ft[RT_FEAT_CHANNELS], o0[3], o1[3];
+  float h0[3], h1[3], ft[RT_FEAT_CHANNELS], o0[3], o1[3], m[3] = {0.0f, 0.0f, 0.0f};
+  float box[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     h0[c] = half0[i * 3 + c];
@@ -637,8 +649,15 @@ __global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_kernel(
   }
 #pragma unroll
   for (int c = 0; c < RT_FEAT_CHANNELS; ++c) ft[c] = feat[i * RT_FEAT_CHANNELS + c];
+  if (MOTION && tp_finite(ft[6])) tp_motion(ids[i], motion, n_bodies, m);
+  if (BOX && f.have_prev) {
+    const TpWord lo = box_lo[i], hi = box_hi[i];
+    box[0] = lo.r, box[1] = lo.g, box[2] = lo.b;
+    box[3] = hi.r, box[4] = hi.g, box[5] = hi.b;
+  }
+  const float wt = WEIGHT ? tp_weight_at(mult, f.width, x, y) : 1.0f;
   const TpPacked src{prev_a0, prev_a1, prev_g};
-  const float n = tp_pixel<false>(src, f, x, y, h0, h1, ft, nullptr, o0, o1);
+  const float n = tp_pixel<MOTION, BOX, WEIGHT>(src, f, x, y, h0, h1, ft, m, o0, o1, box, wt);
   new_a0[i] = TpWord{o0[0], o0[1], o0[2], n};
   new_a1[i] = TpWord{o1[0], o1[1], o1[2], 0.0f};
   new_g[i] = DnGuide{ft[3], ft[4], ft[5], ft[6]};
@@ -649,39 +668,24 @@ __global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_kernel(
   }
 }
 
-// rt_temporal_step_motion's kernel: the same thread, loads and stores, plus the
-// pixel's body id (one dword) and, for an id inside the table, that body's row
-// (one 16-byte word; neighbouring pixels mostly share a body, and the whole
-// table -- 16 bytes a body -- stays in the caches).  A sky pixel loads neither.
+__global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_kernel(
+    const TpFrame f, const float* __restrict__ half0, const float* __restrict__ half1, const float* __restrict__ feat,
+    const TpWord* __restrict__ prev_a0, const TpWord* __restrict__ prev_a1, const DnGuide* __restrict__ prev_g,
+    TpWord* __restrict__ new_a0, TpWord* __restrict__ new_a1, DnGuide* __restrict__ new_g, float* __restrict__ out0,
+    float* __restrict__ out1) {
+  tp_step_thread<false, false, false>(f, half0, half1, feat, nullptr, nullptr, 0, nullptr, nullptr, nullptr, prev_a0,
+                                      prev_a1, prev_g, new_a0, new_a1, new_g, out0, out1);
+}
+
+// rt_temporal_step_motion's kernel
 __global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_motion_kernel(
     const TpFrame f, const float* __restrict__ half0, const float* __restrict__ half1, const float* __restrict__ feat,
     const int32_t* __restrict__ ids, const float* __restrict__ motion, const int n_bodies,
     const TpWord* __restrict__ prev_a0, const TpWord* __restrict__ prev_a1, const DnGuide* __restrict__ prev_g,
     TpWord* __restrict__ new_a0, TpWord* __restrict__ new_a1, DnGuide* __restrict__ new_g, float* __restrict__ out0,
     float* __restrict__ out1) {
-  const int x = static_cast<int>(blockIdx.x) * kDnBx + static_cast<int>(threadIdx.x);
-  const int y = static_cast<int>(blockIdx.y) * kDnBy + static_cast<int>(threadIdx.y);
-  if (x >= f.width || y >= f.rows) return;
-  const size_t i = static_cast<size_t>(y) * f.width + x;
-  float h0[3], h1[3], ft[RT_FEAT_CHANNELS], o0[3], o1[3], m[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    h0[c] = half0[i * 3 + c];
-    h1[c] = half1[i * 3 + c];
-  }
-#pragma unroll
-  for (int c = 0; c < RT_FEAT_CHANNELS; ++c) ft[c] = feat[i * RT_FEAT_CHANNELS + c];
-  if (tp_finite(ft[6])) tp_motion(ids[i], motion, n_bodies, m);
-  const TpPacked src{prev_a0, prev_a1, prev_g};
-  const float n = tp_pixel<true>(src, f, x, y, h0, h1, ft, m, o0, o1);
-  new_a0[i] = TpWord{o0[0], o0[1], o0[2], n};
-  new_a1[i] = TpWord{o1[0], o1[1], o1[2], 0.0f};
-  new_g[i] = DnGuide{ft[3], ft[4], ft[5], ft[6]};
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    out0[i * 3 + c] = o0[c];
-    out1[i * 3 + c] = o1[c];
-  }
+  tp_step_thread<true, false, false>(f, half0, half1, feat, ids, motion, n_bodies, nullptr, nullptr, nullptr, prev_a0,
+                                     prev_a1, prev_g, new_a0, new_a1, new_g, out0, out1);
 }
 
 // ---- the clamp (rt_temporal_step_clamp) ----
@@ -744,10 +748,8 @@ __global__ __launch_bounds__(kDnBx* kDnBy) void temporal_box_kernel(
   box_hi[i] = TpWord{hi[0], hi[1], hi[2], 0.0f};
 }
 
-// rt_temporal_step_clamp's step kernel: temporal_step_kernel's (MOTION = false;
-// ids, motion and n_bodies are not read) or temporal_step_motion_kernel's
-// thread, loads and stores, plus the pixel's own two box words -- loaded only
-// when there is a previous camera: the first step enqueues no box kernel.
+// rt_temporal_step_clamp's step kernel (MOTION = false: ids, motion and
+// n_bodies are not read)
 template <bool MOTION>
 __global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_clamp_kernel(
     const TpFrame f, const float* __restrict__ half0, const float* __restrict__ half1, const float* __restrict__ feat,
@@ -755,35 +757,8 @@ __global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_clamp_kernel(
     const TpWord* __restrict__ box_lo, const TpWord* __restrict__ box_hi, const TpWord* __restrict__ prev_a0,
     const TpWord* __restrict__ prev_a1, const DnGuide* __restrict__ prev_g, TpWord* __restrict__ new_a0,
     TpWord* __restrict__ new_a1, DnGuide* __restrict__ new_g, float* __restrict__ out0, float* __restrict__ out1) {
-  const int x = static_cast<int>(blockIdx.x) * kDnBx + static_cast<int>(threadIdx.x);
-  const int y = static_cast<int>(blockIdx.y) * kDnBy + static_cast<int>(threadIdx.y);
-  if (x >= f.width || y >= f.rows) return;
-  const size_t i = static_cast<size_t>(y) * f.width + x;
-  float h0[3], h1[3], ft[RT_FEAT_CHANNELS], o0[3], o1[3], m[3] = {0.0f, 0.0f, 0.0f};
-  float box[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    h0[c] = half0[i * 3 + c];
-    h1[c] = half1[i * 3 + c];
-  }
-#pragma unroll
-  for (int c = 0; c < RT_FEAT_CHANNELS; ++c) ft[c] = feat[i * RT_FEAT_CHANNELS + c];
-  if (MOTION && tp_finite(ft[6])) tp_motion(ids[i], motion, n_bodies, m);
-  if (f.have_prev) {
-    const TpWord lo = box_lo[i], hi = box_hi[i];
-    box[0] = lo.r, box[1] = lo.g, box[2] = lo.b;
-    box[3] = hi.r, box[4] = hi.g, box[5] = hi.b;
-  }
-  const TpPacked src{prev_a0, prev_a1, prev_g};
-  const float n = tp_pixel<MOTION, true>(src, f, x, y, h0, h1, ft, m, o0, o1, box);
-  new_a0[i] = TpWord{o0[0], o0[1], o0[2], n};
-  new_a1[i] = TpWord{o1[0], o1[1], o1[2], 0.0f};
-  new_g[i] = DnGuide{ft[3], ft[4], ft[5], ft[6]};
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    out0[i * 3 + c] = o0[c];
-    out1[i * 3 + c] = o1[c];
-  }
+  tp_step_thread<MOTION, true, false>(f, half0, half1, feat, ids, motion, n_bodies, nullptr, box_lo, box_hi, prev_a0,
+                                      prev_a1, prev_g, new_a0, new_a1, new_g, out0, out1);
 }
 
 // ---- the budget (rt_temporal_probe, rt_temporal_step_budget) ----
@@ -815,10 +790,8 @@ __global__ __launch_bounds__(kDnBx* kDnBy) void temporal_probe_kernel(
   out_len[i] = tp_pixel<MOTION, false, false, true>(src, f, x, y, nullptr, nullptr, ft, m, nullptr, nullptr);
 }
 
-// rt_temporal_step_budget's step kernel: temporal_step_clamp_kernel's thread,
-// loads and stores, plus one dword of the tile's multiplier (a wave's 64
-// pixels lie in eight tiles of one tile row: eight dwords, one cache line).
-// BOX = false (gamma = +inf, which clamps nothing: rt.h): no box is read.
+// rt_temporal_step_budget's step kernel.  BOX = false (gamma = +inf, which
+// clamps nothing: rt.h): no box is read.
 template <bool MOTION, bool BOX>
 __global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_budget_kernel(
     const TpFrame f, const float* __restrict__ half0, const float* __restrict__ half1, const float* __restrict__ feat,
@@ -827,36 +800,8 @@ __global__ __launch_bounds__(kDnBx* kDnBy) void temporal_step_budget_kernel(
     const TpWord* __restrict__ prev_a0, const TpWord* __restrict__ prev_a1, const DnGuide* __restrict__ prev_g,
     TpWord* __restrict__ new_a0, TpWord* __restrict__ new_a1, DnGuide* __restrict__ new_g, float* __restrict__ out0,
     float* __restrict__ out1) {
-  const int x = static_cast<int>(blockIdx.x) * kDnBx + static_cast<int>(threadIdx.x);
-  const int y = static_cast<int>(blockIdx.y) * kDnBy + static_cast<int>(threadIdx.y);
-  if (x >= f.width || y >= f.rows) return;
-  const size_t i = static_cast<size_t>(y) * f.width + x;
-  float h0[3], h1[3], ft[RT_FEAT_CHANNELS], o0[3], o1[3], m[3] = {0.0f, 0.0f, 0.0f};
-  float box[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    h0[c] = half0[i * 3 + c];
-    h1[c] = half1[i * 3 + c];
-  }
-#pragma unroll
-  for (int c = 0; c < RT_FEAT_CHANNELS; ++c) ft[c] = feat[i * RT_FEAT_CHANNELS + c];
-  if (MOTION && tp_finite(ft[6])) tp_motion(ids[i], motion, n_bodies, m);
-  if (BOX && f.have_prev) {
-    const TpWord lo = box_lo[i], hi = box_hi[i];
-    box[0] = lo.r, box[1] = lo.g, box[2] = lo.b;
-    box[3] = hi.r, box[4] = hi.g, box[5] = hi.b;
-  }
-  const float wt = tp_weight_at(mult, f.width, x, y);
-  const TpPacked src{prev_a0, prev_a1, prev_g};
-  const float n = tp_pixel<MOTION, BOX, true>(src, f, x, y, h0, h1, ft, m, o0, o1, box, wt);
-  new_a0[i] = TpWord{o0[0], o0[1], o0[2], n};
-  new_a1[i] = TpWord{o1[0], o1[1], o1[2], 0.0f};
-  new_g[i] = DnGuide{ft[3], ft[4], ft[5], ft[6]};
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    out0[i * 3 + c] = o0[c];
-    out1[i * 3 + c] = o1[c];
-  }
+  tp_step_thread<MOTION, BOX, true>(f, half0, half1, feat, ids, motion, n_bodies, mult, box_lo, box_hi, prev_a0, prev_a1,
+                                    prev_g, new_a0, new_a1, new_g, out0, out1);
 }
 #endif  // __HIPCC__ && RT_TEMPORAL_KERNEL
 

@@ -4,7 +4,7 @@
 // level order its node pass follows, the pass itself over bvh_refit.h's one
 // text, and the surface-area cost that tells how far a refitted tree has
 // loosened.  Behind rt_tree_build_host, rt_tree_refit_host, rt_tree_cost_host
-// (rt_host.cpp) and rt_scene_upload / rt_scene_update (trace.hip).
+// (rt_host.cpp) and rt_scene_upload / rt_scene_update (trace.hip, refit.hip).
 #if defined(__HIP__)
 #include <hip/hip_runtime.h>   // (the library builds every source as HIP; bvh_pad.h then wants its qualifiers)
 #endif

@@ -15,7 +15,7 @@ namespace rtclj {
 namespace policy {
 
 // The kernels' shapes the policy sizes by (trace_kernel.h, first_hit.h;
-// trace.hip asserts that they are the kernels')
+// trace.hip and first_hit.hip assert that they are the kernels')
 constexpr int kTile = 8;
 constexpr int kPoolPx = kTile * kTile;
 constexpr size_t kXBytes = 8 * 11 * 64 * 4;   // the sorted kernel's exchange buffer
