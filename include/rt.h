@@ -226,6 +226,19 @@ int rt_camera_setup(int image_width, int image_height, double vfov,
                     const double vup[3], double defocus_angle,
                     double focus_dist, rt_camera* out);
 
+/* The camera of a frame of ceil(width / scale) x ceil(height / scale) pixels
+ * whose pixel (I, J) covers the pixels [scale I, scale I + scale) x [scale J,
+ * scale J + scale) of c's frame -- raytracing.clj:129-135's pixel deltas and
+ * pixel00-loc for a viewport divided scale times more coarsely.  In double
+ * from c's float fields, each component rounded to float once:
+ *   p00' = p00 + ((scale - 1) / 2) * (du + dv),  du' = scale * du,  dv' = scale * dv;
+ * center, disk_u, disk_v and defocus are copied.  A pixel's sample is
+ * p00 + fx du + fy dv with the jitter in fx, fy, so a sample of the coarse
+ * frame falls uniformly over its whole block.  scale is 2..4, else RT_E_ARG
+ * (as is a NULL argument); out may be c.  rt_upsample brings such a frame back
+ * to c's size. */
+int rt_camera_coarsen(const rt_camera* c, int scale, rt_camera* out);
+
 /* write-color! per channel (raytracing.clj:19-26):
  * out = int(256 * clamp(c > 0 ? sqrt(c) : 0, 0, 0.999)); NaN -> 0.  n = channel count. */
 int rt_quantize(const float* lin, uint8_t* out, size_t n);
@@ -750,6 +763,83 @@ int rt_denoise_profile(rt_denoiser* dn, const rt_denoise_opts* o, const float* d
  * yardstick of the kernels, and a filter for frames that are on the host. */
 int rt_denoise_host(const rt_denoise_opts* o, const float* half0, const float* half1, const float* feat,
                     int width, int rows, float* out);
+
+/* ---- guided upsampling: colour traced on a coarse grid, rebuilt at full size ----
+ * A render scale: compute-pixel's loop (raytracing.clj:141-155) run for the
+ * frame of rt_camera_coarsen's camera (raytracing.clj:129-135), one pixel per
+ * s x s block of the frame's pixels, and its colour brought up to the frame's
+ * size through the frame's own first-hit features -- a joint bilateral
+ * upsampling (Kopf et al. 2007) of albedo-demodulated colour with rt_denoise's
+ * normal, coverage and depth weights.  The output has rt_denoise's and
+ * rt_temporal_step's input shape and feeds them unchanged.  The result is a
+ * function of the inputs and options alone: a fixed sequence of single fp32
+ * operations, each rounded once in the order written (no fma; / IEEE), which
+ * the device kernel, rt_upsample_host and a NumPy restatement
+ * (tests/test_upsample_host.py) give bit for bit, whatever the workgroup shape.
+ *
+ * Inputs, for a full-size image of rows x width pixels and s = scale, with
+ * cw = ceil(width / s), ch = ceil(rows / s):
+ *   half0, half1  ch x cw x 3 floats each: two estimates of the coarse frame
+ *                 from disjoint sample sets (half1 and out1 may both be NULL:
+ *                 one image; exactly one of them NULL is RT_E_ARG);
+ *   feat_coarse   ch x cw x 8 floats in rt_feat_resolve's layout, the coarse
+ *                 camera's features;
+ *   feat          rows x width x 8 floats likewise, the frame's own features.
+ * Outputs: out0, out1, rows x width x 3 floats each.
+ * Options (NULL: the defaults; outside the ranges: RT_E_ARG):
+ *   scale        2     2..4
+ *   normal_pow2  0     0..8        the normal weight is squared this many times
+ *   sigma_z      0.05  finite > 0  depth edge-stop, relative depth per fine pixel
+ *
+ * Per fine pixel p = (x, y):
+ *   1. Along x: ux = 2 x + 1 - s, X0 = floor(ux / 2 s) (an integer; -1 in the
+ *      first columns), ax = ux - 2 s X0 in [0, 2 s),
+ *      bx0 = float(2 s - ax) / float(2 s), bx1 = float(ax) / float(2 s).
+ *      The same along y.
+ *   2. Taps (Y0, X0), (Y0, X0 + 1), (Y0 + 1, X0), (Y0 + 1, X0 + 1) in that
+ *      order, those outside the coarse image skipped; b = by * bx.
+ *   3. Guides of p from feat, of a tap q from feat_coarse: n = feat[3..5],
+ *      z = feat[6], omc = 1 - feat[7].
+ *   4. dot = ((n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z) + omc_p * omc_q
+ *      wn = min(1, max(0, dot)), squared normal_pow2 times
+ *      wz = 1 where z_p and z_q are both +inf, 0 where exactly one is, else
+ *           r = |z_p - z_q| / ((sigma_z * float(s)) * min(z_p, z_q)),
+ *           wz = 1 / (1 + r * r)
+ *      w = (b * wn) * wz
+ *   5. Irradiance of tap q, half h, channel c:
+ *      i = half_h[q].c / max(feat_coarse[q].c, 2^-10)
+ *   6. In tap order, from 0:  acc_h.c += w * i,  wsum += w.
+ *   7. If !(wsum >= 2^-10): step 6 again with w = b (a thin feature that no
+ *      coarse pixel agrees with; the b of the taps inside the image sum to at
+ *      least 1/4, so wsum > 0 afterwards).
+ *   8. out_h.c = (acc_h.c / wsum) * max(feat[p].c, 2^-10).
+ *
+ * To know: the weights depend on the guides only, so the two outputs stay
+ * estimates from disjoint sample sets; but neighbouring output pixels share
+ * coarse samples, so rt_denoise's variance, which takes its taps as
+ * independent, is understated.  What the features cannot see
+ * -- a shadow's edge, a reflection, what lies behind glass -- comes back at
+ * the coarse resolution.
+ *
+ * The inputs are never written.  An output may not overlap an input or the
+ * other output (RT_E_ARG); RT_E_ARG too on a NULL required pointer, width or
+ * rows <= 0 or more than 2^31 - 1 pixels.  Values other than the library's own
+ * (NaN, a depth <= 0) give unspecified numbers, never an out-of-bounds access,
+ * a fault or a hang. */
+typedef struct rt_upsample_opts {
+  int scale, normal_pow2;
+  float sigma_z;
+} rt_upsample_opts;
+/* Asynchronous: one kernel enqueued on hip_stream (NULL: the default stream)
+ * of the device that holds d_out0.  All pointers are device pointers, aligned
+ * as floats.  Beyond the errors above: RT_E_ARG for more than 4 x 65535 rows
+ * or a stream of another device, RT_E_NODEV without a device. */
+int rt_upsample(const rt_upsample_opts* o, const float* d_half0, const float* d_half1, const float* d_feat_coarse,
+                const float* d_feat, int width, int rows, float* d_out0, float* d_out1, void* hip_stream);
+/* The same on the host, in plain C++ (no device; raytracing.clj:141-155): the
+ * yardstick of the kernel. */
+int rt_upsample_host(const rt_upsample_opts* o, const float* half0, const float* half1, const float* feat_coarse,
+                     const float* feat, int width, int rows, float* out0, float* out1);
 
 /* ---- temporal accumulation: history reprojected through first-hit depth -------
  * What a sequence of low-sample frames of compute-pixel's loop

@@ -1,14 +1,17 @@
 // image.hip — what works on finished images, and knows nothing of scenes: the
 // feature-guided denoiser (rt_denoiser, rt_denoise; denoise.h's kernels) and
 // temporal accumulation (rt_temporal and its steps: plain, motion, clamp,
-// budget, and the probe; temporal.h's kernels).  DESIGN.md §3.8, §3.9, §3.10,
-// §3.12, §3.13.
+// budget, and the probe; temporal.h's kernels) and guided upsampling
+// (rt_upsample; upsample.h's kernel).  DESIGN.md §3.8, §3.9, §3.10, §3.12,
+// §3.13, §3.14.
 #include <hip/hip_runtime.h>
 
 #define RT_DENOISE_KERNEL
 #include "denoise.h"
 #define RT_TEMPORAL_KERNEL
 #include "temporal.h"
+#define RT_UPSAMPLE_KERNEL
+#include "upsample.h"
 #include "launch.h"
 
 #include <algorithm>
@@ -464,5 +467,40 @@ extern "C" int rt_temporal_probe(const rt_temporal* t, const rt_temporal_opts* o
   else
     HIP_TRY(enqueue(temporal_probe_kernel<false>, grid, block, 0, stream, f, d_feat, static_cast<const int32_t*>(nullptr),
                     static_cast<const float*>(nullptr), 0, a0, g, d_len));
+  return RT_OK;
+}
+
+// ---- guided upsampling (rt.h, upsample.h) ---------------------
+// rt_upsample: the checks, the device that holds d_out0, one kernel.
+extern "C" int rt_upsample(const rt_upsample_opts* o, const float* d_half0, const float* d_half1,
+                           const float* d_feat_coarse, const float* d_feat, int width, int rows, float* d_out0,
+                           float* d_out1, void* hip_stream) {
+  clear_error();
+  const std::string me("rt_upsample");
+  const rt_upsample_opts opt = o ? *o : up_default_opts();
+  // (the kernel's grid has a block row per kDnBy image rows)
+  if (rows > 65535 * kDnBy) return set_error(RT_E_ARG, me + ": bad width/rows");
+  if (const char* why = up_args_error(opt, d_half0, d_half1, d_feat_coarse, d_feat, width, rows, d_out0, d_out1))
+    return set_error(RT_E_ARG, me + ": " + why);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return set_error(RT_E_NODEV, me + ": no device available");
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, d_out0) != hipSuccess ||
+      (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged)) {
+    (void)hipGetLastError();
+    return set_error(RT_E_ARG, me + ": d_out0 is not a device pointer");
+  }
+  const int device = at.device;
+  HIP_TRY(hipSetDevice(device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (const int rc = stream_on_device(me, stream, device, "d_out0")) return rc;
+  const dim3 grid(static_cast<unsigned>((width + kDnBx - 1) / kDnBx), static_cast<unsigned>((rows + kDnBy - 1) / kDnBy)),
+      block(kDnBx, kDnBy);
+  const bool two = d_half1 != nullptr;
+  const auto fn = opt.scale == 2   ? (two ? upsample_kernel<2, true> : upsample_kernel<2, false>)
+                  : opt.scale == 3 ? (two ? upsample_kernel<3, true> : upsample_kernel<3, false>)
+                                   : (two ? upsample_kernel<4, true> : upsample_kernel<4, false>);
+  HIP_TRY(enqueue(fn, grid, block, 0, stream, d_half0, d_half1, d_feat_coarse, d_feat, width, rows, opt.normal_pow2,
+                  opt.sigma_z, d_out0, d_out1));
   return RT_OK;
 }

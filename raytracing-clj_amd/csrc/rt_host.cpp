@@ -37,6 +37,7 @@
 #include "rt_internal.h"
 #include "temporal.h"
 #include "budget.h"
+#include "upsample.h"
 
 namespace rtclj {
 
@@ -119,6 +120,22 @@ extern "C" int rt_camera_setup(int image_width, int image_height, double vfov,
   put(out->disk_u, mul(u, radius));
   put(out->disk_v, mul(v, radius));
   out->defocus = defocus_angle > 0 ? 1 : 0;  // (<= defocus-angle 0) -> centre (:147)
+  return RT_OK;
+}
+
+// The camera of the frame whose pixel is a scale x scale block of c's pixels:
+// raytracing.clj:129-135's pixel deltas and pixel00-loc for a viewport divided
+// scale times more coarsely, in double from c's floats, rounded once
+extern "C" int rt_camera_coarsen(const rt_camera* c, int scale, rt_camera* out) {
+  clear_error();
+  if (!c || !out) return set_error(RT_E_ARG, "rt_camera_coarsen: NULL argument");
+  if (scale < kUpMinScale || scale > kUpMaxScale) return set_error(RT_E_ARG, "rt_camera_coarsen: scale outside 2..4");
+  const rt_camera in = *c;   // (out may be c)
+  const D3 p00{in.p00[0], in.p00[1], in.p00[2]}, du{in.du[0], in.du[1], in.du[2]}, dv{in.dv[0], in.dv[1], in.dv[2]};
+  *out = in;
+  put(out->p00, add(p00, mul(add(du, dv), (scale - 1) / 2.0)));   // the block's centre (:135)
+  put(out->du, mul(du, scale));                                   // (:129)
+  put(out->dv, mul(dv, scale));                                   // (:130)
   return RT_OK;
 }
 
@@ -301,6 +318,17 @@ extern "C" int rt_denoise_host(const rt_denoise_opts* o, const float* half0, con
   const std::vector<DnTexel>& last = tex[opt.levels & 1];
   for (size_t i = 0; i < n_px; ++i) dn_finish(last[i], feat + RT_FEAT_CHANNELS * i, out + 3 * i);
   return RT_OK;
+}
+
+// rt_upsample on the host (upsample.h's up_host: the checks and up_pixel, the
+// text the kernel runs)
+extern "C" int rt_upsample_host(const rt_upsample_opts* o, const float* half0, const float* half1,
+                                const float* feat_coarse, const float* feat, int width, int rows, float* out0,
+                                float* out1) {
+  clear_error();
+  const char* why = nullptr;
+  const int rc = up_host(o, half0, half1, feat_coarse, feat, width, rows, out0, out1, &why);
+  return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_upsample_host: ") + (why ? why : "failed"));
 }
 
 // rt_temporal_step on the host (temporal.h's tp_host_step: the checks and

@@ -16,7 +16,7 @@
 //           [--seed S] [--gpus N] [--out PATH] [--png PATH] [--no-png] [--json]
 //           [--host-quantize] [--rejection-samplers] [--passes K]
 //           [--adaptive TOLQ16 [--step S] [--min-spp A] [--max-spp B]]
-//           [--features STEM] [--denoise STEM]
+//           [--features STEM] [--denoise STEM [--scale N]]
 // Defaults follow the reference: spp 100, depth 50, width 400, 16:9.
 // --passes K: the spp in K near-equal accumulating passes on device 0
 // (rt_launch_accum into an rt_accum, the sums read back, rt_resolve_sums and
@@ -39,6 +39,11 @@
 // of all spp, resolved on the device and filtered by rt_denoise with its
 // default options (include/rt.h): STEM.denoised.ppm and STEM.denoised.png hold
 // rt_quantize of the result.  An odd spp is an error (exit status 2).
+// --scale N (2..4, with --denoise): the two accumulators and a second feature
+// pass run on rt_camera_coarsen's camera at ceil(width / N) x ceil(height / N),
+// spp samples per coarse pixel; rt_upsample (default options but the scale)
+// brings the halves up to the frame's size through the frame's own features
+// before rt_denoise.  Without --denoise, or outside 2..4: exit status 2.
 // --json: one more line, a JSON object of where this one-frame process's time
 // went (the device start-up -- the HIP runtime's first rt_device_count, then
 // rt_prepare's context / code object / queue / pageable staging -- on a thread
@@ -63,6 +68,8 @@
 int main(int argc, char** argv) {
   int spp = 100, depth = 50, width = 400, gpus = 0, grid = 11, passes = 0;
   int ad_step = 10, ad_min = 0, ad_max = 0;
+  int scale = 0;   // --scale: the render scale of --denoise's frame (0: off)
+  bool scale_given = false;
   long long ad_tol = -1;   // --adaptive: the tolerance (< 0: off)
   long long ad_samples = 0;
   int ad_tiles = 0, ad_cap_tiles = 0, ad_steps = 0;
@@ -84,7 +91,8 @@ int main(int argc, char** argv) {
   // (a missing option value ends the process before the start-up thread
   // exists: no exit while that thread may be inside the HIP runtime)
   static const char* const kValued[] = {"--scene", "--width", "--seed", "--gpus", "--grid", "--out", "--png", "--passes",
-                                        "--adaptive", "--step", "--min-spp", "--max-spp", "--features", "--denoise"};
+                                        "--adaptive", "--step", "--min-spp", "--max-spp", "--features", "--denoise",
+                                        "--scale"};
   for (int i = 1; i < argc; ++i) {
     const bool valued = std::any_of(std::begin(kValued), std::end(kValued),
                                     [&](const char* f) { return std::strcmp(argv[i], f) == 0; });
@@ -125,6 +133,7 @@ int main(int argc, char** argv) {
     else if (a == "--max-spp") ad_max = std::atoi(val());
     else if (a == "--features") features = val();
     else if (a == "--denoise") denoise = val();
+    else if (a == "--scale") scale = std::atoi(val()), scale_given = true;
     else if (a == "--realm") realm = true;
     else if (a == "--rejection-samplers") rejection = true;   // RT_FLAG_REJECTION_SAMPLERS
     else if (a == "--json") json = true;
@@ -177,6 +186,10 @@ int main(int argc, char** argv) {
   const double prep_wait_ms = ms_since(t_start) - scene_ms;
   if (!denoise.empty() && (spp <= 0 || spp % 2 != 0)) {
     std::fprintf(stderr, "--denoise needs an even spp (two halves of spp / 2 samples), got %d\n", spp);
+    return 2;
+  }
+  if (scale_given && (denoise.empty() || scale < 2 || scale > 4)) {
+    std::fprintf(stderr, "--scale needs --denoise and a value of 2..4, got %d\n", scale);
     return 2;
   }
   rt_params p{};
@@ -337,33 +350,53 @@ int main(int argc, char** argv) {
   if (!denoise.empty()) {
     // the frame's rays as two halves and their features (raytracing.clj:141-155,
     // :144-151, :33-43), resolved and filtered on device 0
+    // (--scale: the halves and a second feature pass on the coarsened camera,
+    // :129-135, brought up to the frame's size by rt_upsample)
     const size_t npx = static_cast<size_t>(width) * height;
     rt_dscene* ds = nullptr;
     rt_accum* acc[2] = {nullptr, nullptr};
-    rt_feat* ft = nullptr;
+    rt_feat *ft = nullptr, *fc = nullptr;
     rt_denoiser* dn = nullptr;
-    float* d_buf = nullptr;   // half0 | half1 | out (3 floats a pixel each) | feat (8)
+    // half0 | half1 | out (3 floats a pixel each) | feat (8); with --scale then
+    // the coarse half0 | half1 (3 a coarse pixel each) | the coarse feat (8)
+    float* d_buf = nullptr;
     std::vector<float> lin(npx * 3);
     std::vector<uint8_t> b8(npx * 3);
     rt_params hp = p;
+    rt_camera hcam = cam;
+    if (scale) {
+      hp.width = (width + scale - 1) / scale;
+      hp.height = hp.row_end = (height + scale - 1) / scale;
+    }
+    const size_t ncp = scale ? static_cast<size_t>(hp.width) * hp.height : 0;
+    rt_params cp = hp;   // the coarse frame's feature pass: all spp
+    cp.n_devices = 0;
     hp.n_devices = 0;
     hp.spp = spp / 2;
     bool ok = rt_scene_upload(0, &s, &ds) == RT_OK && rt_feat_create(ds, &p, &ft) == RT_OK &&
-              rt_denoiser_create(0, width, height, &dn) == RT_OK;
+              rt_denoiser_create(0, width, height, &dn) == RT_OK &&
+              (!scale || (rt_camera_coarsen(&cam, scale, &hcam) == RT_OK && rt_feat_create(ds, &cp, &fc) == RT_OK));
     for (int k = 0; ok && k < 2; ++k) {
       hp.sample_begin = k * (spp / 2);
-      ok = rt_accum_create(ds, &hp, &acc[k]) == RT_OK && rt_launch_accum(ds, &cam, &hp, acc[k], nullptr, nullptr) == RT_OK;
+      ok = rt_accum_create(ds, &hp, &acc[k]) == RT_OK && rt_launch_accum(ds, &hcam, &hp, acc[k], nullptr, nullptr) == RT_OK;
     }
-    ok = ok && rt_launch_feat(ds, &cam, &p, ft, nullptr, nullptr) == RT_OK;
+    ok = ok && rt_launch_feat(ds, &cam, &p, ft, nullptr, nullptr) == RT_OK &&
+         (!scale || rt_launch_feat(ds, &hcam, &cp, fc, nullptr, nullptr) == RT_OK);
     if (!ok) std::fprintf(stderr, "--denoise failed: %s\n", rt_last_error());
-    if (ok && hipMalloc(reinterpret_cast<void**>(&d_buf), npx * (9 + RT_FEAT_CHANNELS) * sizeof(float)) != hipSuccess) {
+    if (ok && hipMalloc(reinterpret_cast<void**>(&d_buf),
+                        (npx * (9 + RT_FEAT_CHANNELS) + ncp * (6 + RT_FEAT_CHANNELS)) * sizeof(float)) != hipSuccess) {
       std::fprintf(stderr, "--denoise failed: no device memory for the frame\n");
       ok = false;
     }
     if (ok) {
       float *d_h0 = d_buf, *d_h1 = d_buf + npx * 3, *d_out = d_buf + npx * 6, *d_feat = d_buf + npx * 9;
-      ok = rt_accum_resolve(acc[0], p.flags, d_h0, nullptr) == RT_OK &&
-           rt_accum_resolve(acc[1], p.flags, d_h1, nullptr) == RT_OK && rt_feat_resolve(ft, d_feat, nullptr) == RT_OK &&
+      float *d_c0 = d_feat + npx * RT_FEAT_CHANNELS, *d_c1 = d_c0 + ncp * 3, *d_fc = d_c1 + ncp * 3;
+      rt_upsample_opts uo{scale, 0, 0.05f};   // (rt.h's defaults but the scale)
+      ok = rt_accum_resolve(acc[0], p.flags, scale ? d_c0 : d_h0, nullptr) == RT_OK &&
+           rt_accum_resolve(acc[1], p.flags, scale ? d_c1 : d_h1, nullptr) == RT_OK &&
+           rt_feat_resolve(ft, d_feat, nullptr) == RT_OK &&
+           (!scale || (rt_feat_resolve(fc, d_fc, nullptr) == RT_OK &&
+                       rt_upsample(&uo, d_c0, d_c1, d_fc, d_feat, width, height, d_h0, d_h1, nullptr) == RT_OK)) &&
            rt_denoise(dn, nullptr, d_h0, d_h1, d_feat, d_out, nullptr) == RT_OK;
       if (!ok) std::fprintf(stderr, "--denoise failed: %s\n", rt_last_error());
       if (ok && hipMemcpy(lin.data(), d_out, lin.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
@@ -380,6 +413,7 @@ int main(int argc, char** argv) {
     if (d_buf) (void)hipFree(d_buf);
     rt_denoiser_free(dn);
     rt_feat_free(ft);
+    rt_feat_free(fc);
     rt_accum_free(acc[0]);
     rt_accum_free(acc[1]);
     rt_scene_free(ds);

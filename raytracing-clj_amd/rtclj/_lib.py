@@ -82,6 +82,14 @@ class rt_denoise_opts(C.Structure):
 DENOISE_DEFAULTS = dict(levels=5, normal_pow2=5, sigma_c=4.0, sigma_z=0.05)
 
 
+class rt_upsample_opts(C.Structure):
+    _fields_ = [("scale", C.c_int), ("normal_pow2", C.c_int), ("sigma_z", C.c_float)]
+
+
+# rt_upsample's defaults (include/rt.h)
+UPSAMPLE_DEFAULTS = dict(scale=2, normal_pow2=0, sigma_z=0.05)
+
+
 class rt_temporal_opts(C.Structure):
     _fields_ = [("max_history", C.c_int), ("sigma_z", C.c_float), ("normal_min", C.c_float)]
 
@@ -124,6 +132,11 @@ BUDGET_DEFAULTS = dict(target=8, max_mult=8, quantile_64=16)
 SIGNATURES = {
     "rt_camera_setup": (C.c_int, [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   C.POINTER(C.c_double), C.c_double, C.c_double, C.POINTER(rt_camera)]),
+    "rt_camera_coarsen": (C.c_int, [C.POINTER(rt_camera), C.c_int, C.POINTER(rt_camera)]),
+    "rt_upsample": (C.c_int, [C.POINTER(rt_upsample_opts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_upsample_host": (C.c_int, [C.POINTER(rt_upsample_opts)] + [C.POINTER(C.c_float)] * 4 + [C.c_int, C.c_int] +
+                         [C.POINTER(C.c_float)] * 2),
     "rt_quantize": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.c_size_t]),
     "rt_write_ppm": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint8), C.c_int, C.c_int]),
     "rt_write_png": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint8), C.c_int, C.c_int]),
@@ -297,7 +310,8 @@ ADDITIVE = {"rt_prepare", "rt_render_u8", "rt_quantize_device", "rt_render_submi
             "rt_budget_mult_read", "rt_budget_device_mult", "rt_budget_samples", "rt_temporal_step_budget",
             "rt_temporal_host_budget", "rt_launch_ids", "rt_ids_host", "rt_ids_occupancy", "rt_body_motion",
             "rt_scene_update", "rt_tree_build_host", "rt_tree_refit_host", "rt_tree_cost_host", "rt_scene_tree_info",
-            "rt_scene_tree_read", "rt_schedule_read", "rt_schedule_sort"}
+            "rt_scene_tree_read", "rt_schedule_read", "rt_schedule_sort", "rt_camera_coarsen", "rt_upsample",
+            "rt_upsample_host"}
 
 RT_FEAT_CHANNELS = 8   # rt_feat_resolve's floats per pixel: albedo rgb, normal xyz, depth, coverage
 

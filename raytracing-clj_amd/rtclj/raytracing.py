@@ -27,7 +27,8 @@ from . import hittable, material
 from ._lib import (BUDGET_DEFAULTS, DENOISE_DEFAULTS, RT_DIELECTRIC, RT_FEAT_CHANNELS, RT_LAMBERTIAN, RT_METAL, RT_NONE,
                    TEMPORAL_CLAMP_DEFAULTS, TEMPORAL_DEFAULTS, RTError, check, dptr, fptr, i64ptr, iptr, lib,
                    rt_adapt_opts, rt_budget_opts, rt_camera, i32ptr, rt_denoise_opts, rt_params, rt_scene, rt_schedule_info, rt_stats,
-                   rt_temporal_clamp_opts, rt_temporal_opts, rt_tree_info, u8ptr, u32ptr, u64ptr)
+                   rt_temporal_clamp_opts, rt_temporal_opts, rt_tree_info, u8ptr, u32ptr, u64ptr,
+                   UPSAMPLE_DEFAULTS, rt_upsample_opts)
 
 # ---- scene (raytracing.clj:63-78) --------------------------------------------
 hittables = [
@@ -630,6 +631,133 @@ def render_denoised(scene, cam: rt_camera, width: int, height: int, spp: int = 8
         feat = d_feat.cpu().numpy().reshape(height, width, RT_FEAT_CHANNELS)
         out = d_out.cpu().numpy().reshape(height, width, 3)
     return out, np.float32(0.5) * (h0 + h1), feat
+
+
+def camera_coarsen(cam: rt_camera, scale: int, library=None) -> rt_camera:
+    """rt_camera_coarsen (include/rt.h): the camera of the frame of
+    ceil(width / scale) x ceil(height / scale) pixels whose pixel covers a
+    scale x scale block of `cam`'s pixels (raytracing.clj:129-135)."""
+    dll = library if library is not None else lib
+    out = rt_camera()
+    code = dll.rt_camera_coarsen(C.byref(cam), int(scale), C.byref(out))
+    if code < 0:
+        raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+    return out
+
+
+def coarse_size(width: int, height: int, scale: int):
+    """(ceil(width / scale), ceil(height / scale)): the frame camera_coarsen's camera draws."""
+    return -(-int(width) // int(scale)), -(-int(height) // int(scale))
+
+
+def _upsample_opts(opts: dict) -> rt_upsample_opts:
+    unknown = set(opts) - set(UPSAMPLE_DEFAULTS)
+    if unknown:
+        raise TypeError(f"upsample: unknown option(s) {sorted(unknown)}")
+    o = {**UPSAMPLE_DEFAULTS, **opts}
+    return rt_upsample_opts(scale=int(o["scale"]), normal_pow2=int(o["normal_pow2"]), sigma_z=float(o["sigma_z"]))
+
+
+def upsample_host(half0, half1, feat_coarse, feat, library=None, **opts):
+    """rt_upsample_host (include/rt.h): guided upsampling on the host, in plain
+    C++ -- the bits upsample_into gives on the device.  half0, half1: float32
+    (ceil(rows / scale), ceil(width / scale), 3), the coarse frame's two
+    estimates (half1 may be None: one image); feat_coarse: float32 of the same
+    extent with 8 channels; feat: float32 (rows, width, 8), the full-size
+    features.  Options: scale, normal_pow2, sigma_z.  Returns (out0, out1),
+    float32 (rows, width, 3) each -- out0 alone when half1 is None."""
+    dll = library if library is not None else lib
+    o = _upsample_opts(opts)
+    half0 = np.ascontiguousarray(half0, np.float32)
+    half1 = None if half1 is None else np.ascontiguousarray(half1, np.float32)
+    feat_coarse = np.ascontiguousarray(feat_coarse, np.float32)
+    feat = np.ascontiguousarray(feat, np.float32)
+    if feat.ndim != 3 or feat.shape[2] != RT_FEAT_CHANNELS:
+        raise ValueError("upsample_host: feat must be (rows, width, 8)")
+    rows, width = feat.shape[:2]
+    cshape = (-(-rows // max(o.scale, 1)), -(-width // max(o.scale, 1)))
+    if half0.shape != cshape + (3,) or (half1 is not None and half1.shape != half0.shape) or \
+            feat_coarse.shape != cshape + (RT_FEAT_CHANNELS,):
+        raise ValueError(f"upsample_host: half0, half1 must be {cshape + (3,)} and feat_coarse {cshape + (8,)}")
+    out0 = np.empty((rows, width, 3), np.float32)
+    out1 = None if half1 is None else np.empty((rows, width, 3), np.float32)
+    code = dll.rt_upsample_host(C.byref(o), fptr(half0), None if half1 is None else fptr(half1), fptr(feat_coarse),
+                                fptr(feat), width, rows, fptr(out0), None if out1 is None else fptr(out1))
+    if code < 0:
+        raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+    return out0 if out1 is None else (out0, out1)
+
+
+def upsample_into(d_half0: int, d_half1, d_feat_coarse: int, d_feat: int, width: int, rows: int, d_out0: int, d_out1,
+                  stream=None, library=None, **opts) -> None:
+    """Enqueue rt_upsample on device addresses (float32 buffers the caller
+    owns, shaped as upsample_host's; d_half1 and d_out1 both None: one image),
+    on `stream` (a HIP stream handle, int; default the NULL stream) of the
+    device that holds d_out0.  `width`, `rows`: the full size."""
+    dll = library if library is not None else lib
+    o = _upsample_opts(opts)
+    code = dll.rt_upsample(C.byref(o), C.c_void_p(d_half0), C.c_void_p(d_half1) if d_half1 else None,
+                           C.c_void_p(d_feat_coarse), C.c_void_p(d_feat), int(width), int(rows), C.c_void_p(d_out0),
+                           C.c_void_p(d_out1) if d_out1 else None, C.c_void_p(stream) if stream else None)
+    if code < 0:
+        raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+
+
+def render_upscaled(scene, cam: rt_camera, width: int, height: int, spp: int = 8, scale: int = 2, max_depth: int = 50,
+                    seed: int = 1, flags: int = 0, library=None, upsample=None, stages: bool = False, **opts):
+    """render_denoised with the colour traced at a render scale, on device 0:
+    the two accumulators (spp / 2 samples per coarse pixel each) and a second
+    Features (spp samples) run on camera_coarsen(cam, scale) at the coarse
+    size; the full-size Features of `cam` (spp samples) guide upsample_into,
+    whose two outputs feed Denoiser.run at full size.  `spp` must be even;
+    `upsample`: a dict of normal_pow2, sigma_z (rt_upsample_opts); further
+    keywords are the denoiser's.  Returns (denoised, mean, feat) as
+    render_denoised does -- mean of the two upsampled halves; with `stages`
+    (denoised, up0, up1, feat, half0, half1, feat_coarse)."""
+    if spp <= 0 or spp % 2:
+        raise ValueError("render_upscaled: spp must be even and positive")
+    uopts = dict(upsample or {}, scale=scale)
+    _upsample_opts(uopts)
+    _denoise_opts(opts)
+    import torch
+    if not torch.cuda.is_available():
+        raise RTError(-5, "render_upscaled: torch sees no GPU (import torch before rtclj)")
+    half = spp // 2
+    sc = scene if isinstance(scene, Scene) else Scene.from_bodies(scene)
+    ccam = camera_coarsen(cam, scale, library=library)
+    cw, ch = coarse_size(width, height, scale)
+    dev = torch.device("cuda", 0)
+    n_px, n_c = width * height, cw * ch
+    d_h = [torch.empty(n_c * 3, dtype=torch.float32, device=dev) for _ in range(2)]
+    d_fc = torch.empty(n_c * RT_FEAT_CHANNELS, dtype=torch.float32, device=dev)
+    d_up = [torch.empty(n_px * 3, dtype=torch.float32, device=dev) for _ in range(2)]
+    d_feat = torch.empty(n_px * RT_FEAT_CHANNELS, dtype=torch.float32, device=dev)
+    d_out = torch.empty(n_px * 3, dtype=torch.float32, device=dev)
+    torch.cuda.synchronize(dev)   # (the passes below run on the NULL stream)
+    with Progressive(sc, ccam, cw, ch, max_depth, seed, flags=flags, library=library) as a0, \
+            Progressive(sc, ccam, cw, ch, max_depth, seed, flags=flags, sample_begin=half, library=library) as a1, \
+            Features(sc, ccam, cw, ch, seed=seed, flags=flags, library=library) as fc, \
+            Features(sc, cam, width, height, seed=seed, flags=flags, library=library) as ft, \
+            Denoiser(width, height, library=library) as dn:
+        a0.add(half)
+        a1.add(half)
+        fc.add(spp)
+        ft.add(spp)
+        a0.resolve_into(d_h[0].data_ptr())
+        a1.resolve_into(d_h[1].data_ptr())
+        fc.resolve_into(d_fc.data_ptr())
+        ft.resolve_into(d_feat.data_ptr())
+        upsample_into(d_h[0].data_ptr(), d_h[1].data_ptr(), d_fc.data_ptr(), d_feat.data_ptr(), width, height,
+                      d_up[0].data_ptr(), d_up[1].data_ptr(), library=library, **uopts)
+        dn.run(d_up[0].data_ptr(), d_up[1].data_ptr(), d_feat.data_ptr(), d_out.data_ptr(), **opts)
+        torch.cuda.synchronize(dev)
+        u0, u1 = (d.cpu().numpy().reshape(height, width, 3) for d in d_up)
+        feat = d_feat.cpu().numpy().reshape(height, width, RT_FEAT_CHANNELS)
+        out = d_out.cpu().numpy().reshape(height, width, 3)
+        if stages:
+            h0, h1 = (d.cpu().numpy().reshape(ch, cw, 3) for d in d_h)
+            return out, u0, u1, feat, h0, h1, d_fc.cpu().numpy().reshape(ch, cw, RT_FEAT_CHANNELS)
+    return out, np.float32(0.5) * (u0 + u1), feat
 
 
 def _temporal_opts(opts: dict) -> rt_temporal_opts:
@@ -1334,7 +1462,7 @@ def _same_but_centres(a: Scene, b: Scene) -> bool:
 
 def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max_depth: int = 50, seed: int = 1,
                      flags: int = 0, library=None, temporal=None, stages: bool = False, refit: bool = False, clamp=None,
-                     budget=None, **opts):
+                     budget=None, scale=None, upsample=None, **opts):
     """render_sequence for bodies that move: one Scene per frame (all with the
     same body count), zipped with `cameras`; a generator that yields float32
     (height, width, 3) per frame, on device 0.  Per frame f: the scene's upload
@@ -1360,7 +1488,21 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
     +inf, which clamps nothing) and Denoiser.run.  Frame 0 has no history and is
     traced at min(target, max_mult) everywhere.  `stages` then yields the
     tiles' multipliers, uint32 (ceil(height / 8), ceil(width / 8)), as an
-    eighth item.  Without `budget` nothing changes."""
+    eighth item.  Without `budget` nothing changes.
+    With `scale` (2..4) the colour is traced at a render scale: the two
+    accumulators and a second rt_feat (spp samples) use camera_coarsen(cam,
+    scale) at the coarse size, and upsample_into (options: `upsample`, a dict of
+    normal_pow2, sigma_z) brings the two resolved halves up to full size between
+    the resolves and the step; the features, ids, motion, step and denoiser stay
+    at full size, and the yielded half0, half1 are the upsampled ones.  `stages`
+    then yields three more items: the coarse half0, half1 and features.  `scale`
+    with `budget` is refused (the budget's tile lists belong to the traced
+    grid).  Without `scale` nothing changes."""
+    if scale is not None and budget is not None:
+        raise ValueError("render_animation: scale and budget cannot be combined")
+    if scale is not None:
+        uopts = dict(upsample or {}, scale=scale)
+        _upsample_opts(uopts)
     if budget is not None:
         bopt = _budget_opts(dict(budget))
         spp = 2 * bopt.half_spp
@@ -1398,8 +1540,16 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
     torch.cuda.synchronize(dev)   # (the passes below run on the NULL stream)
     shape = rt_params(width=width, height=height, row_begin=0, row_end=height, spp=0, max_depth=max_depth, seed=seed,
                       flags=flags)
-    ds, acc, ft = C.c_void_p(), [C.c_void_p(), C.c_void_p()], C.c_void_p()
+    ds, acc, ft, fc = C.c_void_p(), [C.c_void_p(), C.c_void_p()], C.c_void_p(), C.c_void_p()
     prev_sc = first_sc = None
+    traced, d_tr, d_fc = shape, d_h, None   # what the accumulators trace and resolve into
+    if scale is not None:
+        cw, ch = coarse_size(width, height, scale)
+        traced = rt_params(width=cw, height=ch, row_begin=0, row_end=ch, spp=0, max_depth=max_depth, seed=seed,
+                           flags=flags)
+        d_tr = [torch.empty(cw * ch * 3, dtype=torch.float32, device=dev) for _ in range(2)]
+        d_fc = torch.empty(cw * ch * RT_FEAT_CHANNELS, dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
     try:
         with Temporal(width, height, library=library) as tp, Denoiser(width, height, library=library) as dn:
             for f, (scene, cam) in enumerate(zip(scenes, cameras)):
@@ -1418,31 +1568,44 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
                 if f == 0:
                     if budget is None:
                         for a in acc:
-                            ok(dll.rt_accum_create(ds, C.byref(shape), C.byref(a)))
+                            ok(dll.rt_accum_create(ds, C.byref(traced), C.byref(a)))
                     else:
                         bd = Budget(ds, width, height, max_depth=max_depth, seed=seed, flags=flags, library=library,
                                     **dict(budget))
                     ok(dll.rt_feat_create(ds, C.byref(shape), C.byref(ft)))
+                    if scale is not None:
+                        ok(dll.rt_feat_create(ds, C.byref(traced), C.byref(fc)))
                     motion = np.zeros((len(sc), 4), np.float32)
                 else:
                     if budget is None:
                         for a in acc:
                             ok(dll.rt_accum_clear(a, None))
                     ok(dll.rt_feat_clear(ft, None))
+                    if scale is not None:
+                        ok(dll.rt_feat_clear(fc, None))
                     motion = body_motion(sc, prev_sc, library=library)
+                tcam = cam if scale is None else camera_coarsen(cam, scale, library=library)
                 if budget is None:
                     for a, begin, n in ((acc[0], f * spp, half), (acc[1], f * spp + half, half)):
-                        p = rt_params.from_buffer_copy(shape)
+                        p = rt_params.from_buffer_copy(traced)
                         p.spp, p.sample_begin = n, begin
-                        ok(dll.rt_launch_accum(ds, C.byref(cam), C.byref(p), a, None, None))
+                        ok(dll.rt_launch_accum(ds, C.byref(tcam), C.byref(p), a, None, None))
+                if scale is not None:
+                    p = rt_params.from_buffer_copy(traced)
+                    p.spp, p.sample_begin, p.max_depth = spp, f * stride, 1
+                    ok(dll.rt_launch_feat(ds, C.byref(tcam), C.byref(p), fc, None, None))
                 p = rt_params.from_buffer_copy(shape)
                 p.spp, p.sample_begin, p.max_depth = spp, f * stride, 1
                 ok(dll.rt_launch_feat(ds, C.byref(cam), C.byref(p), ft, None, None))
                 ok(dll.rt_launch_ids(ds, C.byref(cam), width, height, 0, C.c_void_p(d_ids.data_ptr()), None))
                 if budget is None:
-                    ok(dll.rt_accum_resolve(acc[0], flags, C.c_void_p(d_h[0].data_ptr()), None))
-                    ok(dll.rt_accum_resolve(acc[1], flags, C.c_void_p(d_h[1].data_ptr()), None))
+                    ok(dll.rt_accum_resolve(acc[0], flags, C.c_void_p(d_tr[0].data_ptr()), None))
+                    ok(dll.rt_accum_resolve(acc[1], flags, C.c_void_p(d_tr[1].data_ptr()), None))
                 ok(dll.rt_feat_resolve(ft, C.c_void_p(d_feat.data_ptr()), None))
+                if scale is not None:
+                    ok(dll.rt_feat_resolve(fc, C.c_void_p(d_fc.data_ptr()), None))
+                    upsample_into(d_tr[0].data_ptr(), d_tr[1].data_ptr(), d_fc.data_ptr(), d_feat.data_ptr(), width,
+                                  height, d_h[0].data_ptr(), d_h[1].data_ptr(), library=library, **uopts)
                 d_motion = torch.from_numpy(motion.reshape(-1)).to(dev)   # (torch's allocations are 256-byte aligned)
                 moved = dict(d_ids=d_ids.data_ptr(), d_motion=d_motion.data_ptr() if len(sc) else None, n_bodies=len(sc))
                 if budget is not None:
@@ -1466,7 +1629,9 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
                     yield (out,) + tuple(d.cpu().numpy().reshape(height, width, 3) for d in d_h) + \
                         (d_feat.cpu().numpy().reshape(height, width, RT_FEAT_CHANNELS),) + \
                         tuple(d.cpu().numpy().reshape(height, width, 3) for d in d_acc) + \
-                        (d_ids.cpu().numpy().reshape(height, width),) + ((bd.mult(),) if bd is not None else ())
+                        (d_ids.cpu().numpy().reshape(height, width),) + ((bd.mult(),) if bd is not None else ()) + \
+                        (() if scale is None else tuple(d.cpu().numpy().reshape(ch, cw, 3) for d in d_tr) +
+                         (d_fc.cpu().numpy().reshape(ch, cw, RT_FEAT_CHANNELS),))
                 else:
                     yield out
     finally:
@@ -1479,6 +1644,8 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
                 dll.rt_accum_free(a)
         if ft:
             dll.rt_feat_free(ft)
+        if fc:
+            dll.rt_feat_free(fc)
 
 
 def pass_sizes(spp: int, passes: int):
@@ -1656,4 +1823,4 @@ if __name__ == "__main__":  # python -m rtclj.raytracing [spp] [depth]
 
 
 __all__ = ["hittables", "REFERENCE_CAMERA", "image_height", "flatten", "flatten64", "Scene", "camera", "render", "Progressive", "Adaptive", "pass_sizes",
-           "Features", "denoise_host", "Denoiser", "render_denoised", "temporal_host", "Temporal", "temporal_probe_host", "budget_plan_host", "Budget", "render_sequence", "ids_host", "body_ids_into", "body_motion", "tree_build_host", "tree_refit_host", "tree_cost", "DeviceScene", "render_animation", "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]
+           "Features", "denoise_host", "Denoiser", "render_denoised", "camera_coarsen", "coarse_size", "upsample_host", "upsample_into", "render_upscaled", "temporal_host", "Temporal", "temporal_probe_host", "budget_plan_host", "Budget", "render_sequence", "ids_host", "body_ids_into", "body_motion", "tree_build_host", "tree_refit_host", "tree_cost", "DeviceScene", "render_animation", "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]
