@@ -1340,7 +1340,10 @@ int rt_quantize_device(const float* d_lin, uint8_t* d_out, size_t n, void* hip_s
  * image per 8 waves); 22 = 16 in a compact LDS image (u8 node-index stack,
  * u32 pixel sums that count their wraps above 255 spp: seven workgroups per
  * CU; 0 selects it wherever spp < 65536, every albedo lies in [-1, 1], the
- * tree has <= 256 nodes and no frame side exceeds 65536, else 16); 24 = 22's
+ * tree has <= 256 nodes and no frame side exceeds 65536, else 16; a path's
+ * camera segment is resolved against a per-tile list of the bodies its
+ * tile's camera rays can reach, not by the traversal); 30 = 22 without that
+ * list (every segment through the traversal); 24 = 22's
  * image in 512-thread workgroups (one per 8 waves; 16 where 22 does not
  * apply); 26 = the same in 1024-thread workgroups (8 waves per SIMD); 12 = BVH
  * with 2 bodies per leaf read from global memory (the fallback for a tree

@@ -244,10 +244,11 @@ static const void* variant_fn(int v) {
     case policy::kGlobal: return RT_K(SRC_SCALAR, SCAN_BVH, false);
     case policy::kFull4: return RT_K(SRC_LDS, SCAN_BVHQ, false);
     case policy::kLeaf8: return RT_KW(SRC_LDS, SCAN_BVHO, false, 8);
-    case policy::kCompact: return RT_K(SRC_LDS, SCAN_BVHQ7, false);
+    case policy::kCompact: return reinterpret_cast<const void*>(&trace_kernel<SRC_LDS, SCAN_BVHQ7, false, 4, 0, false, true>);
     case policy::kCompactW8: return RT_KW(SRC_LDS, SCAN_BVHQ7, false, 8);
     case policy::kCompactW16: return trace_kernel_w16();   // (trace_w16.hip, compiled with its own scheduler flag)
     case policy::kCompactTh4: return RT_KWT(SRC_LDS, SCAN_BVHQ7, false, 4, 4);
+    case policy::kCompactWalk: return RT_K(SRC_LDS, SCAN_BVHQ7, false);
   }
 #ifdef RTCLJ_DIAG
   return diag_kernel(v);

@@ -60,6 +60,7 @@
 #include "bvh_pad.h"
 #include "fp_rn.h"
 #include "rt_internal.h"
+#include "tile_list.h"
 
 namespace rtclj {
 
@@ -477,7 +478,9 @@ __device__ void diag_scan(const struct KArgs& a, const float4* s_geo, float ox, 
 // workgroups = 8 waves per SIMD, where 4-wave workgroups fit 3 per CU)
 // THT: the pool's tile rows (0: tile_rows(SCAN); variant 28 runs 22's
 // compact image on 8 x 4-pixel pools, for launches of few 8 x 8 tiles)
-template <int SRC, int SCAN, bool STATS = false, int NW = 4, int THT = 0, bool SWEEP = false>
+// PRE: camera segments resolved against the tile's list in a prelude of the
+// wave iteration (tile_list.h): variant 22 (30 is 22 without)
+template <int SRC, int SCAN, bool STATS = false, int NW = 4, int THT = 0, bool SWEEP = false, bool PRE = false>
 __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_kernel(const KArgs a) {
   constexpr int NT = 64 * NW;   // threads
   // The sample pool: the workgroup's 8 x 8 pixels x spp samples are the
@@ -785,7 +788,48 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
   if constexpr (kCompactPx) {
     if (threadIdx.x < NPX * 3 / 4) s_carry[threadIdx.x] = 0u;
   }
+  // The tile's list (PRE): the leaf records, big bodies' included, that hold a
+  // body some camera ray of the unit's pixel rectangle can reach
+  // (tile_list.h) -- as their LDS addresses, u16, behind a count word: 32
+  // bytes, all that variant 22's image leaves of a seventh of a CU's LDS (a
+  // copy of the surviving bodies would be 80 bytes per four).  A record is
+  // listed whole: its other bodies are bodies of the scene, and a test more
+  // never changes the closest hit.  More than kTlMax records, or a record
+  // above 64 KB: the count says so, and the tile's camera segments take the walk.
+  constexpr int kTlMax = 14;
+  unsigned* s_tl = nullptr;
+  if constexpr (PRE) {
+    __shared__ unsigned tl_words[8];
+    s_tl = tl_words;
+    if (threadIdx.x == 0) tl_words[0] = 0u;
+  }
   __syncthreads();
+  if constexpr (PRE) {
+    static_assert(SRC == SRC_LDS && is_q(SCAN) && !SWEEP, "the tile list: the 4-body tree's leaf records in LDS");
+    if (npx > 0) {
+      // the rectangle's first and last pixel centres (interleaved row tiles: the
+      // rows between count as the rectangle's)
+      const TileRays tr = tile_rays(a.cam, a.defocus, static_cast<float>(qx0), static_cast<float>(qx0 + vw - 1),
+                                    static_cast<float>(image_row(qy0)), static_cast<float>(image_row(qy0 + vh - 1)));
+      const int n_rec = (a.bvh_off_pidx - a.bvh_off_pairs) >> 6;   // 64 bytes of pairs each
+      const unsigned rec0 = lds_addr(s_geo) + static_cast<unsigned>(a.bvh_off_pairs >> 4) * 16u;
+      for (int i = static_cast<int>(threadIdx.x); i < n_rec; i += NT) {
+        const unsigned ra = rec0 + static_cast<unsigned>(i) * kLeafRecBytes;
+        bool any = false;
+#pragma unroll 1
+        for (unsigned b = 0; b < 4; ++b) {
+          const f4v g = *(LdsF4)(uintptr_t)(ra + 16u * b);
+          any = any || tile_keeps(tr, g.x, g.y, g.z, g.w);
+        }
+        if (any) {
+          const unsigned slot = atomicAdd(&s_tl[0], ra > 0xffffu ? static_cast<unsigned>(kTlMax + 1) : 1u);
+          if (slot < static_cast<unsigned>(kTlMax))
+            reinterpret_cast<unsigned short*>(s_tl + 1)[slot] = static_cast<unsigned short>(ra);
+        }
+      }
+    }
+    __syncthreads();
+  }
   // the wave's batch [wb, we) of pool indices (wave-uniform; empty at first:
   // the lanes start on first + threadIdx.x)
   int wb = 0, we = 0;
@@ -958,8 +1002,11 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
   };
   // one segment of the wave's active lanes' paths, then their refill (with
   // compaction, j's states above; `active` and `fresh` are only the step's and
-  // the other variants')
-  auto iteration = [&]() {
+  // the other variants').  LIST (PRE's prelude, below): the closest hit from
+  // the tile's list instead of the big bodies' leaves and the tree -- for
+  // camera segments only, every other block the same text
+  auto segment = [&](auto list_tag) __attribute__((always_inline)) {
+    constexpr bool LIST = decltype(list_tag)::value;
     bool done = false;
     if constexpr (STATS) st_ts = stamp();
     if constexpr (STATS) {  // counted once per wave event, by its first active lane
@@ -969,6 +1016,14 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
         st_lanes += __popcll(ex);
       }
     }
+    // PRE: the lanes of this segment -- the prelude's are those holding an
+    // unstarted sample, the walk's those holding a sample or a path (a lane
+    // retired by the prelude's refill stays in the wave's loop to the end of
+    // the iteration).  The predicate stands inside the segment, around the
+    // lanes' work only: the refill's wave-level state (the batch [wb, we))
+    // is then changed by every lane alike and stays in scalar registers
+    const bool in = !PRE || (LIST ? j >= 0 : j >= -1);
+    if (in) {
     RT_MARK("iteration");
     if (kCompact ? j >= 0 : fresh) {
       RT_MARK("camera");
@@ -1380,6 +1435,12 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
         hit0 = pad_meets(tn0, tf0, tmin, best_t);
         hit1 = pad_meets(tn1, tf1, tmin, best_t);
       };
+      if constexpr (LIST) {
+        // the tile's list: a wave-uniform loop of leaf passes, no walk
+        RT_MARK("tile_list");
+        const int n_list = min(sgpr(static_cast<int>(s_tl[0])), kTlMax);   // (<= kTlMax here: the prelude's condition)
+        for (int b = 0; b < n_list; ++b) leaf(static_cast<int>(reinterpret_cast<const unsigned short*>(s_tl + 1)[b]));
+      } else {
       // the big bodies' leaves first: every lane, so a wave-uniform loop (their
       // hits, e.g. the ground, then cull the tree)
       RT_MARK("bigleaf");
@@ -1448,6 +1509,7 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
         }
         node = nxt;
       }
+      }   // (!LIST)
       // the ray's origin and unit direction again from the packed copies the
       // walk used (the same values): the scalar ones are dead through it,
       // six VGPRs fewer at its peak
@@ -1672,6 +1734,7 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
         __hip_atomic_fetch_add(acc + 2, static_cast<AccT>(fix24(cb)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
     }
+    }   // (in)
     // refill: the lanes whose paths ended take their next indices
     RT_MARK("refill");
     const uint64_t m = __ballot(done);
@@ -1731,7 +1794,7 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
     }
     if constexpr (STATS) st_c_acc += stamp() - st_ts;
     RT_MARK("compaction");
-    if constexpr (kCompact) {
+    if constexpr (kCompact && !LIST) {
       // spent: out to the compaction step when this wave may post its few
       // paths, or its idle lanes may take posted ones
       // (the limit and the flags from LDS: no registers held for them)
@@ -1748,6 +1811,36 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
             j = -3;   // (out of the loop, the path kept)
         }
       }
+    }
+  };
+  // A wave iteration.  PRE, in a tile with a list: first the prelude -- the
+  // lanes holding a sample not started yet (j >= 0) run its camera segment
+  // against the list, shade it and refill, up to kPreTrips times while some
+  // lane holds one -- so that a lane enters the walk with its second segment,
+  // and a sample that ends at its first (the sky) never does.  The same text
+  // (segment), the same draws in the same order per path: the same bits.
+  // With no live path in the wave after the prelude the iteration ends there
+  // (the lanes then hold unstarted samples, or none: the drain check below
+  // the walk acts only on live paths).
+  // (1, 2 and 4 trips measured on C1 with -DRTCLJ_PRE_TRIPS: DESIGN.md §3.1)
+#ifdef RTCLJ_PRE_TRIPS
+  constexpr int kPreTrips = RTCLJ_PRE_TRIPS;
+#else
+  constexpr int kPreTrips = 2;
+#endif
+  auto iteration = [&]() {
+    if constexpr (PRE) {
+      if (sgpr(static_cast<int>(s_tl[0])) <= kTlMax) {
+#pragma unroll 1
+        for (int trip = 0; trip < kPreTrips; ++trip) {
+          if (__ballot(j >= 0) == 0) break;
+          segment(std::true_type{});
+        }
+        if (__ballot(j == -1) == 0) return;
+      }
+      segment(std::false_type{});
+    } else {
+      segment(std::false_type{});
     }
   };
   for (;;) {

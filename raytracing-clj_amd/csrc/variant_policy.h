@@ -36,6 +36,11 @@ enum { FEAT_LDS = 0, FEAT_GLOBAL = 1, FEAT_SCAN = 2 };   // where a feature laun
 //   28 22 on 8 x 4-pixel pools (whole pools for launches of few 8 x 8 tiles
 //      instead of sample splits: measured slower, selected only explicitly
 //      or by RTCLJ_TH4)
+//      -- camera segments resolved against a per-tile body list in a prelude
+//      of the wave iteration, not by the walk (tile_list.h)
+//   30 22 without the tile list (every segment through the walk: 22 as it was
+//      before the list; selected only explicitly, for A/B and the tests that
+//      hold the list path to the walk bit for bit)
 //   18 BVH in LDS, 8-body leaves (large scenes where 24 does not fit)
 //   12 BVH (2-body leaves) read from global memory: a tree too big for LDS
 //    5 linear scan, grouped, table through the scalar cache: a tree too deep
@@ -56,7 +61,8 @@ enum : int {
   kCompactW8 = 24,    // ... in 8-wave workgroups
   kCompactW16 = 26,   // ... in 16-wave workgroups
   kCompactTh4 = 28,   // ... on 8 x 4-pixel pools
-  kVariants = 30
+  kCompactWalk = 30,  // ... without the per-tile list: camera segments through the walk
+  kVariants = 32
 };
 
 enum { WALK_NONE = 0 /* a body scan */, WALK_BVH = 1, WALK_SORTED = 2 /* sorted_kernel */ };
@@ -118,6 +124,9 @@ constexpr Traits kTraits[kVariants] = {
     // (22 on 8 x 4-pixel pools: whole pools of half the pixels for launches of
     // few 8 x 8 tiles instead of sample splits; measured slower)
     {8, 256, 4, true, false, BUILD_PRODUCT, WALK_BVH, 1, true, 1, 0},     // 28
+    kNone,
+    // (22 without the tile list: camera segments through the walk)
+    {8, 256, 0, true, false, BUILD_PRODUCT, WALK_BVH, 1, true, 1, 0},     // 30
     kNone,
 };
 // does a build (diag: the diagnostic library) carry variant v?

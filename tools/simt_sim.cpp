@@ -21,6 +21,17 @@
 //          to back in one traversal loop, then all shaded (round 6)
 //   DEFER=1 (with any policy): a visit's second leaf pushed and tested as a
 //          leaf-only step next (one leaf pass per step); CNODE overrides C_NODE
+//   PRE=T  (with the wave policy; round 19): up to T prelude
+//          trips at the head of a wave iteration, in which the lanes holding
+//          an unstarted sample resolve its camera segment against the tile's
+//          body list, shade it and refill; a lane enters the walk with its
+//          second segment, and with no live path in the wave the iteration
+//          ends after the prelude.  The list is csrc/tile_list.h's own cull
+//          of the scene for the tile, its length times INFL (default 1; the
+//          kernel lists whole leaf records: 4 bodies a pass either way).  A
+//          trip costs CPRE (default 330, close to the whole outer block) plus
+//          the list's leaf passes and the exact passes of the trip's busiest
+//          lane (its camera segment's candidates as the walk met them).
 //
 //   g++ -O2 -std=c++17 -I include tools/simt_sim.cpp raytracing-clj_amd/csrc/bvh.cpp \
 //       -Lraytracing-clj_amd/lib -lrtclj -Wl,-rpath,$PWD/raytracing-clj_amd/lib -o /tmp/simt_sim
@@ -36,6 +47,7 @@
 #include "../include/rt.h"
 #include "../raytracing-clj_amd/csrc/bvh.h"
 #include "../raytracing-clj_amd/csrc/bvh_pad.h"
+#include "../raytracing-clj_amd/csrc/tile_list.h"
 
 using namespace rtclj;
 namespace rtclj { extern float g_bvh_big_ratio; }
@@ -54,6 +66,9 @@ static double C_BALL = 27, C_DISK = 21;   // one rejection-loop trip (random-uni
 static int g_restart_k = 32;
 static int g_pair = 2;   // policy 3: paths per lane   // policy 2: shade once this many lanes finished traversal
 static int g_charge_rej = 0;   // policies 0/1: add the rejection trips to the cost (RJ=1)
+static int g_pre = 0;          // PRE=T: prelude trips per wave iteration (0: none)
+static double g_infl = 1.0, C_PRE = 330;   // INFL, CPRE
+static double g_pre_trips = 0, g_pre_lanes = 0, g_list_len = 0, g_list_tiles = 0, g_list_max = 0;
 
 // VALU wave-instructions per block (from the ISA of the default kernel,
 // trace_kernel<1, 5, -3, false>); leaf and exact costs for NP body pairs per leaf
@@ -569,6 +584,22 @@ static void run_tile(const Ctx& C, int tx, int ty, int policy, int key_mode, Res
     return;
   }
   if (policy == 0) {
+    // the tile's list (PRE): tile_list.h's cull of every body
+    int list_passes = 0;
+    if (g_pre) {
+      const float* cam = C.cam.center;   // center, p00, du, dv, disk_u, disk_v: contiguous
+      const TileRays tr = tile_rays(cam, C.cam.defocus, float(tx * 8), float(tx * 8 + 7), float(ty * g_tile_h),
+                                    float(ty * g_tile_h + g_tile_h - 1));
+      int nb = 0;
+      for (int b = 0; b < C.S->n; ++b) {
+        const float* sp = &C.S->sph[4 * b];
+        nb += tile_keeps(tr, sp[0], sp[1], sp[2], -(sp[3] * sp[3]));
+      }
+      list_passes = int(std::ceil(nb * g_infl / 4.0));
+      g_list_len += nb;
+      g_list_tiles += 1;
+      g_list_max = std::max(g_list_max, double(nb));
+    }
     // 4 independent waves, advanced in order of accumulated cost
     std::vector<double> wc(g_nw, 0.0);
     for (;;) {
@@ -582,6 +613,39 @@ static void run_tile(const Ctx& C, int tx, int ty, int policy, int key_mode, Res
       std::vector<Trav> tr(64);
       std::vector<const Trav*> act;
       std::vector<int> done;
+      if (g_pre) {   // the prelude: camera segments against the list, shaded, refilled
+        bool live = false;
+        for (int trip = 0; trip < g_pre; ++trip) {
+          int n_in = 0, max_c = 0;
+          for (int l = 0; l < 64; ++l) {
+            Path& p = lanes[64 * w + l];
+            if (p.j < 0 || !p.fresh) continue;
+            int px, py;
+            pixel(p.j, px, py);
+            Trav t;
+            const bool ended = step(C, p, px, py, t);
+            int nc = __builtin_popcount(t.big_c);
+            for (size_t i = 0; i < t.leaves.size(); ++i) nc += __builtin_popcount(t.c1[i]) + __builtin_popcount(t.c2[i]);
+            max_c = std::max(max_c, nc);
+            ++n_in;
+            if (ended) {
+              p = Path{};
+              p.j = next < pool ? next++ : -1;
+            }
+          }
+          if (!n_in) break;
+          const double c = C_PRE + C_LEAF * list_passes + C_EXACT * max_c;
+          wc[w] += c;
+          R.cost += c;
+          g_pre_trips += 1;
+          g_pre_lanes += n_in;
+        }
+        for (int l = 0; l < 64; ++l) live |= lanes[64 * w + l].j >= 0 && !lanes[64 * w + l].fresh;
+        if (!live) {   // no live path: the iteration ends after the prelude
+          R.iters += 1;
+          continue;
+        }
+      }
       if (g_qt == 2) {   // probe pass on copies: the wave's common start node
         int ref[2] = {-1, -1};
         unsigned xo = 0;
@@ -780,6 +844,9 @@ int main(int argc, char** argv) {
   if (std::getenv("PAIR")) g_pair = std::atoi(std::getenv("PAIR"));
   if (std::getenv("RJ")) g_charge_rej = std::atoi(std::getenv("RJ"));
   if (std::getenv("RK")) g_restart_k = std::atoi(std::getenv("RK"));
+  if (std::getenv("PRE")) g_pre = std::atoi(std::getenv("PRE"));
+  if (std::getenv("INFL")) g_infl = std::atof(std::getenv("INFL"));
+  if (std::getenv("CPRE")) C_PRE = std::atof(std::getenv("CPRE"));
   const int v0 = std::getenv("V0") ? std::atoi(std::getenv("V0")) : 0;
   const int nv = std::getenv("NV") ? std::atoi(std::getenv("NV")) : 4;
   for (int v = v0; v < nv; ++v) {
@@ -798,6 +865,10 @@ int main(int argc, char** argv) {
     std::printf("  candidates rejected by the t bound: %.3f of %.0f; per segment: %.2f node visits, %.2f leaves\n",
                 g_rej / g_cand, g_cand, g_visits / g_segs, g_leafs / g_segs);
     g_rej = g_cand = g_segs = g_visits = g_leafs = 0;
+    if (g_pre && pol[v] == 0)
+      std::printf("  prelude: %.3f trips per wave-iter, %.1f lanes a trip; list %.2f bodies a tile, %.0f at most\n",
+                  g_pre_trips / R.iters, g_pre_lanes / std::max(g_pre_trips, 1.0), g_list_len / std::max(g_list_tiles, 1.0),
+                  g_list_max);
     std::printf("%-22s cost/sample %8.1f  wave-iters/sample %.3f  trav steps/wave-iter %.2f  lane eff %.3f\n",
                 names[v], R.cost / R.samples, R.iters / R.samples * 64, R.steps / R.iters,
                 R.lane_steps / (R.steps * 64));

@@ -70,7 +70,9 @@ int main(int argc, char** argv) {
     ds.unit_albedo = q[11] != 0;
     const Frame p{static_cast<int>(q[12]), static_cast<int>(q[13]), static_cast<int>(q[14]), static_cast<int>(q[15])};
     const int ratio = static_cast<int>(q[16]), slots = static_cast<int>(q[17]);
-    for (int sel = 0; sel < kVariants; ++sel) {
+    // (the selectors the file records, 0..29: variant 30, 22 without the tile
+    // list, is explicit only and launches as 22 does -- tests/test_gpu_tile_list.py)
+    for (int sel = 0; sel < 30; ++sel) {
       if (!has_variant(sel, diag)) {
         std::printf("%zu %d -1 -1 -1 -1 -1 -1 -1 -1\n", g, sel);
         continue;
