@@ -570,8 +570,9 @@ int64_t rt_feat_samples(const rt_feat* f);
  * linear scan; 12: the BVH in global memory; otherwise the BVH in LDS where it
  * fits): the contents never depend on it.  The stream's tile-cost record
  * (rt_set_schedule) is neither read nor written.  RT_E_ARG when p's width,
- * height or row selection differ from f's, when ds is on another device, or
- * when the count would pass 2^32 - 1; f is unchanged then. */
+ * height or row selection differ from f's, when ds is on another device, when
+ * the count would pass 2^32 - 1, or when f holds specular-chain passes
+ * (rt_launch_feat_chain, below); f is unchanged then. */
 int rt_launch_feat(const rt_dscene* ds, const rt_camera* c, const rt_params* p, rt_feat* f,
                    uint64_t* d_counters, void* hip_stream);
 /* compute-pixel's accum / spp for the features (raytracing.clj:155).
@@ -605,6 +606,108 @@ int rt_feat_resolve_host(const int64_t* sums, const uint32_t* hits, const float*
  * per CU, VGPRs per lane, LDS bytes per workgroup, the bodies' source: 0 = BVH
  * in LDS, 1 = BVH in global memory, 2 = linear scan}. */
 int rt_feat_occupancy(const rt_dscene* ds, int* out4);
+
+/* ---- specular-chain features: guides for what glass and mirrors show ------------
+ * rt_launch_feat stops at the first surface: on a mirror or on glass every
+ * pixel then has one albedo and a smooth normal and depth, and a denoiser or an
+ * upsampler guided by them treats the reflected or refracted scene as paint on
+ * that surface.  A chain pass follows the deterministic part of ray-color's
+ * recursion (raytracing.clj:45-58) from the same camera ray to the first rough
+ * surface, or to the sky, and takes the features there.  It adds to an rt_feat
+ * in rt_launch_feat's units, so rt_feat_resolve, _read, _add, _resolve_host,
+ * rt_denoise and rt_upsample take its result as they take the first-hit one.
+ *
+ * Per sample, in fp32, every fma written out (the trace kernel's operations;
+ * sqrt and 1/x correctly rounded): the ray (o, d) is rt_launch_feat's camera
+ * ray; thr = (1, 1, 1), L = 0, last = -1 (no body), b = 0.  Then, repeated:
+ *   1. u = d * (1 / |d|), t-min = 1e-3 in |d| units (raytracing.clj:48).
+ *   2. The closest hit as rt_launch_ids' step 2 finds it, with the trace
+ *      kernel's self-hit guard: for the body `last` the root is taken with |h|
+ *      in place of sqrt(disc) (the origin lies on that body: exact arithmetic
+ *      has cc = 0).  With last = -1 this is rt_launch_feat's search bit for bit.
+ *   3. No hit: albedo_c = thr_c * sky_c (raytracing.clj:55-58, from u), normal
+ *      0, not a hit, no depth.  The chain ends.
+ *   4. A hit at t: L = L + t.  P = o + t u, n = (P - C) * (1 / r), turned
+ *      against d (hittable.clj:24-31, hit.clj:14-15).  The body is smooth iff it
+ *      is RT_DIELECTRIC, or RT_METAL with fuzz <= fuzz_max (a NaN fuzz is not).
+ *   5. Smooth, and b < max_bounces:
+ *      metal (material.clj:21-28 with the fuzz term dropped: no random vector
+ *        is drawn; at fuzz 0 this is the reference's direction exactly):
+ *        rdir = d - 2 dot(d, n) n on the un-normalised d.  Unless
+ *        dot(rdir, n) > 0 the chain ends here as in 6; else thr_c *= albedo_c,
+ *        d = rdir.
+ *      dielectric (realm/raytracing.clj:158-177, the branch RT_FLAG_REALM runs:
+ *        no Schlick term, no draw): ri = 1 / index on a front face, the index on
+ *        a back face; cos = min(-dot(u, n), 1), sin = sqrt(1 - cos^2); total
+ *        internal reflection of u iff not (ri * sin <= 1), else vec3a.clj:97-101's
+ *        refraction.  thr is unchanged.
+ *      Then o = P, last = the body, b = b + 1, and back to 1.
+ *   6. Otherwise the chain ends on this surface: albedo_c = thr_c * att_c with
+ *      rt_launch_feat's ::attenuation (the body's rgb, 1 for glass, 0 for
+ *      RT_NONE), the normal n scaled by one correctly rounded 1 / |n|, a hit,
+ *      depth = L.
+ * Accumulated as rt_launch_feat accumulates: the six sums, the hit count, the
+ * minimum of L over the hit samples.
+ *
+ * Two properties (tests/test_chain_host.py, tests/test_gpu_chain.py):
+ *  - with max_bounces = 0, or on a scene without smooth bodies, every sample is
+ *    rt_launch_feat's bit for bit (1 * x, 0 + t and the unguarded test are exact);
+ *  - on a scene of smooth bodies only the chain is the path rt_launch traces
+ *    under RT_FLAG_REALM: the same segments, the same bits.
+ *
+ * What a user must know:
+ *  - Depth is a VIRTUAL distance: camera to the rough surface along the bends,
+ *    the minimum over the pixel's hit samples.  It is no distance from the
+ *    camera to anything, and a reprojection through it is wrong: chain features
+ *    must never be given to rt_temporal_step* or rt_temporal_probe.  A sequence
+ *    keeps a first-hit rt_feat for those and a chain rt_feat for rt_denoise and
+ *    rt_upsample.
+ *  - The normal is the last surface's in world space.  It is not mirrored into
+ *    the reflecting surface's frame.
+ *  - Glass takes the refraction branch only, as under RT_FLAG_REALM.  The glass's
+ *    own faint reflection, which the default namespace draws by Schlick's
+ *    reflectance (material.clj:30-46), is not followed: the guides describe what
+ *    is seen through the glass, and the reflection on it is filtered as before.
+ *  - Metal with fuzz above fuzz_max is rough: the chain ends on it with its own
+ *    albedo.  Metal at or below it is followed as a perfect mirror.
+ *  - Coverage is the share of samples whose chain ended on a surface.
+ *  - A chain that runs out of bounces ends on the smooth surface it is on.
+ *
+ * NULL options: {8, 0.0f}.  max_bounces 0 .. 64, fuzz_max finite and >= 0, else
+ * RT_E_ARG. */
+typedef struct rt_feat_chain_opts {
+  int max_bounces;   /* smooth surfaces passed per sample, at most             */
+  float fuzz_max;    /* metal with fuzz <= this is followed as a mirror        */
+} rt_feat_chain_opts;
+/* One chain pass (raytracing.clj:45-58, :33-43, :144-151, hittable.clj:7-31,
+ * material.clj:13-46, realm/raytracing.clj:158-177) added to f exactly as
+ * rt_launch_feat adds one: the same checks, row selections, samplers, streams
+ * and selector; RT_FLAG_REALM and RT_FLAG_STREAMED are accepted and inert.
+ * d_counters: NULL or device u64[2] += {segments traced, samples traced}.
+ * An rt_feat remembers which kind of pass it holds since its last clear: a
+ * chain pass into one that holds first-hit passes, rt_launch_feat into one that
+ * holds chain passes, or a chain pass with other options than the ones it
+ * holds, is RT_E_ARG with f unchanged.  rt_feat_clear lifts the kind,
+ * rt_feat_add keeps it.  All argument errors are returned before anything is
+ * enqueued. */
+int rt_launch_feat_chain(const rt_dscene* ds, const rt_camera* c, const rt_params* p, const rt_feat_chain_opts* opts,
+                         rt_feat* f, uint64_t* d_counters, void* hip_stream);
+/* The chain of one ray on the host, in plain C++ (no device; the same text the
+ * kernel runs, over raytracing.clj:33-43's scan in array order): rays = n x
+ * (o, d) float32, e.g. a camera's samples; out[i] = the body the chain ended on
+ * (-1: the sky), the bounces taken, L (+inf on the sky), and the albedo and
+ * normal floats before their conversion to 2^-24 units.  The yardstick of the
+ * kernel.  RT_E_MATERIAL on an unknown material kind. */
+typedef struct rt_chain_sample {
+  int32_t body, bounces;
+  float length, albedo[3], normal[3];
+} rt_chain_sample;
+int rt_feat_chain_host(const rt_scene* s, const rt_feat_chain_opts* opts, const float* rays, size_t n,
+                       rt_chain_sample* out);
+/* The chain kernel a launch on ds would run under the current selector
+ * (diagnostic; raytracing.clj:33-43's scan as it is run): out4 as
+ * rt_feat_occupancy's. */
+int rt_feat_chain_occupancy(const rt_dscene* ds, int* out4);
 
 /* ---- body ids: which body a pixel shows -----------------------------------------
  * The index hit-anything's reduce (raytracing.clj:33-43) ends on, per pixel,

@@ -92,13 +92,19 @@ RT_FH_FN FhBest fh_none() { return FhBest{INFINITY, -1}; }
 // min(disc, max(h, -c)) >= 0: what it drops has no root above t-min.  A root
 // of +inf (a body whose r * r overflows) is no hit: t < best.t fails against
 // "none yet" and -1 is below every index.
-RT_FH_FN void fh_test(const FhRay& r, float cx, float cy, float cz, float nr2, int s, FhBest& b) {
+// GUARD (spec_chain.h): the body the ray is leaving, `last`, takes sq = |h| for
+// sqrt(disc), trace_kernel.h's self-hit guard (`consider`); without it, the
+// default, `last` is not read and the code is what it was.
+template <bool GUARD = false>
+RT_FH_FN void fh_test(const FhRay& r, float cx, float cy, float cz, float nr2, int s, FhBest& b, int last = -1) {
   const float ocx = cx - r.ox, ocy = cy - r.oy, ocz = cz - r.oz;
   const float h = fmaf(r.uz, ocz, fmaf(r.uy, ocy, r.ux * ocx));
   const float c = fmaf(ocx, ocx, fmaf(ocz, ocz, fmaf(ocy, ocy, nr2)));
   const float disc = fmaf(h, h, -c);
   if (!(fminf(disc, fmaxf(h, -c)) >= 0.0f)) return;
-  const float sq = fh_sqrt(disc);
+  float sq;
+  if constexpr (GUARD) sq = s == last ? fabsf(h) : fh_sqrt(disc);
+  else sq = fh_sqrt(disc);
   const float tn = h - sq;
   const float t = tn > r.tmin ? tn : h + sq;
   const bool acc = (t > r.tmin) & ((t < b.t) | ((t == b.t) & (s < b.body)));
@@ -116,8 +122,9 @@ RT_FH_FN void fh_geo(const float* sphere4, float* geo4) {
 }
 
 // the linear scan: geo = n x (cx, cy, cz, -r^2), in array order
-RT_FH_FN void fh_scan(const FhRay& r, const float* geo, int n, FhBest& b) {
-  for (int s = 0; s < n; ++s) fh_test(r, geo[4 * s], geo[4 * s + 1], geo[4 * s + 2], geo[4 * s + 3], s, b);
+template <bool GUARD = false>
+RT_FH_FN void fh_scan(const FhRay& r, const float* geo, int n, FhBest& b, int last = -1) {
+  for (int s = 0; s < n; ++s) fh_test<GUARD>(r, geo[4 * s], geo[4 * s + 1], geo[4 * s + 2], geo[4 * s + 3], s, b, last);
 }
 
 // A tree as the walk reads it: `base` = the blob nodes | pairs | pidx
@@ -135,12 +142,13 @@ struct FhTree {
 };
 
 // a leaf: its pairs' bodies, each by fh_test (a pad has -r^2 = +inf: disc = -inf)
-RT_FH_FN void fh_leaf(const FhRay& r, const FhTree& t, int p, FhBest& b) {
+template <bool GUARD = false>
+RT_FH_FN void fh_leaf(const FhRay& r, const FhTree& t, int p, FhBest& b, int last = -1) {
   const float* g = reinterpret_cast<const float*>(t.base + t.off_pairs) + 8 * static_cast<size_t>(p);
   const int* id = reinterpret_cast<const int*>(t.base + t.off_pidx) + 2 * static_cast<size_t>(p);
   for (int q = 0; q < t.leaf_pairs; ++q, g += 8, id += 2) {
-    fh_test(r, g[0], g[2], g[4], g[6], id[0], b);
-    fh_test(r, g[1], g[3], g[5], g[7], id[1], b);
+    fh_test<GUARD>(r, g[0], g[2], g[4], g[6], id[0], b, last);
+    fh_test<GUARD>(r, g[1], g[3], g[5], g[7], id[1], b, last);
   }
 }
 
@@ -150,10 +158,10 @@ RT_FH_FN void fh_leaf(const FhRay& r, const FhTree& t, int p, FhBest& b) {
 // every padded box on its path (bvh_pad.h), a box is skipped only if its
 // padded interval misses (t-min, best], and the acceptance is the scan's in
 // any order: the result is fh_scan's, bit for bit.
-template <class Stack>
-RT_FH_FN void fh_walk(const FhRay& r, const FhTree& t, Stack& st, FhBest& b) {
+template <bool GUARD = false, class Stack>
+RT_FH_FN void fh_walk(const FhRay& r, const FhTree& t, Stack& st, FhBest& b, int last = -1) {
   // 1) the big bodies, kept out of the tree (bvh.cpp): their hits cull the tree
-  for (int k = 0; k < t.n_big_leaves; ++k) fh_leaf(r, t, t.big_pair0 + k * t.leaf_pairs, b);
+  for (int k = 0; k < t.n_big_leaves; ++k) fh_leaf<GUARD>(r, t, t.big_pair0 + k * t.leaf_pairs, b, last);
   // 2) the tree, nearer child first
   const float ex = r.ox - t.c[0], ey = r.oy - t.c[1], ez = r.oz - t.c[2];
   const PadRay pr = pad_ray(ex, ey, ez, r.ux, r.uy, r.uz, t.r, t.c0);
@@ -172,8 +180,8 @@ RT_FH_FN void fh_walk(const FhRay& r, const FhTree& t, Stack& st, FhBest& b) {
     pad_interval(ax, ay, az, px[0], px[2], py[0], py[2], pz[0], pz[2], tn0, tf0);
     pad_interval(ax, ay, az, px[1], px[3], py[1], py[3], pz[1], pz[3], tn1, tf1);
     const bool hit0 = pad_meets(tn0, tf0, r.tmin, b.t), hit1 = pad_meets(tn1, tf1, r.tmin, b.t);
-    if (hit0 && c0 < 0) fh_leaf(r, t, ~c0, b);
-    if (hit1 && c1 < 0) fh_leaf(r, t, ~c1, b);
+    if (hit0 && c0 < 0) fh_leaf<GUARD>(r, t, ~c0, b, last);
+    if (hit1 && c1 < 0) fh_leaf<GUARD>(r, t, ~c1, b, last);
     const bool i0 = hit0 && c0 >= 0, i1 = hit1 && c1 >= 0;
     const unsigned n0 = static_cast<unsigned>(c0) * static_cast<unsigned>(t.ref_mul),
                    n1 = static_cast<unsigned>(c1) * static_cast<unsigned>(t.ref_mul);

@@ -1,12 +1,16 @@
 // first_hit.hip — the passes that stop at a camera ray's first hit: the feature
 // buffers (rt_feat, rt_launch_feat; first_hit.h's feat_kernel) and the body-id
-// pass (rt_launch_ids; body_ids.h's ids_kernel), with their occupancy entries.
-// Both follow the trace unit's selector (dscene.h).  DESIGN.md §3.7, §3.10.
+// pass (rt_launch_ids; body_ids.h's ids_kernel), with their occupancy entries;
+// and the pass into the same buffers that goes on through mirrors and glass
+// (rt_launch_feat_chain; spec_chain.h's chain_kernel).  All follow the trace
+// unit's selector (dscene.h).  DESIGN.md §3.7, §3.10, §3.15.
 #include "trace_kernel.h"
 #define RT_FIRST_HIT_KERNEL
 #include "first_hit.h"
 #define RT_BODY_IDS_KERNEL
 #include "body_ids.h"
+#define RT_SPEC_CHAIN_KERNEL
+#include "spec_chain.h"
 #include "dscene.h"
 
 using namespace rtclj;
@@ -25,6 +29,10 @@ struct rt_feat : FrameBuf {
   DevBuf<unsigned long long> sums;   // n_px x 6
   DevBuf<unsigned> hits;             // n_px
   DevBuf<unsigned> depth;            // n_px, float bits (+inf: no hit yet)
+  // the kind of pass held since the last clear (rt_launch_feat_chain, rt.h)
+  enum { NONE = 0, FIRST_HIT = 1, CHAIN = 2 };
+  int kind = NONE;
+  rt_feat_chain_opts chain{};        // kind == CHAIN: its options
 };
 
 // the feature kernel for a source of bodies (policy::feat_source)
@@ -33,6 +41,9 @@ static const void* feat_fn(int src) {
          : src == FEAT_GLOBAL ? reinterpret_cast<const void*>(&feat_kernel<FEAT_GLOBAL>)
                               : reinterpret_cast<const void*>(&feat_kernel<FEAT_SCAN>);
 }
+
+static FeatArgs feat_args(const rt_dscene& dsr, const rt_camera& cr, const rt_params& pr, const rt_feat& fr, int rows,
+                          uint64_t* d_counters);
 
 static hipError_t feat_reset(rt_feat* f, hipStream_t stream) {
   hipError_t e = fill_zero(f->sums, f->n_px * 6, stream);
@@ -66,6 +77,7 @@ extern "C" int rt_feat_clear(rt_feat* f, void* hip_stream) {
   HIP_TRY(hipSetDevice(f->device));
   HIP_TRY(feat_reset(f, static_cast<hipStream_t>(hip_stream)));
   f->samples = 0;
+  f->kind = rt_feat::NONE;
   return RT_OK;
 }
 
@@ -78,11 +90,80 @@ extern "C" int rt_launch_feat(const rt_dscene* ds, const rt_camera* c, const rt_
   if (const int rc = check_frame_args("rt_launch_feat", *p)) return rc;
   std::lock_guard<std::mutex> lk(f->mu);
   if (const int rc = check_pass("rt_launch_feat", "the feature buffers", *f, *ds, *p)) return rc;
+  if (f->kind == rt_feat::CHAIN)
+    return set_error(RT_E_ARG, "rt_launch_feat: the feature buffers hold chain passes (rt_feat_clear first)");
   if (p->spp == 0) return RT_OK;
   const int rows = rows_out(*p);
   HIP_TRY(hipSetDevice(ds->device));
   const policy::Scene si = scene_info(*ds);
   const int src = policy::feat_source(si, selected_variant(), diag_build());
+  FeatArgs a = feat_args(*ds, *c, *p, *f, rows, d_counters);
+  const int gy = (rows + kTile - 1) / kTile;
+  HIP_TRY(enqueue(feat_fn(src), dim3(static_cast<unsigned>(a.tiles_x * gy)), dim3(kFeatThreads), policy::feat_lds(si, src),
+                  static_cast<hipStream_t>(hip_stream), a));
+  f->samples += p->spp;
+  f->kind = rt_feat::FIRST_HIT;
+  return RT_OK;
+}
+
+// ---- specular-chain features (rt.h, spec_chain.h) ------------------------------
+static const void* chain_fn(int src) {
+  return src == FEAT_LDS      ? reinterpret_cast<const void*>(&chain_kernel<FEAT_LDS>)
+         : src == FEAT_GLOBAL ? reinterpret_cast<const void*>(&chain_kernel<FEAT_GLOBAL>)
+                              : reinterpret_cast<const void*>(&chain_kernel<FEAT_SCAN>);
+}
+
+extern "C" int rt_launch_feat_chain(const rt_dscene* ds, const rt_camera* c, const rt_params* p,
+                                    const rt_feat_chain_opts* opts, rt_feat* f, uint64_t* d_counters, void* hip_stream) {
+  clear_error();
+  if (!ds || !c || !p || !f) return set_error(RT_E_ARG, "rt_launch_feat_chain: NULL argument");
+  if (const int rc = check_frame_args("rt_launch_feat_chain", *p)) return rc;
+  rt_feat_chain_opts o;
+  if (const char* why = chain_opts_resolve(opts, &o)) return set_error(RT_E_ARG, std::string("rt_launch_feat_chain: ") + why);
+  std::lock_guard<std::mutex> lk(f->mu);
+  if (const int rc = check_pass("rt_launch_feat_chain", "the feature buffers", *f, *ds, *p)) return rc;
+  if (f->kind == rt_feat::FIRST_HIT)
+    return set_error(RT_E_ARG, "rt_launch_feat_chain: the feature buffers hold first-hit passes (rt_feat_clear first)");
+  if (f->kind == rt_feat::CHAIN && (f->chain.max_bounces != o.max_bounces || f->chain.fuzz_max != o.fuzz_max))
+    return set_error(RT_E_ARG, "rt_launch_feat_chain: the feature buffers hold chain passes of other options");
+  if (p->spp == 0) return RT_OK;
+  const int rows = rows_out(*p);
+  HIP_TRY(hipSetDevice(ds->device));
+  const policy::Scene si = scene_info(*ds);
+  const int src = policy::feat_source(si, selected_variant(), diag_build());
+  ChainArgs a{};
+  a.f = feat_args(*ds, *c, *p, *f, rows, d_counters);
+  a.max_bounces = o.max_bounces;
+  a.fuzz_max = o.fuzz_max;
+  const int gy = (rows + kTile - 1) / kTile;
+  HIP_TRY(enqueue(chain_fn(src), dim3(static_cast<unsigned>(a.f.tiles_x * gy)), dim3(kFeatThreads),
+                  policy::feat_lds(si, src), static_cast<hipStream_t>(hip_stream), a));
+  f->samples += p->spp;
+  f->kind = rt_feat::CHAIN;
+  f->chain = o;
+  return RT_OK;
+}
+
+// The chain kernel a launch on ds would run under the current selector
+// (diagnostic, tools/chain_time.py): out4 as rt_feat_occupancy's.
+extern "C" int rt_feat_chain_occupancy(const rt_dscene* ds, int* out4) {
+  clear_error();
+  if (!ds || !out4) return set_error(RT_E_ARG, "rt_feat_chain_occupancy: NULL argument");
+  HIP_TRY(hipSetDevice(ds->device));
+  const policy::Scene si = scene_info(*ds);
+  const int src = policy::feat_source(si, selected_variant(), diag_build());
+  if (const int rc = occupancy_report(chain_fn(src), kFeatThreads, policy::feat_lds(si, src), out4)) return rc;
+  out4[3] = src;
+  return RT_OK;
+}
+
+// a pass's kernel arguments (feat_kernel's, and chain_kernel's first part)
+static FeatArgs feat_args(const rt_dscene& dsr, const rt_camera& cr, const rt_params& pr, const rt_feat& fr, int rows,
+                          uint64_t* d_counters) {
+  const rt_dscene* ds = &dsr;
+  const rt_camera* c = &cr;
+  const rt_params* p = &pr;
+  const rt_feat* f = &fr;
   const DTree& tr = ds->tree[1];
   FeatArgs a{};
   a.geo = ds->geo;
@@ -107,11 +188,7 @@ extern "C" int rt_launch_feat(const rt_dscene* ds, const rt_camera* c, const rt_
   a.hits = f->hits.p;
   a.depth = f->depth.p;
   a.counters = reinterpret_cast<unsigned long long*>(d_counters);
-  const int gy = (rows + kTile - 1) / kTile;
-  HIP_TRY(enqueue(feat_fn(src), dim3(static_cast<unsigned>(a.tiles_x * gy)), dim3(kFeatThreads), policy::feat_lds(si, src),
-                  static_cast<hipStream_t>(hip_stream), a));
-  f->samples += p->spp;
-  return RT_OK;
+  return a;
 }
 
 extern "C" int rt_feat_resolve(const rt_feat* f, float* d_out, void* hip_stream) {

@@ -35,6 +35,7 @@
 #include "denoise.h"
 #include "first_hit.h"
 #include "rt_internal.h"
+#include "spec_chain.h"
 #include "temporal.h"
 #include "budget.h"
 #include "upsample.h"
@@ -417,6 +418,16 @@ extern "C" int rt_ids_host(const rt_scene* s, const rt_camera* c, int width, int
   const char* why = nullptr;
   const int rc = ids_host_pass(s, c, width, rows, row0, out, &why);
   return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_ids_host: ") + (why ? why : "failed"));
+}
+
+// rt_launch_feat_chain's samples on the host (spec_chain.h's chain_host_pass:
+// the text chain_kernel runs, over first_hit.h's scan)
+extern "C" int rt_feat_chain_host(const rt_scene* s, const rt_feat_chain_opts* opts, const float* rays, size_t n,
+                                  rt_chain_sample* out) {
+  clear_error();
+  const char* why = nullptr;
+  const int rc = chain_host_pass(s, opts, rays, n, out, &why);
+  return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_feat_chain_host: ") + (why ? why : "failed"));
 }
 
 // the bodies' displacement between two scenes (body_ids.h's body_motion)

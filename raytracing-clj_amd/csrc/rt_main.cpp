@@ -16,7 +16,7 @@
 //           [--seed S] [--gpus N] [--out PATH] [--png PATH] [--no-png] [--json]
 //           [--host-quantize] [--rejection-samplers] [--passes K]
 //           [--adaptive TOLQ16 [--step S] [--min-spp A] [--max-spp B]]
-//           [--features STEM] [--denoise STEM [--scale N]]
+//           [--features STEM] [--denoise STEM [--scale N] [--chain K]]
 // Defaults follow the reference: spp 100, depth 50, width 400, 16:9.
 // --passes K: the spp in K near-equal accumulating passes on device 0
 // (rt_launch_accum into an rt_accum, the sums read back, rt_resolve_sums and
@@ -44,6 +44,10 @@
 // spp samples per coarse pixel; rt_upsample (default options but the scale)
 // brings the halves up to the frame's size through the frame's own features
 // before rt_denoise.  Without --denoise, or outside 2..4: exit status 2.
+// --chain K (0..64, with --denoise): the feature passes are specular-chain
+// passes of at most K bounces (rt_launch_feat_chain, fuzz_max 0): the filter and
+// --scale's upsampling are guided by what mirrors and glass show.  Without
+// --denoise, or outside 0..64: exit status 2.
 // --json: one more line, a JSON object of where this one-frame process's time
 // went (the device start-up -- the HIP runtime's first rt_device_count, then
 // rt_prepare's context / code object / queue / pageable staging -- on a thread
@@ -70,6 +74,8 @@ int main(int argc, char** argv) {
   int ad_step = 10, ad_min = 0, ad_max = 0;
   int scale = 0;   // --scale: the render scale of --denoise's frame (0: off)
   bool scale_given = false;
+  int chain = -1;   // --chain: the bounces of --denoise's feature passes (< 0: first-hit features)
+  bool chain_given = false;
   long long ad_tol = -1;   // --adaptive: the tolerance (< 0: off)
   long long ad_samples = 0;
   int ad_tiles = 0, ad_cap_tiles = 0, ad_steps = 0;
@@ -92,7 +98,7 @@ int main(int argc, char** argv) {
   // exists: no exit while that thread may be inside the HIP runtime)
   static const char* const kValued[] = {"--scene", "--width", "--seed", "--gpus", "--grid", "--out", "--png", "--passes",
                                         "--adaptive", "--step", "--min-spp", "--max-spp", "--features", "--denoise",
-                                        "--scale"};
+                                        "--scale", "--chain"};
   for (int i = 1; i < argc; ++i) {
     const bool valued = std::any_of(std::begin(kValued), std::end(kValued),
                                     [&](const char* f) { return std::strcmp(argv[i], f) == 0; });
@@ -134,6 +140,7 @@ int main(int argc, char** argv) {
     else if (a == "--features") features = val();
     else if (a == "--denoise") denoise = val();
     else if (a == "--scale") scale = std::atoi(val()), scale_given = true;
+    else if (a == "--chain") chain = std::atoi(val()), chain_given = true;
     else if (a == "--realm") realm = true;
     else if (a == "--rejection-samplers") rejection = true;   // RT_FLAG_REJECTION_SAMPLERS
     else if (a == "--json") json = true;
@@ -190,6 +197,10 @@ int main(int argc, char** argv) {
   }
   if (scale_given && (denoise.empty() || scale < 2 || scale > 4)) {
     std::fprintf(stderr, "--scale needs --denoise and a value of 2..4, got %d\n", scale);
+    return 2;
+  }
+  if (chain_given && (denoise.empty() || chain < 0 || chain > 64)) {
+    std::fprintf(stderr, "--chain needs --denoise and a value of 0..64, got %d\n", chain);
     return 2;
   }
   rt_params p{};
@@ -380,8 +391,13 @@ int main(int argc, char** argv) {
       hp.sample_begin = k * (spp / 2);
       ok = rt_accum_create(ds, &hp, &acc[k]) == RT_OK && rt_launch_accum(ds, &hcam, &hp, acc[k], nullptr, nullptr) == RT_OK;
     }
-    ok = ok && rt_launch_feat(ds, &cam, &p, ft, nullptr, nullptr) == RT_OK &&
-         (!scale || rt_launch_feat(ds, &hcam, &cp, fc, nullptr, nullptr) == RT_OK);
+    // (--chain: the guides of what mirrors and glass show, raytracing.clj:45-58)
+    const rt_feat_chain_opts co{chain, 0.0f};
+    auto feat_pass = [&](const rt_camera* fcam, const rt_params* fp, rt_feat* f) {
+      return chain_given ? rt_launch_feat_chain(ds, fcam, fp, &co, f, nullptr, nullptr)
+                         : rt_launch_feat(ds, fcam, fp, f, nullptr, nullptr);
+    };
+    ok = ok && feat_pass(&cam, &p, ft) == RT_OK && (!scale || feat_pass(&hcam, &cp, fc) == RT_OK);
     if (!ok) std::fprintf(stderr, "--denoise failed: %s\n", rt_last_error());
     if (ok && hipMalloc(reinterpret_cast<void**>(&d_buf),
                         (npx * (9 + RT_FEAT_CHANNELS) + ncp * (6 + RT_FEAT_CHANNELS)) * sizeof(float)) != hipSuccess) {

@@ -86,6 +86,22 @@ class rt_upsample_opts(C.Structure):
     _fields_ = [("scale", C.c_int), ("normal_pow2", C.c_int), ("sigma_z", C.c_float)]
 
 
+class rt_feat_chain_opts(C.Structure):
+    _fields_ = [("max_bounces", C.c_int), ("fuzz_max", C.c_float)]
+
+
+class rt_chain_sample(C.Structure):
+    _fields_ = [("body", C.c_int32), ("bounces", C.c_int32), ("length", C.c_float), ("albedo", C.c_float * 3),
+                ("normal", C.c_float * 3)]
+
+
+# rt_launch_feat_chain's defaults (include/rt.h)
+CHAIN_DEFAULTS = dict(max_bounces=8, fuzz_max=0.0)
+# rt_chain_sample as a NumPy record (36 bytes, no padding)
+CHAIN_SAMPLE_DTYPE = [("body", "<i4"), ("bounces", "<i4"), ("length", "<f4"), ("albedo", "<f4", (3,)),
+                      ("normal", "<f4", (3,))]
+
+
 # rt_upsample's defaults (include/rt.h)
 UPSAMPLE_DEFAULTS = dict(scale=2, normal_pow2=0, sigma_z=0.05)
 
@@ -200,6 +216,11 @@ SIGNATURES = {
     "rt_feat_resolve_host": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_size_t,
                                        C.c_int64, C.POINTER(C.c_float)]),
     "rt_feat_occupancy": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "rt_launch_feat_chain": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params),
+                                       C.POINTER(rt_feat_chain_opts), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_feat_chain_host": (C.c_int, [C.POINTER(rt_scene), C.POINTER(rt_feat_chain_opts), C.POINTER(C.c_float),
+                                     C.c_size_t, C.POINTER(rt_chain_sample)]),
+    "rt_feat_chain_occupancy": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rt_adapt_resolve_half": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rt_denoiser_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "rt_denoiser_free": (C.c_int, [C.c_void_p]),
@@ -311,7 +332,7 @@ ADDITIVE = {"rt_prepare", "rt_render_u8", "rt_quantize_device", "rt_render_submi
             "rt_temporal_host_budget", "rt_launch_ids", "rt_ids_host", "rt_ids_occupancy", "rt_body_motion",
             "rt_scene_update", "rt_tree_build_host", "rt_tree_refit_host", "rt_tree_cost_host", "rt_scene_tree_info",
             "rt_scene_tree_read", "rt_schedule_read", "rt_schedule_sort", "rt_camera_coarsen", "rt_upsample",
-            "rt_upsample_host"}
+            "rt_upsample_host", "rt_launch_feat_chain", "rt_feat_chain_host", "rt_feat_chain_occupancy"}
 
 RT_FEAT_CHANNELS = 8   # rt_feat_resolve's floats per pixel: albedo rgb, normal xyz, depth, coverage
 

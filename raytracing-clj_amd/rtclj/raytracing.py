@@ -28,7 +28,8 @@ from ._lib import (BUDGET_DEFAULTS, DENOISE_DEFAULTS, RT_DIELECTRIC, RT_FEAT_CHA
                    TEMPORAL_CLAMP_DEFAULTS, TEMPORAL_DEFAULTS, RTError, check, dptr, fptr, i64ptr, iptr, lib,
                    rt_adapt_opts, rt_budget_opts, rt_camera, i32ptr, rt_denoise_opts, rt_params, rt_scene, rt_schedule_info, rt_stats,
                    rt_temporal_clamp_opts, rt_temporal_opts, rt_tree_info, u8ptr, u32ptr, u64ptr,
-                   UPSAMPLE_DEFAULTS, rt_upsample_opts)
+                   UPSAMPLE_DEFAULTS, rt_upsample_opts, CHAIN_DEFAULTS, CHAIN_SAMPLE_DTYPE, rt_chain_sample,
+                   rt_feat_chain_opts)
 
 # ---- scene (raytracing.clj:63-78) --------------------------------------------
 hittables = [
@@ -387,6 +388,45 @@ class Adaptive:
         self.close()
 
 
+def _chain_opts(chain):
+    """`chain` as the hosts take it -> rt_feat_chain_opts, or None for a
+    first-hit pass: None or False, True (the defaults), an int (max_bounces),
+    or a dict of max_bounces, fuzz_max."""
+    if chain is None or chain is False:
+        return None
+    if chain is True:
+        chain = {}
+    elif isinstance(chain, (int, np.integer)):
+        chain = dict(max_bounces=int(chain))
+    unknown = set(chain) - set(CHAIN_DEFAULTS)
+    if unknown:
+        raise TypeError(f"chain: unknown option(s) {sorted(unknown)}")
+    o = {**CHAIN_DEFAULTS, **chain}
+    return rt_feat_chain_opts(max_bounces=int(o["max_bounces"]), fuzz_max=float(o["fuzz_max"]))
+
+
+def feat_chain_host(scene, rays, library=None, **opts) -> np.ndarray:
+    """rt_feat_chain_host (include/rt.h): the specular chain of each ray on the
+    host, in plain C++ -- per sample what a Features(chain=...) pass adds on the
+    device.  rays: float32 (..., 6), origin and un-normalised direction.
+    Options: max_bounces, fuzz_max.  Returns a record array of rays' leading
+    shape with fields body (-1: the sky), bounces, length (+inf on the sky),
+    albedo (3,), normal (3,)."""
+    dll = library if library is not None else lib
+    sc = scene if isinstance(scene, Scene) else Scene.from_bodies(scene)
+    o = _chain_opts(dict(opts))
+    rays = np.ascontiguousarray(rays, np.float32)
+    if rays.ndim < 1 or rays.shape[-1] != 6:
+        raise ValueError("feat_chain_host: rays must be (..., 6)")
+    out = np.zeros(rays.shape[:-1], np.dtype(CHAIN_SAMPLE_DTYPE))
+    assert out.dtype.itemsize == C.sizeof(rt_chain_sample)
+    code = dll.rt_feat_chain_host(C.byref(sc.c), C.byref(o), fptr(rays), out.size,
+                                  out.ctypes.data_as(C.POINTER(rt_chain_sample)))
+    if code < 0:
+        raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+    return out
+
+
 class Features:
     """First-hit feature buffers (rt_feat, include/rt.h): per pixel the albedo,
     normal, depth and coverage of the first surface the pixel's camera rays
@@ -400,12 +440,19 @@ class Features:
     Two choices to know: depth is the NEAREST hit of the pixel's samples (+inf
     where none hit), not a mean; the normal is the mean over all samples with
     misses as zero, not re-normalised.  add() advances sample_begin itself;
-    frame() and raw() wait for the passes enqueued on `stream`."""
+    frame() and raw() wait for the passes enqueued on `stream`.
+
+    With `chain` (True, an int max_bounces, or a dict of max_bounces, fuzz_max:
+    rt_feat_chain_opts) every pass is a specular-chain pass
+    (rt_launch_feat_chain): the features of what mirrors and glass show.  Its
+    depth is the path length along the bends: guides for Denoiser.run and
+    upsample_into, never for Temporal.step or Temporal.probe."""
 
     def __init__(self, scene, cam: rt_camera, width: int, height: int, seed: int = 1, flags: int = 0, rows=None,
                  row_tile: int = 8, tile_first: int = 0, tile_step: int = 0, sample_begin: int = 0,
-                 device: int = 0, stream=None, library=None):
+                 device: int = 0, stream=None, library=None, chain=None):
         self._dll = library if library is not None else lib
+        self._chain = _chain_opts(chain)
         self.scene = scene if isinstance(scene, Scene) else Scene.from_bodies(scene)
         self.cam = cam
         r0, r1 = (0, height) if rows is None else rows
@@ -433,15 +480,21 @@ class Features:
         """Samples per pixel added so far (rt_feat_samples)."""
         return int(self._dll.rt_feat_samples(self._ft))
 
-    def add(self, spp: int) -> int:
-        """Enqueue one pass of `spp` more samples per pixel (rt_launch_feat);
-        returns the new count."""
+    def add(self, spp: int, d_counters=None) -> int:
+        """Enqueue one pass of `spp` more samples per pixel (rt_launch_feat, or
+        rt_launch_feat_chain with `chain`); returns the new count.  d_counters:
+        the address of two device uint64, += {segments, samples}."""
         if spp < 0:
             raise ValueError("Features.add: spp < 0")
         self._p.spp = int(spp)
         self._p.sample_begin = self._next
-        self._check(self._dll.rt_launch_feat(self._ds, C.byref(self.cam), C.byref(self._p), self._ft, None,
-                                             self._stream))
+        cnt = C.c_void_p(d_counters) if d_counters else None
+        if self._chain is None:
+            self._check(self._dll.rt_launch_feat(self._ds, C.byref(self.cam), C.byref(self._p), self._ft, cnt,
+                                                 self._stream))
+        else:
+            self._check(self._dll.rt_launch_feat_chain(self._ds, C.byref(self.cam), C.byref(self._p),
+                                                       C.byref(self._chain), self._ft, cnt, self._stream))
         self._next += int(spp)
         return self.samples
 
@@ -592,7 +645,7 @@ class Denoiser:
 
 
 def render_denoised(scene, cam: rt_camera, width: int, height: int, spp: int = 8, max_depth: int = 50, seed: int = 1,
-                    flags: int = 0, library=None, **opts):
+                    flags: int = 0, library=None, chain=None, **opts):
     """A low-sample frame and its denoised version, on device 0: two
     accumulators of spp / 2 samples each (sample indices [0, spp / 2) and
     [spp / 2, spp): together the rays render() traces at spp), the first-hit
@@ -601,9 +654,12 @@ def render_denoised(scene, cam: rt_camera, width: int, height: int, spp: int = 8
     float32 (height, width, 3), the plain mean of the two halves likewise, and
     the feature frame (height, width, 8).  The device buffers are torch's
     (import torch before rtclj, as the GPU tests and bench.py do: both bring
-    a HIP runtime and the first one loaded serves the process)."""
+    a HIP runtime and the first one loaded serves the process).  With `chain`
+    (as Features takes it) the guides are specular-chain features: what a
+    mirror or glass shows is filtered along its own edges."""
     if spp <= 0 or spp % 2:
         raise ValueError("render_denoised: spp must be even and positive")
+    _chain_opts(chain)
     import torch
     if not torch.cuda.is_available():
         raise RTError(-5, "render_denoised: torch sees no GPU (import torch before rtclj)")
@@ -617,7 +673,7 @@ def render_denoised(scene, cam: rt_camera, width: int, height: int, spp: int = 8
     torch.cuda.synchronize(dev)   # (the passes below run on the NULL stream)
     with Progressive(sc, cam, width, height, max_depth, seed, flags=flags, library=library) as a0, \
             Progressive(sc, cam, width, height, max_depth, seed, flags=flags, sample_begin=half, library=library) as a1, \
-            Features(sc, cam, width, height, seed=seed, flags=flags, library=library) as ft, \
+            Features(sc, cam, width, height, seed=seed, flags=flags, library=library, chain=chain) as ft, \
             Denoiser(width, height, library=library) as dn:
         a0.add(half)
         a1.add(half)
@@ -704,7 +760,8 @@ def upsample_into(d_half0: int, d_half1, d_feat_coarse: int, d_feat: int, width:
 
 
 def render_upscaled(scene, cam: rt_camera, width: int, height: int, spp: int = 8, scale: int = 2, max_depth: int = 50,
-                    seed: int = 1, flags: int = 0, library=None, upsample=None, stages: bool = False, **opts):
+                    seed: int = 1, flags: int = 0, library=None, upsample=None, stages: bool = False, chain=None,
+                    **opts):
     """render_denoised with the colour traced at a render scale, on device 0:
     the two accumulators (spp / 2 samples per coarse pixel each) and a second
     Features (spp samples) run on camera_coarsen(cam, scale) at the coarse
@@ -713,9 +770,12 @@ def render_upscaled(scene, cam: rt_camera, width: int, height: int, spp: int = 8
     `upsample`: a dict of normal_pow2, sigma_z (rt_upsample_opts); further
     keywords are the denoiser's.  Returns (denoised, mean, feat) as
     render_denoised does -- mean of the two upsampled halves; with `stages`
-    (denoised, up0, up1, feat, half0, half1, feat_coarse)."""
+    (denoised, up0, up1, feat, half0, half1, feat_coarse).  With `chain` (as
+    Features takes it) both the coarse and the full-size features are
+    specular-chain features: a reflection comes back along its own edges."""
     if spp <= 0 or spp % 2:
         raise ValueError("render_upscaled: spp must be even and positive")
+    _chain_opts(chain)
     uopts = dict(upsample or {}, scale=scale)
     _upsample_opts(uopts)
     _denoise_opts(opts)
@@ -736,8 +796,8 @@ def render_upscaled(scene, cam: rt_camera, width: int, height: int, spp: int = 8
     torch.cuda.synchronize(dev)   # (the passes below run on the NULL stream)
     with Progressive(sc, ccam, cw, ch, max_depth, seed, flags=flags, library=library) as a0, \
             Progressive(sc, ccam, cw, ch, max_depth, seed, flags=flags, sample_begin=half, library=library) as a1, \
-            Features(sc, ccam, cw, ch, seed=seed, flags=flags, library=library) as fc, \
-            Features(sc, cam, width, height, seed=seed, flags=flags, library=library) as ft, \
+            Features(sc, ccam, cw, ch, seed=seed, flags=flags, library=library, chain=chain) as fc, \
+            Features(sc, cam, width, height, seed=seed, flags=flags, library=library, chain=chain) as ft, \
             Denoiser(width, height, library=library) as dn:
         a0.add(half)
         a1.add(half)
@@ -1462,7 +1522,7 @@ def _same_but_centres(a: Scene, b: Scene) -> bool:
 
 def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max_depth: int = 50, seed: int = 1,
                      flags: int = 0, library=None, temporal=None, stages: bool = False, refit: bool = False, clamp=None,
-                     budget=None, scale=None, upsample=None, **opts):
+                     budget=None, scale=None, upsample=None, chain=None, **opts):
     """render_sequence for bodies that move: one Scene per frame (all with the
     same body count), zipped with `cameras`; a generator that yields float32
     (height, width, 3) per frame, on device 0.  Per frame f: the scene's upload
@@ -1497,7 +1557,14 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
     at full size, and the yielded half0, half1 are the upsampled ones.  `stages`
     then yields three more items: the coarse half0, half1 and features.  `scale`
     with `budget` is refused (the budget's tile lists belong to the traced
-    grid).  Without `scale` nothing changes."""
+    grid).  Without `scale` nothing changes.
+    With `chain` (as Features takes it) a second full-size rt_feat holds
+    specular-chain passes of the same samples and guides Denoiser.run and, with
+    `scale`, upsample_into, whose coarse features are chain passes too.  The
+    probe and the step keep the first-hit features: a reprojection needs the
+    real surface's depth and normal, so their stages are the bits of a run
+    without `chain`.  `stages` then yields the chain features as a last item."""
+    copt = _chain_opts(chain)
     if scale is not None and budget is not None:
         raise ValueError("render_animation: scale and budget cannot be combined")
     if scale is not None:
@@ -1540,7 +1607,15 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
     torch.cuda.synchronize(dev)   # (the passes below run on the NULL stream)
     shape = rt_params(width=width, height=height, row_begin=0, row_end=height, spp=0, max_depth=max_depth, seed=seed,
                       flags=flags)
-    ds, acc, ft, fc = C.c_void_p(), [C.c_void_p(), C.c_void_p()], C.c_void_p(), C.c_void_p()
+    ds, acc, ft, fc, fch = C.c_void_p(), [C.c_void_p(), C.c_void_p()], C.c_void_p(), C.c_void_p(), C.c_void_p()
+    d_chain = torch.empty(n_px * RT_FEAT_CHANNELS, dtype=torch.float32, device=dev) if copt is not None else None
+    d_guide = d_feat if copt is None else d_chain   # what the denoiser and the upsampler are guided by
+
+    def launch_feat(cam_, p_, f_, chained):
+        if chained and copt is not None:
+            ok(dll.rt_launch_feat_chain(ds, C.byref(cam_), C.byref(p_), C.byref(copt), f_, None, None))
+        else:
+            ok(dll.rt_launch_feat(ds, C.byref(cam_), C.byref(p_), f_, None, None))
     prev_sc = first_sc = None
     traced, d_tr, d_fc = shape, d_h, None   # what the accumulators trace and resolve into
     if scale is not None:
@@ -1575,6 +1650,8 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
                     ok(dll.rt_feat_create(ds, C.byref(shape), C.byref(ft)))
                     if scale is not None:
                         ok(dll.rt_feat_create(ds, C.byref(traced), C.byref(fc)))
+                    if copt is not None:
+                        ok(dll.rt_feat_create(ds, C.byref(shape), C.byref(fch)))
                     motion = np.zeros((len(sc), 4), np.float32)
                 else:
                     if budget is None:
@@ -1583,6 +1660,8 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
                     ok(dll.rt_feat_clear(ft, None))
                     if scale is not None:
                         ok(dll.rt_feat_clear(fc, None))
+                    if copt is not None:
+                        ok(dll.rt_feat_clear(fch, None))
                     motion = body_motion(sc, prev_sc, library=library)
                 tcam = cam if scale is None else camera_coarsen(cam, scale, library=library)
                 if budget is None:
@@ -1593,18 +1672,22 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
                 if scale is not None:
                     p = rt_params.from_buffer_copy(traced)
                     p.spp, p.sample_begin, p.max_depth = spp, f * stride, 1
-                    ok(dll.rt_launch_feat(ds, C.byref(tcam), C.byref(p), fc, None, None))
+                    launch_feat(tcam, p, fc, True)
                 p = rt_params.from_buffer_copy(shape)
                 p.spp, p.sample_begin, p.max_depth = spp, f * stride, 1
-                ok(dll.rt_launch_feat(ds, C.byref(cam), C.byref(p), ft, None, None))
+                launch_feat(cam, p, ft, False)
+                if copt is not None:
+                    launch_feat(cam, p, fch, True)
                 ok(dll.rt_launch_ids(ds, C.byref(cam), width, height, 0, C.c_void_p(d_ids.data_ptr()), None))
                 if budget is None:
                     ok(dll.rt_accum_resolve(acc[0], flags, C.c_void_p(d_tr[0].data_ptr()), None))
                     ok(dll.rt_accum_resolve(acc[1], flags, C.c_void_p(d_tr[1].data_ptr()), None))
                 ok(dll.rt_feat_resolve(ft, C.c_void_p(d_feat.data_ptr()), None))
+                if copt is not None:
+                    ok(dll.rt_feat_resolve(fch, C.c_void_p(d_chain.data_ptr()), None))
                 if scale is not None:
                     ok(dll.rt_feat_resolve(fc, C.c_void_p(d_fc.data_ptr()), None))
-                    upsample_into(d_tr[0].data_ptr(), d_tr[1].data_ptr(), d_fc.data_ptr(), d_feat.data_ptr(), width,
+                    upsample_into(d_tr[0].data_ptr(), d_tr[1].data_ptr(), d_fc.data_ptr(), d_guide.data_ptr(), width,
                                   height, d_h[0].data_ptr(), d_h[1].data_ptr(), library=library, **uopts)
                 d_motion = torch.from_numpy(motion.reshape(-1)).to(dev)   # (torch's allocations are 256-byte aligned)
                 moved = dict(d_ids=d_ids.data_ptr(), d_motion=d_motion.data_ptr() if len(sc) else None, n_bodies=len(sc))
@@ -1618,7 +1701,7 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
                     moved["d_mult"] = bd.d_mult
                 tp.step(cam, d_h[0].data_ptr(), d_h[1].data_ptr(), d_feat.data_ptr(), d_acc[0].data_ptr(),
                         d_acc[1].data_ptr(), **moved, **topts)
-                dn.run(d_acc[0].data_ptr(), d_acc[1].data_ptr(), d_feat.data_ptr(), d_out.data_ptr(), **opts)
+                dn.run(d_acc[0].data_ptr(), d_acc[1].data_ptr(), d_guide.data_ptr(), d_out.data_ptr(), **opts)
                 torch.cuda.synchronize(dev)
                 if not refit:
                     ok(dll.rt_scene_free(ds))
@@ -1631,7 +1714,8 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
                         tuple(d.cpu().numpy().reshape(height, width, 3) for d in d_acc) + \
                         (d_ids.cpu().numpy().reshape(height, width),) + ((bd.mult(),) if bd is not None else ()) + \
                         (() if scale is None else tuple(d.cpu().numpy().reshape(ch, cw, 3) for d in d_tr) +
-                         (d_fc.cpu().numpy().reshape(ch, cw, RT_FEAT_CHANNELS),))
+                         (d_fc.cpu().numpy().reshape(ch, cw, RT_FEAT_CHANNELS),)) + \
+                        (() if copt is None else (d_chain.cpu().numpy().reshape(height, width, RT_FEAT_CHANNELS),))
                 else:
                     yield out
     finally:
@@ -1646,6 +1730,8 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
             dll.rt_feat_free(ft)
         if fc:
             dll.rt_feat_free(fc)
+        if fch:
+            dll.rt_feat_free(fch)
 
 
 def pass_sizes(spp: int, passes: int):
@@ -1823,4 +1909,4 @@ if __name__ == "__main__":  # python -m rtclj.raytracing [spp] [depth]
 
 
 __all__ = ["hittables", "REFERENCE_CAMERA", "image_height", "flatten", "flatten64", "Scene", "camera", "render", "Progressive", "Adaptive", "pass_sizes",
-           "Features", "denoise_host", "Denoiser", "render_denoised", "camera_coarsen", "coarse_size", "upsample_host", "upsample_into", "render_upscaled", "temporal_host", "Temporal", "temporal_probe_host", "budget_plan_host", "Budget", "render_sequence", "ids_host", "body_ids_into", "body_motion", "tree_build_host", "tree_refit_host", "tree_cost", "DeviceScene", "render_animation", "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]
+           "Features", "feat_chain_host", "denoise_host", "Denoiser", "render_denoised", "camera_coarsen", "coarse_size", "upsample_host", "upsample_into", "render_upscaled", "temporal_host", "Temporal", "temporal_probe_host", "budget_plan_host", "Budget", "render_sequence", "ids_host", "body_ids_into", "body_motion", "tree_build_host", "tree_refit_host", "tree_cost", "DeviceScene", "render_animation", "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]
