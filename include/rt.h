@@ -1457,8 +1457,8 @@ int rt_quantize_device(const float* d_lin, uint8_t* d_out, size_t n, void* hip_s
  * (north_star's LDS-staged sphere list); 8 / 9 = packed-fp32 scan, LDS /
  * scalar; 11 = BVH in LDS, 2 bodies per leaf; 20 / 21 = direction-sorted
  * 8-wave lock-step workgroups (octant sort / live-path packing); and the
- * statistics builds 3, 6, 7, 10, 13, 17, 19 (= 1, 4, 5, 9, 11, 16, 18 with
- * wave-level counters, rt_debug_stats).  Returns the previous value, or
+ * statistics builds 3, 6, 7, 10, 13, 17, 19, 31 (= 1, 4, 5, 9, 11, 16, 18, 22
+ * with wave-level counters, rt_debug_stats).  Returns the previous value, or
  * RT_E_ARG for a variant this build does not hold.  Applies to subsequent
  * launches in this
  * process (an atomic, read once per launch). */
@@ -1504,7 +1504,11 @@ int rt_set_schedule(int mode);
  * [16] / [17] wave-level camera-sample blocks / lanes in them, [18] executed
  * fp32 flops (per lane, fma = 2), [19] / [20] wave-level
  * dielectric shading blocks / lanes in them, [21] / [22] wave-level
- * lambertian-or-metal shading blocks / lanes in them, [23..31] 0.
+ * lambertian-or-metal shading blocks / lanes in them, [23..26] wave-level
+ * colour-sum blocks, refills, batch claims, drain checks, [27..31] variant
+ * 31 (the tile list's prelude): wave-level prelude trips,
+ * lanes in them, the trips' leaf passes, their exact-test passes (both also
+ * in [12] / [13]), walk segments entered in an iteration that ran a trip.
  * Synchronises the devices. */
 int rt_debug_stats(uint64_t* out32);
 

@@ -3,8 +3,9 @@
 // the sphere table, the direction-coherent waves (sorted_kernel, variants 20
 // and 21: measured slower) and the statistics builds of the
 // product traversals (variants 3, 6, 7, 10, 13, 17, 19: the same kernel with
-// event and flop counters, which bench.py's roofline reads).  Every variant
-// renders the product kernel's bits.
+// event and flop counters, which bench.py's roofline reads; 31: variant 22's,
+// with the prelude's counters, which tools/prelude_stats.py reads).  Every
+// variant renders the product kernel's bits.
 #include "trace_kernel.h"
 
 namespace rtclj {
@@ -592,6 +593,8 @@ const void* diag_kernel(int v) {
     // octant-sorted, and lock-step packing only
     case 20: return reinterpret_cast<const void*>(&sorted_kernel<true>);
     case 21: return reinterpret_cast<const void*>(&sorted_kernel<false>);
+    // variant 22 with the statistics: the compact image, the tile list and its prelude
+    case 31: return reinterpret_cast<const void*>(&trace_kernel<SRC_LDS, SCAN_BVHQ7, true, 4, 0, false, true>);
   }
   return nullptr;   // (14, 15 dropped: the while-while traversal and its stats build)
 }

@@ -187,7 +187,17 @@ __device__ __forceinline__ float rng_sym(uint32_t& s) {
 // ISA block markers: in a listing built with -DRTCLJ_ISA_MARKS (make isa-marks,
 // tools/isa_blocks.py) each names the block of the kernel the lines after it
 // belong to ("cold": a rare branch); the shipped and diagnostic builds contain
-// none.  (Defined in fp_rn.h, included above.)
+// none.  (Defined in fp_rn.h, included above.)  Inside the segment's text,
+// which the prelude instantiates a second time (LIST), RT_MARKL names the
+// prelude's copy of a block "pre_<name>".
+#define RT_MARKL(name)                \
+  do {                                \
+    if constexpr (LIST) {             \
+      RT_MARK("pre_" name);           \
+    } else {                          \
+      RT_MARK(name);                  \
+    }                                 \
+  } while (0)
 
 // stats builds: count one event per wave (by its first active lane)
 __device__ __forceinline__ void wave_event(uint64_t& c) {
@@ -528,6 +538,10 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
   // wave-level events of the loop's bookkeeping: colour sums
   // added, refills, batch claims, drain-phase checks (batches spent)
   uint64_t st_sums = 0, st_refill = 0, st_claim = 0, st_drain = 0;
+  // PRE, wave-level: prelude trips and the lanes in them, the trips' leaf
+  // passes and exact passes (counted in st_leafw / st_consw too), and the walk
+  // segments entered in an iteration that ran a trip
+  uint64_t st_pre = 0, st_pre_lanes = 0, st_pre_leaf = 0, st_pre_exact = 0, st_pre_walk = 0;
   uint64_t st_c_cam = 0, st_c_scan = 0, st_c_shade = 0, st_c_acc = 0, st_ts = 0;  // clock split
   uint64_t st_t0 = 0;
   if (STATS || a.tile_cost || a.dbgw) st_t0 = __builtin_amdgcn_s_memrealtime();
@@ -1005,6 +1019,24 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
   // the other variants').  LIST (PRE's prelude, below): the closest hit from
   // the tile's list instead of the big bodies' leaves and the tree -- for
   // camera segments only, every other block the same text
+  // (1, 2 and 4 trips measured on C1 with -DRTCLJ_PRE_TRIPS: DESIGN.md §3.1)
+#ifdef RTCLJ_PRE_TRIPS
+  constexpr int kPreTrips = RTCLJ_PRE_TRIPS;
+#else
+  constexpr int kPreTrips = 2;
+#endif
+  // The gate on the trips (8, 16 and 24 measured on C1 with -DRTCLJ_PRE_MIN:
+  // DESIGN.md §3.1, §8.1): a trip runs only when at least kPreMin lanes hold
+  // an unstarted sample, or no lane holds a live path, or the wave's batches
+  // are spent; otherwise those lanes sit out this iteration's walk.  0: no
+  // gate -- a trip for any such lane, and after kPreTrips of them the lanes
+  // walk their camera segments (the kernel as it was).
+#ifdef RTCLJ_PRE_MIN
+  constexpr int kPreMin = RTCLJ_PRE_MIN;
+#else
+  constexpr int kPreMin = 16;
+#endif
+  bool pre_listed = false;   // PRE: the tile has a list (wave-uniform; set per iteration)
   auto segment = [&](auto list_tag) __attribute__((always_inline)) {
     constexpr bool LIST = decltype(list_tag)::value;
     bool done = false;
@@ -1022,11 +1054,20 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
     // the iteration).  The predicate stands inside the segment, around the
     // lanes' work only: the refill's wave-level state (the batch [wb, we))
     // is then changed by every lane alike and stays in scalar registers
-    const bool in = !PRE || (LIST ? j >= 0 : j >= -1);
+    // (under the gate, kPreMin, a lane holding an unstarted sample sits out
+    // the walk in a tile with a list: its camera segment waits for a trip)
+    const bool in = !PRE || (LIST ? j >= 0 : (kPreMin > 1 && pre_listed) ? j == -1 : j >= -1);
     if (in) {
-    RT_MARK("iteration");
+    RT_MARKL("iteration");
+    if constexpr (STATS && LIST) {
+      const uint64_t ex = __builtin_amdgcn_read_exec();
+      if (lane == __ffsll(static_cast<long long>(ex)) - 1) {
+        ++st_pre;
+        st_pre_lanes += __popcll(ex);
+      }
+    }
     if (kCompact ? j >= 0 : fresh) {
-      RT_MARK("camera");
+      RT_MARKL("camera");
       if constexpr (SWEEP) {   // a record of the launch before: the path as it left its wave
         const uint4* r = kargs_opaque()->xq + 4 * static_cast<size_t>(j);
         const uint4 r0 = r[0], r1 = r[1], r2 = r[2];
@@ -1093,9 +1134,9 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
         float qx, qy2;
         if (a.sampler & RT_SAMPLER_DISK) {
           disk_direct<STATS>(st, qx, qy2, &st_disk, &st_fl);
-          RT_MARK("camera");
+          RT_MARKL("camera");
         } else {
-          RT_MARK("rejection_disk");
+          RT_MARKL("rejection_disk");
           do {
             if constexpr (STATS) {
               wave_event(st_disk);
@@ -1133,7 +1174,7 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
       st_ts = t;
     }
     // ---- one ray-color level: hit-anything over all bodies ----
-    RT_MARK("setup");
+    RT_MARKL("setup");
     --rem;
     ++segs;
     // |d| and 1/|d| (vec3a/unit as d * (1/|d|)), both correctly rounded; one
@@ -1249,11 +1290,14 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
       // (the 4-body tree in LDS: p is a leaf record's LDS address, see the copy)
       constexpr bool kLeafRec = SRC == SRC_LDS && is_q(SCAN);
       auto leaf = [&](int p) {
-        RT_MARK("leaf");
+        RT_MARKL("leaf");
         if constexpr (STATS) {
           ++st_blk;
           const uint64_t ex = __builtin_amdgcn_read_exec();
-          if (lane == __ffsll(static_cast<long long>(ex)) - 1) ++st_leafw;
+          if (lane == __ffsll(static_cast<long long>(ex)) - 1) {
+            ++st_leafw;
+            if constexpr (LIST) ++st_pre_leaf;
+          }
         }
         // (the other trees: pairs and their indices in separate arrays; an
         // 8-body leaf runs as two 4-body halves, each with its own exact
@@ -1290,20 +1334,23 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
           const unsigned b23 = __builtin_amdgcn_perm(nc[3], nc[2], 0x0b090c0cu);
           unsigned m = __builtin_amdgcn_bitop3_b32(b01, b23, 0x01010101u, 0xa8);
           while (m) {
-            RT_MARK("exact");
+            RT_MARKL("exact");
             if constexpr (STATS) {
               const uint64_t ex = __builtin_amdgcn_read_exec();
-              if (lane == __ffsll(static_cast<long long>(ex)) - 1) ++st_consw;
+              if (lane == __ffsll(static_cast<long long>(ex)) - 1) {
+                ++st_consw;
+                if constexpr (LIST) ++st_pre_exact;
+              }
             }
             const unsigned k = __builtin_ctz(m);
             m &= m - 1;
             float h, c, disc;
             body(pa + k + k, h, c, disc);
             const int sidx = *(const int __attribute__((address_space(3)))*)(uintptr_t)(pa + 64u + (k >> 1));
-            RT_MARK("exact_accept");
+            RT_MARKL("exact_accept");
             consider_tie(h, disc, sidx);
           }
-          RT_MARK("node");
+          RT_MARKL("node");
           return;
         }
 #pragma unroll
@@ -1437,7 +1484,7 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
       };
       if constexpr (LIST) {
         // the tile's list: a wave-uniform loop of leaf passes, no walk
-        RT_MARK("tile_list");
+        RT_MARKL("tile_list");
         const int n_list = min(sgpr(static_cast<int>(s_tl[0])), kTlMax);   // (<= kTlMax here: the prelude's condition)
         for (int b = 0; b < n_list; ++b) leaf(static_cast<int>(reinterpret_cast<const unsigned short*>(s_tl + 1)[b]));
       } else {
@@ -1467,7 +1514,7 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
       asm volatile("" : "+v"(row_b));
       bool go = true;
       while (go) {
-        RT_MARK("node");
+        RT_MARKL("node");
         if constexpr (STATS) {
           ++st_sph;
           const uint64_t ex = __builtin_amdgcn_read_exec();
@@ -1513,7 +1560,7 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
       // the ray's origin and unit direction again from the packed copies the
       // walk used (the same values): the scalar ones are dead through it,
       // six VGPRs fewer at its peak
-      RT_MARK("hit");
+      RT_MARKL("hit");
       ox = o_xy.x;
       oy = o_xy.y;
       oz = o_zux.x;
@@ -1602,7 +1649,7 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
       oz = hz;
       last = best;
       if (kind == RT_LAMBERTIAN || kind == RT_METAL) {
-        RT_MARK("lambert_metal");
+        RT_MARKL("lambert_metal");
         if constexpr (STATS) {
           const uint64_t ex = __builtin_amdgcn_read_exec();
           if (lane == __ffsll(static_cast<long long>(ex)) - 1) {
@@ -1616,9 +1663,9 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
         float qx, qy, qz;
         if (a.sampler & RT_SAMPLER_SPHERE) {
           sphere_direct<STATS>(st, qx, qy, qz, &st_ball, &st_fl);
-          RT_MARK("lambert_metal");
+          RT_MARKL("lambert_metal");
         } else {
-          RT_MARK("rejection_sphere");
+          RT_MARKL("rejection_sphere");
           random_unit<STATS>(st, qx, qy, qz, &st_ball, &st_fl);
         }
         if constexpr (STATS) st_fl += kind == RT_LAMBERTIAN ? 6 : 26;
@@ -1657,7 +1704,7 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
         done = true;  // no ::scatter-fn -> black (raytracing.clj:49-54)
       } else {
         // material.clj:34-46 dielectric, reflectance :30-32, refract vec3a.clj:97-101
-        RT_MARK("dielectric");
+        RT_MARKL("dielectric");
         if constexpr (STATS) {
           const uint64_t ex = __builtin_amdgcn_read_exec();
           if (lane == __ffsll(static_cast<long long>(ex)) - 1) {
@@ -1703,7 +1750,7 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
       st_c_shade += t - st_ts;
       st_ts = t;
     }
-    RT_MARK("sums");
+    RT_MARKL("sums");
     if (done) {   // the sample's colour into its pixel's fixed-point sum (order-free)
       if constexpr (STATS) st_fl += 3;
       if constexpr (STATS) wave_event(st_sums);
@@ -1736,7 +1783,7 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
     }
     }   // (in)
     // refill: the lanes whose paths ended take their next indices
-    RT_MARK("refill");
+    RT_MARKL("refill");
     const uint64_t m = __ballot(done);
     if (m) {
       if constexpr (STATS) wave_event(st_refill);
@@ -1756,7 +1803,7 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
         wb += take;
         r0 += take;
         if (r0 >= need || we >= pool) break;
-        RT_MARK("claim");
+        RT_MARKL("claim");
         if constexpr (STATS) wave_event(st_claim);
         int g = 0;
         // a shared tile's claims shrink as its pool is spent (guided: an
@@ -1785,7 +1832,7 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
         we = min(g + (SWEEP ? 64 : want), pool);
         if (wb >= pool) we = pool;   // spent: the lanes left over retire
       }
-      RT_MARK("refill");
+      RT_MARKL("refill");
       if (done) {
         j = kCompact && nj < 0 ? -2 : nj;
         fresh = true;
@@ -1793,7 +1840,7 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
       }
     }
     if constexpr (STATS) st_c_acc += stamp() - st_ts;
-    RT_MARK("compaction");
+    RT_MARKL("compaction");
     if constexpr (kCompact && !LIST) {
       // spent: out to the compaction step when this wave may post its few
       // paths, or its idle lanes may take posted ones
@@ -1815,28 +1862,36 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
   };
   // A wave iteration.  PRE, in a tile with a list: first the prelude -- the
   // lanes holding a sample not started yet (j >= 0) run its camera segment
-  // against the list, shade it and refill, up to kPreTrips times while some
-  // lane holds one -- so that a lane enters the walk with its second segment,
-  // and a sample that ends at its first (the sky) never does.  The same text
+  // against the list, shade it and refill, up to kPreTrips times while enough
+  // lanes hold one (the gate, kPreMin) -- so that a lane enters the walk with
+  // its second segment, and a sample that ends at its first (the sky) never
+  // does; under the gate the lanes left holding one sit out the walk.  The same text
   // (segment), the same draws in the same order per path: the same bits.
   // With no live path in the wave after the prelude the iteration ends there
   // (the lanes then hold unstarted samples, or none: the drain check below
   // the walk acts only on live paths).
-  // (1, 2 and 4 trips measured on C1 with -DRTCLJ_PRE_TRIPS: DESIGN.md §3.1)
-#ifdef RTCLJ_PRE_TRIPS
-  constexpr int kPreTrips = RTCLJ_PRE_TRIPS;
-#else
-  constexpr int kPreTrips = 2;
-#endif
   auto iteration = [&]() {
     if constexpr (PRE) {
-      if (sgpr(static_cast<int>(s_tl[0])) <= kTlMax) {
+      bool tripped = false;
+      pre_listed = sgpr(static_cast<int>(s_tl[0])) <= kTlMax;
+      if (pre_listed) {
 #pragma unroll 1
         for (int trip = 0; trip < kPreTrips; ++trip) {
-          if (__ballot(j >= 0) == 0) break;
+          const uint64_t fm = __ballot(j >= 0);
+          if (fm == 0) break;
+          if constexpr (kPreMin > 1) {
+            // the gate: too few fresh lanes for a trip while the wave has live
+            // paths to walk -- unless its batches are spent: then no refill
+            // adds to them, and the drain check waits for them to start
+            if (static_cast<int>(__popcll(fm)) < kPreMin && __ballot(j == -1) != 0 && wb < pool) break;
+          }
           segment(std::true_type{});
+          tripped = true;
         }
         if (__ballot(j == -1) == 0) return;
+      }
+      if constexpr (STATS) {
+        if (tripped) wave_event(st_pre_walk);
       }
       segment(std::false_type{});
     } else {
@@ -1968,6 +2023,13 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
       atomicAdd(&a.dbg[24], static_cast<unsigned long long>(st_refill));
       atomicAdd(&a.dbg[25], static_cast<unsigned long long>(st_claim));
       atomicAdd(&a.dbg[26], static_cast<unsigned long long>(st_drain));
+    }
+    if (a.dbg && st_pre) {
+      atomicAdd(&a.dbg[27], static_cast<unsigned long long>(st_pre));
+      atomicAdd(&a.dbg[28], static_cast<unsigned long long>(st_pre_lanes));
+      atomicAdd(&a.dbg[29], static_cast<unsigned long long>(st_pre_leaf));
+      atomicAdd(&a.dbg[30], static_cast<unsigned long long>(st_pre_exact));
+      atomicAdd(&a.dbg[31], static_cast<unsigned long long>(st_pre_walk));
     }
     if (a.dbg && st_blk) {
       atomicAdd(&a.dbg[3], static_cast<unsigned long long>(st_blk));

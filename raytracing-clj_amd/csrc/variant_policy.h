@@ -49,7 +49,8 @@ enum { FEAT_LDS = 0, FEAT_GLOBAL = 1, FEAT_SCAN = 2 };   // where a feature laun
 // A/B variants -- 1, 2 simple scan (LDS, scalar cache), 4 grouped scan in LDS
 // (north_star's LDS-staged scan), 8, 9 packed pairs, 11 BVH with 2-body leaves
 // in LDS, 20 / 21 direction-coherent waves (sorted_kernel) -- and the
-// statistics builds 3, 6, 7, 10, 13, 17 (= 16 + stats), 19 (= 18 + stats).
+// statistics builds 3, 6, 7, 10, 13, 17 (= 16 + stats), 19 (= 18 + stats),
+// 31 (= 22 + stats: the list path with the prelude's counters).
 // Every variant renders the same bits.
 enum : int {
   kDefault = 0,
@@ -127,7 +128,8 @@ constexpr Traits kTraits[kVariants] = {
     kNone,
     // (22 without the tile list: camera segments through the walk)
     {8, 256, 0, true, false, BUILD_PRODUCT, WALK_BVH, 1, true, 1, 0},     // 30
-    kNone,
+    // (22's statistics build, the prelude's counters included: rt_debug_stats 27-31)
+    {8, 256, 0, true, true, BUILD_DIAG, WALK_BVH, 1, true, 1, 0},         // 31 = 22 + stats
 };
 // does a build (diag: the diagnostic library) carry variant v?
 constexpr bool has_variant(int v, bool diag) {

@@ -21,8 +21,10 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tools"))
 from isa_cost import classify  # noqa: E402
 
-# variant 22: trace_kernel<SRC_LDS, SCAN_BVHQ7, false, 4, 0>
-DEFAULT_KERNEL = "_ZN5rtclj12trace_kernelILi1ELi8ELb0ELi4ELi0EEEvNS_5KArgsE"
+# variant 22: trace_kernel<SRC_LDS, SCAN_BVHQ7, false, 4, 0, false, true> (the
+# tile list: its prelude instantiates the segment a second time, and that
+# copy's blocks are named pre_<block>, RT_MARKL in trace_kernel.h)
+DEFAULT_KERNEL = "_ZN5rtclj12trace_kernelILi1ELi8ELb0ELi4ELi0ELb0ELb1EEEvNS_5KArgsE"
 
 
 # blocks whose code the compiler copies per call site (the leaf lambda is
@@ -34,6 +36,11 @@ DEFAULT_KERNEL = "_ZN5rtclj12trace_kernelILi1ELi8ELb0ELi4ELi0EEEvNS_5KArgsE"
 # EXCESS_TO
 PER_COPY = ("leaf", "exact_tail", "exact", "exact_accept")
 EXCESS_TO = "tree_setup"
+# the prelude's copies (the leaf lambda inlined at the dense records' loop and
+# at the address list's): what a larger copy holds goes to the list loop's block
+PRE = "pre_"
+PER_COPY += tuple(PRE + b for b in PER_COPY)
+PRE_EXCESS_TO = PRE + "tile_list"
 TAIL_SPLIT = re.compile(r"v_bitop3_b32.*bitop3:0xa8")
 
 
@@ -62,11 +69,11 @@ def blocks(isa, kernel):
         # the exact-test loop is rotated: its tail (root choice, acceptance,
         # the next candidate) is laid out right after the leaf pass, whose
         # last instruction merges the candidate mask (v_bitop3 0xa8)
-        if cur == "leaf" and TAIL_SPLIT.search(ln):
+        if cur in ("leaf", PRE + "leaf") and TAIL_SPLIT.search(ln):
             k0 = classify(ln)
             if k0:
-                copies["leaf"][-1][k0] += 1
-            cur = hot = "exact_tail"
+                copies[cur][-1][k0] += 1
+            cur = hot = cur[:-len("leaf")] + "exact_tail"
             copies.setdefault(cur, []).append(dict(zero))
             continue
         k = classify(ln)
@@ -78,7 +85,7 @@ def blocks(isa, kernel):
     for k, cs in copies.items():
         small = min(cs, key=lambda c: c["D"] + c["S"] + c["T"])
         out[k] = dict(small, copies=len(cs))
-        ex = out.setdefault(EXCESS_TO, dict(zero))
+        ex = out.setdefault(PRE_EXCESS_TO if k.startswith(PRE) else EXCESS_TO, dict(zero))
         for c in cs:
             for f in zero:
                 ex[f] += c[f] - small[f]
@@ -97,14 +104,15 @@ def main():
     ap.add_argument("--bench", default=None, help="a bench.py --full JSON line with stats_build (events per wave iteration)")
     ap.add_argument("--pmc-valu-per-iter", type=float, default=None,
                     help="measured VALU instructions per wave iteration (PMC SQ_INSTS_VALU / wave iterations)")
-    ap.add_argument("--iters-per-wave", type=float, default=69.0,
-                    help="wave iterations per wave (C1: 3.53 M per launch over 12,750 tiles x 4 waves)")
+    ap.add_argument("--iters-per-wave", type=float, default=90.4,
+                    help="segment calls per wave (C1, variant 22: 4.61 M per launch over 12,750 tiles x 4 waves)")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     bl = blocks(a.isa, a.kernel)
     print(f"{'block':18s} {'D':>5s} {'S':>5s} {'T':>3s} {'VALU':>5s} {'quad-cycles':>11s} {'SALU':>5s}")
     for k, b in bl.items():
-        note = f"  (one copy of {b['copies']}; the rest in {EXCESS_TO})" if "copies" in b else ""
+        note = (f"  (one copy of {b['copies']}; the rest in {PRE_EXCESS_TO if k.startswith(PRE) else EXCESS_TO})"
+                if "copies" in b else "")
         print(f"{k:18s} {b['D']:5.0f} {b['S']:5.0f} {b['T']:3.0f} {b['D'] + b['S'] + b['T']:5.0f} {qc(b):11.1f} "
               f"{b['SALU']:5.0f}{note}")
     res = {"static": bl}
@@ -124,6 +132,24 @@ def main():
               "drain_check": pw.get("drain_checks", 1.0),
               "compaction": 1.0, "loop": per_wave, "epilogue": per_wave, "prologue": per_wave,
               "compact_step": per_wave, "rejection_disk": 0.0, "rejection_sphere": 0.0, "cold": 0.0}
+        # the prelude (variant 31's counters, tools/prelude_stats.py): a trip
+        # runs the prelude's copy of the iteration's head, the camera block,
+        # the set-up, the list loop and the hit block; its leaf and exact
+        # passes are counted apart.  The shading, sums, refill and claim
+        # events above count both copies of those blocks (the same text)
+        if "prelude_trips" in pw:
+            tr = pw["prelude_trips"]
+            ev.update({PRE + b: tr for b in ("iteration", "camera", "setup", "tile_list", "hit", "compaction")})
+            ev.update({PRE + "leaf": pw["prelude_leaf_passes"], PRE + "node": pw["prelude_leaf_passes"]})
+            ev.update({PRE + b: pw["prelude_exact_passes"] for b in ("exact", "exact_accept", "exact_tail")})
+            # (the walk's once-per-iteration blocks: the iterations that reach the walk)
+            walk = pw.get("walk_segments", 1.0)
+            for b in ("iteration", "setup", "bigleaf", "tree_setup", "hit", "compaction"):
+                ev[b] = walk
+            ev["camera"] = max(pw["fresh_blocks"] - tr, 0.0)
+            ev["leaf"] = pw["leaf_passes"] - pw["prelude_leaf_passes"]
+            for b in ("exact", "exact_accept", "exact_tail"):
+                ev[b] = pw["exact_passes"] - pw["prelude_exact_passes"]
         tot_v = tot_q = 0.0
         rows = []
         for k, b in bl.items():

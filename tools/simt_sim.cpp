@@ -32,6 +32,16 @@
 //          trip costs CPRE (default 330, close to the whole outer block) plus
 //          the list's leaf passes and the exact passes of the trip's busiest
 //          lane (its camera segment's candidates as the walk met them).
+//   PREK=K (with PRE; round 21): the gate on the trips -- a
+//          trip runs only when at least K lanes hold an unstarted sample, or
+//          no lane holds a live path, or the pool is spent; otherwise those
+//          lanes sit out the iteration's walk, so a camera segment is never
+//          walked.  The policy only reorders work: the "counts:" line (samples,
+//          segments) is the same with and without it (tests/test_gpu_prelude.py's
+//          CPU test).  C1, PADT=1 PRE=2 INFL=2, 60 tiles, cost per sample at
+//          K = 0 / 8 / 16 / 24 / 32 / 48 (profiles/r21/prelude/simt_sim_prek.txt): CPRE=330
+//          54.9 / 54.5 / 53.7 / 53.2 / 53.7 / 58.7; CPRE=200 51.1 / 50.9 / 50.4 /
+//          50.4 / 51.0 / 56.2.
 //
 //   g++ -O2 -std=c++17 -I include tools/simt_sim.cpp raytracing-clj_amd/csrc/bvh.cpp \
 //       -Lraytracing-clj_amd/lib -lrtclj -Wl,-rpath,$PWD/raytracing-clj_amd/lib -o /tmp/simt_sim
@@ -68,6 +78,7 @@ static int g_pair = 2;   // policy 3: paths per lane   // policy 2: shade once t
 static int g_charge_rej = 0;   // policies 0/1: add the rejection trips to the cost (RJ=1)
 static int g_pre = 0;          // PRE=T: prelude trips per wave iteration (0: none)
 static double g_infl = 1.0, C_PRE = 330;   // INFL, CPRE
+static int g_prek = 0;         // PREK=K: the gate on the prelude's trips (0: none)
 static double g_pre_trips = 0, g_pre_lanes = 0, g_list_len = 0, g_list_tiles = 0, g_list_max = 0;
 
 // VALU wave-instructions per block (from the ISA of the default kernel,
@@ -617,6 +628,14 @@ static void run_tile(const Ctx& C, int tx, int ty, int policy, int key_mode, Res
         bool live = false;
         for (int trip = 0; trip < g_pre; ++trip) {
           int n_in = 0, max_c = 0;
+          if (g_prek > 1) {   // the gate
+            int n_fresh = 0, n_live = 0;
+            for (int l = 0; l < 64; ++l) {
+              const Path& p = lanes[64 * w + l];
+              if (p.j >= 0) (p.fresh ? n_fresh : n_live) += 1;
+            }
+            if (n_fresh < g_prek && n_live > 0 && next < pool) break;
+          }
           for (int l = 0; l < 64; ++l) {
             Path& p = lanes[64 * w + l];
             if (p.j < 0 || !p.fresh) continue;
@@ -676,6 +695,7 @@ static void run_tile(const Ctx& C, int tx, int ty, int policy, int key_mode, Res
       for (int l = 0; l < 64; ++l) {
         Path& p = lanes[64 * w + l];
         if (p.j < 0) continue;
+        if (g_pre && g_prek > 1 && p.fresh) continue;   // (gated: its camera segment waits for a trip)
         int px, py;
         pixel(p.j, px, py);
         if (step(C, p, px, py, tr[l])) done.push_back(l);
@@ -847,6 +867,7 @@ int main(int argc, char** argv) {
   if (std::getenv("PRE")) g_pre = std::atoi(std::getenv("PRE"));
   if (std::getenv("INFL")) g_infl = std::atof(std::getenv("INFL"));
   if (std::getenv("CPRE")) C_PRE = std::atof(std::getenv("CPRE"));
+  if (std::getenv("PREK")) g_prek = std::atoi(std::getenv("PREK"));
   const int v0 = std::getenv("V0") ? std::atoi(std::getenv("V0")) : 0;
   const int nv = std::getenv("NV") ? std::atoi(std::getenv("NV")) : 4;
   for (int v = v0; v < nv; ++v) {
@@ -864,6 +885,7 @@ int main(int argc, char** argv) {
     if (g_qt) { std::printf("  qt: %.3f of segments skip the tree\n", g_qt_skip / g_qt_n); g_qt_skip = g_qt_n = 0; }
     std::printf("  candidates rejected by the t bound: %.3f of %.0f; per segment: %.2f node visits, %.2f leaves\n",
                 g_rej / g_cand, g_cand, g_visits / g_segs, g_leafs / g_segs);
+    std::printf("  counts: samples %.0f segments %.0f\n", double(R.samples), g_segs);
     g_rej = g_cand = g_segs = g_visits = g_leafs = 0;
     if (g_pre && pol[v] == 0)
       std::printf("  prelude: %.3f trips per wave-iter, %.1f lanes a trip; list %.2f bodies a tile, %.0f at most\n",

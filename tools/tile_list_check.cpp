@@ -31,6 +31,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <string>
 #include <vector>
 
 #include "../include/rt.h"
@@ -289,9 +290,41 @@ void c1_lists(std::FILE* out) {
                static_cast<double>(sum_r) / tiles, max_r, static_cast<double>(over_r) / tiles, static_cast<double>(empty) / tiles);
 }
 
+// `tile_list_check count FILE`: the list length of one pixel rectangle of a
+// scene given as text -- 18 camera floats (center, p00, du, dv, disk_u,
+// disk_v) and the defocus flag; x0 x1 y0 y1 (first and last pixel centres:
+// columns, image rows); then cx cy cz r per body -- as the kernel's prologue
+// counts it: tile_keeps over every body's (centre, -r * r in fp32).  Prints
+// the count (tests/test_gpu_prelude.py builds tiles of 15, 16 and 17 with it).
+int count_file(const char* path) {
+  std::FILE* f = std::fopen(path, "r");
+  if (!f) {
+    std::fprintf(stderr, "tile_list_check: cannot read %s\n", path);
+    return 2;
+  }
+  float cam[18], r4[4];
+  int defocus = 0;
+  for (float& c : cam)
+    if (std::fscanf(f, "%f", &c) != 1) return 2;
+  if (std::fscanf(f, "%d", &defocus) != 1) return 2;
+  for (float& c : r4)
+    if (std::fscanf(f, "%f", &c) != 1) return 2;
+  const TileRays t = tile_rays(cam, defocus, r4[0], r4[1], r4[2], r4[3]);
+  float b[4];
+  int kept = 0, n = 0;
+  while (std::fscanf(f, "%f %f %f %f", &b[0], &b[1], &b[2], &b[3]) == 4) {
+    kept += tile_keeps(t, b[0], b[1], b[2], -(b[3] * b[3]));
+    ++n;
+  }
+  std::fclose(f);
+  std::printf("{\"bodies\": %d, \"kept\": %d}\n", n, kept);
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+  if (argc > 2 && std::string(argv[1]) == "count") return count_file(argv[2]);
   const long want = argc > 1 ? std::atol(argv[1]) : 5000000;   // candidate pairs at least
   std::mt19937 g(20240611u);
   Counts n;
