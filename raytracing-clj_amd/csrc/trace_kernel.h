@@ -188,16 +188,40 @@ __device__ __forceinline__ float rng_sym(uint32_t& s) {
 // tools/isa_blocks.py) each names the block of the kernel the lines after it
 // belong to ("cold": a rare branch); the shipped and diagnostic builds contain
 // none.  (Defined in fp_rn.h, included above.)  Inside the segment's text,
-// which the prelude instantiates a second time (LIST), RT_MARKL names the
-// prelude's copy of a block "pre_<name>".
-#define RT_MARKL(name)                \
-  do {                                \
-    if constexpr (LIST) {             \
-      RT_MARK("pre_" name);           \
-    } else {                          \
-      RT_MARK(name);                  \
-    }                                 \
+// which the prelude kernel instantiates in parts (SegTag, below), RT_MARKL
+// names a block by the copy it stands in (MK): the walk's "<name>", the
+// prelude trip's "pre_<name>", the merged tail's "tail_<name>" and the walk's
+// miss exit's "miss_<name>".
+enum { MK_WALK = 0, MK_PRE = 1, MK_TAIL = 2, MK_MISS = 3 };
+#define RT_MARKL(name)                    \
+  do {                                    \
+    if constexpr (MK == MK_PRE) {         \
+      RT_MARK("pre_" name);               \
+    } else if constexpr (MK == MK_TAIL) { \
+      RT_MARK("tail_" name);              \
+    } else if constexpr (MK == MK_MISS) { \
+      RT_MARK("miss_" name);              \
+    } else {                              \
+      RT_MARK(name);                      \
+    }                                     \
   } while (0)
+// The parts of a segment: all of it, for the kernels without
+// the prelude; or its search alone (the camera sample, the set-up and the
+// closest hit -- from the tile's list with LIST, by the walk without), the
+// walk's miss exit (the sky's colour, the sums, the refill), or its tail (the
+// shading of a search's result, the sums, the refill, the drain check).
+enum { SEG_ALL = 0, SEG_SEARCH = 1, SEG_MISS = 2, SEG_TAIL = 3 };
+template <int PART_, bool LIST_>
+struct SegTag {
+  static constexpr int part = PART_;
+  static constexpr bool list = LIST_;
+};
+// a search's result, handed from one part to the next: the ray's unit
+// direction and its closest hit (best < 0: none)
+struct SegHit {
+  float ux, uy, uz, best_t;
+  int best;
+};
 
 // stats builds: count one event per wave (by its first active lane)
 __device__ __forceinline__ void wave_event(uint64_t& c) {
@@ -1016,30 +1040,31 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
   };
   // one segment of the wave's active lanes' paths, then their refill (with
   // compaction, j's states above; `active` and `fresh` are only the step's and
-  // the other variants').  LIST (PRE's prelude, below): the closest hit from
-  // the tile's list instead of the big bodies' leaves and the tree -- for
-  // camera segments only, every other block the same text
-  // (1, 2 and 4 trips measured on C1 with -DRTCLJ_PRE_TRIPS: DESIGN.md §3.1)
-#ifdef RTCLJ_PRE_TRIPS
-  constexpr int kPreTrips = RTCLJ_PRE_TRIPS;
-#else
-  constexpr int kPreTrips = 2;
-#endif
+  // the other variants').  The kernels without the prelude run it whole
+  // (SEG_ALL); PRE's iteration, below, runs it in parts (SegTag), a search's
+  // result passing from part to part in `hit`.  LIST (the prelude's trip):
+  // the closest hit from the tile's list instead of the big bodies' leaves and
+  // the tree -- for camera segments only, every other block the same text
+  //
   // The gate on the trips (8, 16 and 24 measured on C1 with -DRTCLJ_PRE_MIN:
   // DESIGN.md §3.1, §8.1): a trip runs only when at least kPreMin lanes hold
-  // an unstarted sample, or no lane holds a live path, or the wave's batches
-  // are spent; otherwise those lanes sit out this iteration's walk.  0: no
-  // gate -- a trip for any such lane, and after kPreTrips of them the lanes
-  // walk their camera segments (the kernel as it was).
+  // an unstarted sample, or no lane holds a hit to shade, or the wave's
+  // batches are spent; otherwise those lanes sit out this iteration.  0: no
+  // gate -- a trip for any such lane.
 #ifdef RTCLJ_PRE_MIN
   constexpr int kPreMin = RTCLJ_PRE_MIN;
 #else
   constexpr int kPreMin = 16;
 #endif
   bool pre_listed = false;   // PRE: the tile has a list (wave-uniform; set per iteration)
-  auto segment = [&](auto list_tag) __attribute__((always_inline)) {
-    constexpr bool LIST = decltype(list_tag)::value;
+  auto segment = [&](auto seg_tag, SegHit& hit) __attribute__((always_inline)) {
+    constexpr bool LIST = decltype(seg_tag)::list;
+    constexpr int PART = decltype(seg_tag)::part;
+    constexpr bool kSearch = PART == SEG_ALL || PART == SEG_SEARCH;   // this part holds the search
+    constexpr bool kTail = PART != SEG_SEARCH;                        // ... the shading's side
+    constexpr int MK = PART == SEG_MISS ? MK_MISS : PART == SEG_TAIL ? MK_TAIL : LIST ? MK_PRE : MK_WALK;
     bool done = false;
+    if constexpr (kSearch) {
     if constexpr (STATS) st_ts = stamp();
     if constexpr (STATS) {  // counted once per wave event, by its first active lane
       const uint64_t ex = __builtin_amdgcn_read_exec();
@@ -1048,16 +1073,25 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
         st_lanes += __popcll(ex);
       }
     }
-    // PRE: the lanes of this segment -- the prelude's are those holding an
-    // unstarted sample, the walk's those holding a sample or a path (a lane
-    // retired by the prelude's refill stays in the wave's loop to the end of
-    // the iteration).  The predicate stands inside the segment, around the
+    }
+    // the search's result: this part's own, or (PRE) the one an earlier part left
+    float ux, uy, uz, best_t;
+    int best;
+    if constexpr (!kSearch) {
+      ux = hit.ux, uy = hit.uy, uz = hit.uz, best_t = hit.best_t, best = hit.best;
+    }
+    // PRE: the lanes of this part -- the trip's are those holding an
+    // unstarted sample; the walk's those holding a path, and in a tile
+    // without a list those holding a sample too; the miss exit's the walk's
+    // that hit nothing; the tail's all that hold a search's result (a lane
+    // retired by a refill stays in the wave's loop to the end of the
+    // iteration).  The predicate stands inside the segment, around the
     // lanes' work only: the refill's wave-level state (the batch [wb, we))
     // is then changed by every lane alike and stays in scalar registers
-    // (under the gate, kPreMin, a lane holding an unstarted sample sits out
-    // the walk in a tile with a list: its camera segment waits for a trip)
-    const bool in = !PRE || (LIST ? j >= 0 : (kPreMin > 1 && pre_listed) ? j == -1 : j >= -1);
+    const bool in = !PRE || (PART == SEG_SEARCH ? (LIST ? j >= 0 : pre_listed ? j == -1 : j >= -1)
+                             : PART == SEG_MISS ? (j == -1 && best < 0) : j == -1);
     if (in) {
+    if constexpr (kSearch) {
     RT_MARKL("iteration");
     if constexpr (STATS && LIST) {
       const uint64_t ex = __builtin_amdgcn_read_exec();
@@ -1190,11 +1224,11 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
       len = sqrt_rn(len2);
       il = rcp_rn(len);
     }
-    float ux = dx * il, uy = dy * il, uz = dz * il;
+    ux = dx * il, uy = dy * il, uz = dz * il;
     const float tmin = 1e-3f * len;                           // t-min 1e-3 in |d| units (:48)
     if constexpr (STATS) st_fl += 11;                         // |d|, 1/|d|, u, t-min
-    float best_t = INFINITY;
-    int best = -1;
+    best_t = INFINITY;
+    best = -1;
     // the candidate block: roots, root choice, strict closest test.  The body
     // the ray is leaving gets sq = |h| (exact arithmetic has c = 0 there:
     // the origin lies on its surface) -- the self-hit acne guard.
@@ -1609,14 +1643,20 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
       const uint64_t ex = __builtin_amdgcn_read_exec();
       if (lane == __ffsll(static_cast<long long>(ex)) - 1) st_sph += static_cast<uint64_t>(n);
     }
+    if constexpr (PART == SEG_SEARCH) {   // left for the miss exit and the tail
+      hit.ux = ux, hit.uy = uy, hit.uz = uz, hit.best_t = best_t, hit.best = best;
+    }
+    }   // (kSearch)
 
+    if constexpr (kTail) {
+    if constexpr (PART != SEG_ALL) RT_MARKL("shade");   // (whole, it goes on in the search's "hit")
     if constexpr (STATS) {
       const uint64_t t = stamp();
       st_c_scan += t - st_ts;
       st_ts = t;
     }
     float cr = 0.0f, cg = 0.0f, cb = 0.0f;
-    if (best < 0) {
+    if (PART == SEG_MISS || best < 0) {
       // sky (raytracing.clj:55-58)
       if constexpr (STATS) st_fl += 12;
       const float sa = 0.5f * (uy + 1.0f);
@@ -1781,7 +1821,9 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
         __hip_atomic_fetch_add(acc + 2, static_cast<AccT>(fix24(cb)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
     }
+    }   // (kTail)
     }   // (in)
+    if constexpr (kTail) {
     // refill: the lanes whose paths ended take their next indices
     RT_MARKL("refill");
     const uint64_t m = __ballot(done);
@@ -1841,7 +1883,7 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
     }
     if constexpr (STATS) st_c_acc += stamp() - st_ts;
     RT_MARKL("compaction");
-    if constexpr (kCompact && !LIST) {
+    if constexpr (kCompact && PART != SEG_MISS) {
       // spent: out to the compaction step when this wave may post its few
       // paths, or its idle lanes may take posted ones
       // (the limit and the flags from LDS: no registers held for them)
@@ -1859,43 +1901,55 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
         }
       }
     }
+    }   // (kTail)
   };
-  // A wave iteration.  PRE, in a tile with a list: first the prelude -- the
-  // lanes holding a sample not started yet (j >= 0) run its camera segment
-  // against the list, shade it and refill, up to kPreTrips times while enough
-  // lanes hold one (the gate, kPreMin) -- so that a lane enters the walk with
-  // its second segment, and a sample that ends at its first (the sky) never
-  // does; under the gate the lanes left holding one sit out the walk.  The same text
+  // A wave iteration.  PRE, in a tile with a list, shades the walk's hits and
+  // the camera rays' in one pass:
+  //   1. the lanes holding a path (j == -1) walk their segment; those that hit
+  //      nothing leave at once -- the sky's colour, the sums, the refill (the
+  //      miss exit);
+  //   2. the trip: the lanes holding a sample not started yet (j >= 0), those
+  //      just refilled included, run its camera segment's search against the
+  //      tile's list -- under the gate (kPreMin) only when enough lanes hold
+  //      one, or no lane is left holding a hit, or the batches are spent;
+  //      otherwise they sit out the iteration;
+  //   3. one tail for every lane that now holds a search's result: the walk's
+  //      hits and the trip's lanes (its camera rays into the sky included) are
+  //      shaded together; the paths that end there are summed and refilled.
+  // The two searches leave (u, best_t, best) in the same variables, each under
+  // its own lanes.  So a lane enters the walk with its second segment, a
+  // sample that ends at its first never does, and a wave pays for the
+  // shading's blocks once per iteration, not once per search.  The same text
   // (segment), the same draws in the same order per path: the same bits.
-  // With no live path in the wave after the prelude the iteration ends there
-  // (the lanes then hold unstarted samples, or none: the drain check below
-  // the walk acts only on live paths).
+  // A tile without a list keeps the plain flow: the camera sample inside the
+  // walk's part, no miss exit, the same tail.
   auto iteration = [&]() {
+    SegHit hit;
     if constexpr (PRE) {
-      bool tripped = false;
       pre_listed = sgpr(static_cast<int>(s_tl[0])) <= kTlMax;
+      const bool walked = __ballot(pre_listed ? j == -1 : j >= -1) != 0;
+      bool tripped = false;
+      if (walked) {
+        segment(SegTag<SEG_SEARCH, false>{}, hit);
+        if (pre_listed) segment(SegTag<SEG_MISS, false>{}, hit);
+      }
       if (pre_listed) {
-#pragma unroll 1
-        for (int trip = 0; trip < kPreTrips; ++trip) {
-          const uint64_t fm = __ballot(j >= 0);
-          if (fm == 0) break;
-          if constexpr (kPreMin > 1) {
-            // the gate: too few fresh lanes for a trip while the wave has live
-            // paths to walk -- unless its batches are spent: then no refill
-            // adds to them, and the drain check waits for them to start
-            if (static_cast<int>(__popcll(fm)) < kPreMin && __ballot(j == -1) != 0 && wb < pool) break;
-          }
-          segment(std::true_type{});
+        RT_MARK("gate");
+        const uint64_t fm = __ballot(j >= 0);
+        // the gate: too few fresh lanes for a trip while lanes hold hits to
+        // shade -- unless the wave's batches are spent: then no refill adds to
+        // them, and the drain check waits for them to start
+        if (fm != 0 && (static_cast<int>(__popcll(fm)) >= kPreMin || __ballot(j == -1) == 0 || wb >= pool)) {
+          segment(SegTag<SEG_SEARCH, true>{}, hit);
           tripped = true;
         }
-        if (__ballot(j == -1) == 0) return;
       }
+      segment(SegTag<SEG_TAIL, false>{}, hit);
       if constexpr (STATS) {
-        if (tripped) wave_event(st_pre_walk);
+        if (tripped && walked) wave_event(st_pre_walk);
       }
-      segment(std::false_type{});
     } else {
-      segment(std::false_type{});
+      segment(SegTag<SEG_ALL, false>{}, hit);
     }
   };
   for (;;) {

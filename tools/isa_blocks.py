@@ -22,8 +22,11 @@ sys.path.insert(0, str(ROOT / "tools"))
 from isa_cost import classify  # noqa: E402
 
 # variant 22: trace_kernel<SRC_LDS, SCAN_BVHQ7, false, 4, 0, false, true> (the
-# tile list: its prelude instantiates the segment a second time, and that
-# copy's blocks are named pre_<block>, RT_MARKL in trace_kernel.h)
+# tile list: its iteration instantiates the segment in parts, RT_MARKL in
+# trace_kernel.h -- the walk's search "<block>", the prelude trip's search
+# "pre_<block>", the walk's miss exit "miss_<block>" and the merged tail
+# "tail_<block>"; a listing from before the merged tail has the segment twice,
+# whole: "<block>" and "pre_<block>")
 DEFAULT_KERNEL = "_ZN5rtclj12trace_kernelILi1ELi8ELb0ELi4ELi0ELb0ELb1EEEvNS_5KArgsE"
 
 
@@ -150,6 +153,21 @@ def main():
             ev["leaf"] = pw["leaf_passes"] - pw["prelude_leaf_passes"]
             for b in ("exact", "exact_accept", "exact_tail"):
                 ev[b] = pw["exact_passes"] - pw["prelude_exact_passes"]
+            if "tail_shade" in bl:
+                # the merged tail: a wave iteration is a walk, a trip or both
+                # (walk_segments_after_a_trip), and shades once.  The miss exit
+                # is priced once per walk (an upper bound: it needs a lane that
+                # hit nothing, in a tile with a list); the statistics build
+                # counts the sums and refills of both copies together, so the
+                # tail's are what the walks leave of them; a claim costs the
+                # same in either copy
+                its = 1.0 - pw.get("walk_segments_after_a_trip", 0.0)
+                ev.update({"miss_shade": walk, "miss_sums": walk, "miss_refill": walk, "miss_compaction": walk,
+                           "miss_claim": 0.0, "gate": its, "tail_shade": its, "tail_compaction": its,
+                           "tail_lambert_metal": pw["lambert_metal_blocks"], "tail_dielectric": pw["dielectric_blocks"],
+                           "tail_rejection_sphere": 0.0,
+                           "tail_sums": max(pw.get("sums_blocks", 1.0) - walk, 0.0),
+                           "tail_refill": max(pw.get("refills", 1.0) - walk, 0.0), "tail_claim": pw.get("claims", 1.0)})
         tot_v = tot_q = 0.0
         rows = []
         for k, b in bl.items():

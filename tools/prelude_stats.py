@@ -3,9 +3,10 @@
 the C1 frame: one warm-up launch, one counted launch, and the wave-level events
 per segment call -- the walk's and the prelude's (rt_debug_stats 27-31:
 prelude trips, lanes in them, their leaf and exact passes, walk segments
-entered after a trip).  Under the tile list a wave iteration is up to
-kPreTrips prelude trips and a walk segment, each one call of the segment's
-text and one count of rt_debug_stats[0]; the rates below are per such call.
+entered in an iteration that ran a trip).  Under the tile list a wave
+iteration is a walk segment, a prelude trip or both, shaded in one tail; a walk
+and a trip are each one search of the segment's text and one count of
+rt_debug_stats[0]; the rates below are per such call.
 
 Prints one JSON line in the shape of a bench.py --full line's stats_build, so
 that tools/isa_blocks.py --bench reads it:
@@ -77,7 +78,8 @@ def main():
           "leaf_passes": d[12] / wi, "exact_passes": d[13] / wi,
           "prelude_trips": trips / wi, "prelude_lanes": d[28] / max(trips, 1),
           "prelude_leaf_passes": d[29] / wi, "prelude_exact_passes": d[30] / wi,
-          "walk_segments": (wi - trips) / wi, "walk_segments_after_a_trip": d[31] / wi}
+          "walk_segments": (wi - trips) / wi, "walk_segments_after_a_trip": d[31] / wi,
+          "wave_iterations": (wi - d[31]) / wi}
     line = {"workload": f"cover({a.grid}) {w}x{h} spp {a.spp} depth {a.depth}", "segments": segs, "samples": smp,
             "occupancy": list(occ), "raw": d,
             "prelude": {"trips_per_sample": trips / smp, "lanes_per_trip": d[28] / max(trips, 1),

@@ -42,6 +42,21 @@
 //          K = 0 / 8 / 16 / 24 / 32 / 48 (profiles/r21/prelude/simt_sim_prek.txt): CPRE=330
 //          54.9 / 54.5 / 53.7 / 53.2 / 53.7 / 58.7; CPRE=200 51.1 / 50.9 / 50.4 /
 //          50.4 / 51.0 / 56.2.
+//   TAIL=1 (with PRE and PREK; round 22): the rotated
+//          iteration -- the lanes holding a path walk first and the misses
+//          leave at once (the miss exit: CMISS, default 40, per walk); then one
+//          gated trip for the fresh lanes, those just refilled included; then
+//          one tail (CTAIL, default 140: hit record, lambertian/metal, the
+//          dielectric block's share, sums, refill) for every lane holding a
+//          search's result, paid once per iteration that has one.  The walk and
+//          the trip are priced without their own tails (C_OUT - CTAIL, CPRE -
+//          CTAIL); a path that ends in the tail is refilled after it, fresh for
+//          the next iteration's trip.  The same samples and segments
+//          (tests/test_gpu_merged_tail.py's CPU test).  C1, PADT=1 PRE=2 INFL=2
+//          PREK=16 CPRE=264, 150 tiles, cost per sample
+//          (profiles/r22/merged_tail/simt_sim_tail.txt): TAIL=0 48.6, TAIL=1
+//          46.9 (-3.5 %); TAIL=0 with the trip merely priced without a tail (CPRE=170)
+//          46.3.
 //
 //   g++ -O2 -std=c++17 -I include tools/simt_sim.cpp raytracing-clj_amd/csrc/bvh.cpp \
 //       -Lraytracing-clj_amd/lib -lrtclj -Wl,-rpath,$PWD/raytracing-clj_amd/lib -o /tmp/simt_sim
@@ -79,6 +94,8 @@ static int g_charge_rej = 0;   // policies 0/1: add the rejection trips to the c
 static int g_pre = 0;          // PRE=T: prelude trips per wave iteration (0: none)
 static double g_infl = 1.0, C_PRE = 330;   // INFL, CPRE
 static int g_prek = 0;         // PREK=K: the gate on the prelude's trips (0: none)
+static int g_tail = 0;         // TAIL=1: the rotated iteration -- walk, miss exit, trip, one tail
+static double C_TAIL = 140, C_MISS = 40;   // CTAIL, CMISS
 static double g_pre_trips = 0, g_pre_lanes = 0, g_list_len = 0, g_list_tiles = 0, g_list_max = 0;
 
 // VALU wave-instructions per block (from the ISA of the default kernel,
@@ -110,6 +127,7 @@ struct Scene {
 struct Trav {
   int disk_tries = 0, ball_tries = 0;   // rejection-loop trips of this lane's iteration
   int absorbed = 0;                     // a metal scatter went below the surface
+  int missed = 0;                       // the segment hit nothing (the sky)
   int big_c = 0;                 // candidate bitmask of the big bodies (their leaf pass: every segment)
   std::vector<uint8_t> leaves;   // per visit: leaves entered (0-2)
   std::vector<uint8_t> c1, c2;   // per visit: candidate bitmasks of the first / second leaf
@@ -322,6 +340,7 @@ static bool step(const Ctx& C, Path& p, int px, int py, Trav& tr) {
   const float len = std::sqrt(p.d[0] * p.d[0] + p.d[1] * p.d[1] + p.d[2] * p.d[2]);
   const float u[3] = {p.d[0] / len, p.d[1] / len, p.d[2] / len};
   const Hit h = trace(S, p.o[0], p.o[1], p.o[2], u[0], u[1], u[2], 1e-3f * len, p.last, &tr);
+  if (h.body < 0) tr.missed = 1;
   if (h.body < 0 || p.rem == 0) return true;
   const float* c = &S.sph[4 * h.body];
   float hp[3], n[3];
@@ -624,6 +643,63 @@ static void run_tile(const Ctx& C, int tx, int ty, int policy, int key_mode, Res
       std::vector<Trav> tr(64);
       std::vector<const Trav*> act;
       std::vector<int> done;
+      if (g_pre && g_tail) {
+        // the rotated iteration: the lanes holding a path walk; the misses
+        // leave at once (the miss exit: sums and refill); then one gated trip
+        // for the fresh lanes, those just refilled included; then one tail for
+        // every lane holding a search's result, whose ended paths are refilled
+        // after it -- fresh for the next iteration's trip
+        double c = 0.0;
+        int n_hold = 0;
+        std::vector<int> ends;   // ended in the tail
+        for (int l = 0; l < 64; ++l) {
+          Path& p = lanes[64 * w + l];
+          if (p.j < 0 || p.fresh) continue;
+          int px, py;
+          pixel(p.j, px, py);
+          const bool ended = step(C, p, px, py, tr[l]);
+          act.push_back(&tr[l]);
+          R.lane_steps += tr[l].leaves.size();
+          if (tr[l].missed) {
+            p = Path{};
+            p.j = next < pool ? next++ : -1;
+          } else {
+            ++n_hold;
+            if (ended) ends.push_back(l);
+          }
+        }
+        if (!act.empty()) c += wave_cost(act, &R.steps) - C_TAIL + C_MISS;
+        int n_fresh = 0;
+        for (int l = 0; l < 64; ++l) n_fresh += lanes[64 * w + l].j >= 0 && lanes[64 * w + l].fresh;
+        if (n_fresh > 0 && (g_prek <= 1 || n_fresh >= g_prek || n_hold == 0 || next >= pool)) {
+          int max_c = 0;
+          for (int l = 0; l < 64; ++l) {
+            Path& p = lanes[64 * w + l];
+            if (p.j < 0 || !p.fresh) continue;
+            int px, py;
+            pixel(p.j, px, py);
+            Trav t;
+            if (step(C, p, px, py, t)) ends.push_back(l);
+            int nc = __builtin_popcount(t.big_c);
+            for (size_t i = 0; i < t.leaves.size(); ++i) nc += __builtin_popcount(t.c1[i]) + __builtin_popcount(t.c2[i]);
+            max_c = std::max(max_c, nc);
+            ++n_hold;
+          }
+          c += C_PRE - C_TAIL + C_LEAF * list_passes + C_EXACT * max_c;
+          g_pre_trips += 1;
+          g_pre_lanes += n_fresh;
+        }
+        if (n_hold > 0) c += C_TAIL;
+        for (int l : ends) {
+          Path& p = lanes[64 * w + l];
+          p = Path{};
+          p.j = next < pool ? next++ : -1;
+        }
+        wc[w] += c;
+        R.cost += c;
+        R.iters += 1;
+        continue;
+      }
       if (g_pre) {   // the prelude: camera segments against the list, shaded, refilled
         bool live = false;
         for (int trip = 0; trip < g_pre; ++trip) {
@@ -868,6 +944,9 @@ int main(int argc, char** argv) {
   if (std::getenv("INFL")) g_infl = std::atof(std::getenv("INFL"));
   if (std::getenv("CPRE")) C_PRE = std::atof(std::getenv("CPRE"));
   if (std::getenv("PREK")) g_prek = std::atoi(std::getenv("PREK"));
+  if (std::getenv("TAIL")) g_tail = std::atoi(std::getenv("TAIL"));
+  if (std::getenv("CTAIL")) C_TAIL = std::atof(std::getenv("CTAIL"));
+  if (std::getenv("CMISS")) C_MISS = std::atof(std::getenv("CMISS"));
   const int v0 = std::getenv("V0") ? std::atoi(std::getenv("V0")) : 0;
   const int nv = std::getenv("NV") ? std::atoi(std::getenv("NV")) : 4;
   for (int v = v0; v < nv; ++v) {
