@@ -1288,6 +1288,42 @@ int rt_budget_plan_mult(rt_budget* bd, const uint32_t* d_mult, void* hip_stream)
  * neither read nor written.  d_counters as rt_launch_accum's. */
 int rt_budget_trace(const rt_dscene* ds, const rt_camera* c, const rt_params* p, rt_budget* bd, uint64_t* d_counters,
                     void* hip_stream);
+/* raytracing.clj:141-155's samples, as planned, in two launches: rt_budget_trace's
+ * arguments, checks, refusals and contract -- afterwards H0 and H1 each hold,
+ * integer for integer, what rt_budget_trace leaves on the same plan, and
+ * d_counters receives the same {segments, samples}.  It waits for the plan's
+ * read-back as rt_budget_trace does, then enqueues a kernel that writes, per
+ * half h, a table of U = sum_j n_j units on the device,
+ *   slot sum_{j' < j} n_j' + i:  {tile = list[i], (2 j + h) | (2 max_mult) << 8},
+ * for j = 0 .. max_mult - 1 and list positions i < n_j (block-major, in list
+ * order: pass 0's tiles, then pass 1's, ...), and one pass per half over its
+ * table: U workgroups, unit {tile, k | s << 8} tracing samples [k spp / s,
+ * (k + 1) spp / s) of the tile with spp = 2 max_mult half_spp -- block k of
+ * half_spp samples, indices p->sample_begin + k half_spp ....  The kernel picks
+ * the width of its pixel sums from that total spp, not from half_spp: this
+ * changes the variant's internals, not the bits.  Returns the number of trace
+ * launches, 2.  The tables (n_tiles x max_mult x 8 bytes per half) are
+ * allocated by the first call. */
+int rt_budget_trace_fused(const rt_dscene* ds, const rt_camera* c, const rt_params* p, rt_budget* bd,
+                          uint64_t* d_counters, void* hip_stream);
+/* The unit table of half `half` (0 or 1) on the host, in plain C++ (no device;
+ * raytracing.clj:141-155, before a frame): from `list` (every tile 0 .. n_tiles -
+ * 1 once, by descending multiplier) and mult (n_tiles values in 1 .. max_mult),
+ * units receives sum_t mult[t] entries of two int32 each, as above; returns
+ * their number.  RT_E_ARG, with nothing written, on a NULL argument, n_tiles <=
+ * 0, max_mult outside 1..16, a half other than 0 or 1, a multiplier outside
+ * 1 .. max_mult, or a list that is no permutation of the tiles in descending
+ * order of multiplier. */
+int rt_budget_units_host(const int32_t* list, const uint32_t* mult, int n_tiles, int max_mult, int half,
+                         int32_t* units);
+/* raytracing.clj:141-155's plan as traced: the device's table of half `half`
+ * copied to host_units (room for n_tiles x max_mult entries of two int32 is
+ * always enough); returns the number of entries U.  RT_E_ARG when no
+ * rt_budget_trace_fused has run since the last plan.  And the device's list
+ * (n_tiles int32: every tile, by descending multiplier) of the current plan.
+ * Both return when the data is there. */
+int rt_budget_units_read(const rt_budget* bd, int half, int32_t* host_units, void* hip_stream);
+int rt_budget_list_read(const rt_budget* bd, int32_t* host_list, void* hip_stream);
 /* compute-pixel's accum / spp per tile (raytracing.clj:155): rt_adapt_resolve's
  * and rt_adapt_resolve_half's conversions with this frame's counts. */
 int rt_budget_resolve(const rt_budget* bd, int flags, float* d_out, void* hip_stream);

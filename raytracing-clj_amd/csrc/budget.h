@@ -17,12 +17,14 @@
 //     counts through a callable, so that the host may loop over the tile's
 //     pixels and the device take a ballot.
 //  2. The device kernels (under __HIPCC__ and RT_BUDGET_KERNEL): the plan (one
-//     wave per tile, lane = pixel), the clamp of a caller's multipliers, and
-//     the list (the tiles by descending multiplier, the prefix counts and the
-//     per-tile sample counts).
+//     wave per tile, lane = pixel), the clamp of a caller's multipliers, the
+//     list (the tiles by descending multiplier, the prefix counts and the
+//     per-tile sample counts), and the fused trace's unit tables -- whose rule
+//     is again one text for the device and for rt_budget_units_host.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include "denoise.h"
 
@@ -99,6 +101,98 @@ inline int bd_host_plan(const rt_budget_opts* o, const float* len, int width, in
           bd_tile_mult(count, bd_tile_px(tx, ty, width, rows), o->target, o->max_mult, o->quantile_64);
     }
   return RT_OK;
+}
+
+// ---- the fused trace's unit table (rt_budget_trace_fused) ----
+// One entry per (tile, pass j < mult[tile]) and half h: trace_kernel's explicit
+// unit (KArgs::unit_tab) {x = tile, y = k | s << 8}, samples [k spp / s,
+// (k + 1) spp / s) of the tile.  With spp = 2 max_mult half_spp, s = 2 max_mult
+// and k = 2 j + h that is block k of half_spp samples: what pass j, half h of
+// rt_budget_trace traces.  Block-major, in list order: pass 0's tiles, then
+// pass 1's, ...; pass j's are the list's first n_j (it is sorted by descending
+// multiplier), so list position i of pass j has slot sum_{j' < j} n_j' + i and
+// the table is a function of the list alone.  (An int2's members; a host
+// caller's array need not be 8-byte aligned.)
+struct BdUnit {
+  int32_t x, y;
+};
+
+// List position i holds `tile`, of multiplier m (1 .. max_mult): its entries of
+// both halves' tables (either may be NULL), m each.  nj[j] = #{tiles with
+// mult > j}; a slot at or past `cap` is not written (never, for a list in
+// descending order and its own n_j: then i < n_j for every j < m).
+RT_DN_FN void bd_units_at(int i, int tile, uint32_t m, const unsigned* nj, int max_mult, int cap, BdUnit* tab0,
+                          BdUnit* tab1) {
+  const int s = (2 * max_mult) << 8;
+  int base = 0;   // sum_{j' < j} n_j'
+  for (int j = 0; j < static_cast<int>(m) && j < max_mult; ++j) {
+    const int slot = base + i;
+    if (slot >= 0 && slot < cap) {
+      if (tab0) tab0[slot] = BdUnit{tile, (2 * j) | s};
+      if (tab1) tab1[slot] = BdUnit{tile, (2 * j + 1) | s};
+    }
+    base += static_cast<int>(nj[j]);
+  }
+}
+
+// rt_budget_units_host (rt.h): the checks, the n_j from mult, then every list
+// position.  The number of entries (the sum of the multipliers), or RT_E_ARG
+// with *why set and nothing written.
+inline int bd_host_units(const int32_t* list, const uint32_t* mult, int n_tiles, int max_mult, int half, int32_t* out,
+                         const char** why) {
+  *why = nullptr;
+  if (!list || !mult || !out) {
+    *why = "NULL argument";
+    return RT_E_ARG;
+  }
+  if (max_mult < 1 || max_mult > kBdMaxMult) {
+    *why = "max_mult outside 1..16";
+    return RT_E_ARG;
+  }
+  if (half != 0 && half != 1) {
+    *why = "half is neither 0 nor 1";
+    return RT_E_ARG;
+  }
+  if (n_tiles <= 0 || n_tiles > 0x7fffffff / kBdMaxMult) {
+    *why = "bad n_tiles";
+    return RT_E_ARG;
+  }
+  unsigned nj[kBdMaxMult] = {};
+  for (int t = 0; t < n_tiles; ++t) {
+    if (mult[t] < 1u || mult[t] > static_cast<uint32_t>(max_mult)) {
+      *why = "a multiplier outside 1..max_mult";
+      return RT_E_ARG;
+    }
+    for (uint32_t j = 0; j < mult[t]; ++j) ++nj[j];
+  }
+  // the list: every tile once, by descending multiplier (nj[m] as the tile's
+  // mark: positions [nj[m], nj[m - 1]) hold the tiles of multiplier m)
+  for (int i = 0; i < n_tiles; ++i) {
+    if (list[i] < 0 || list[i] >= n_tiles) {
+      *why = "a list entry outside the tiles";
+      return RT_E_ARG;
+    }
+    const uint32_t m = mult[list[i]];
+    const unsigned lo = m < static_cast<uint32_t>(kBdMaxMult) ? nj[m] : 0u;
+    if (static_cast<unsigned>(i) < lo || static_cast<unsigned>(i) >= nj[m - 1]) {
+      *why = "the list is not in descending order of multiplier";
+      return RT_E_ARG;
+    }
+  }
+  std::vector<unsigned char> seen(static_cast<size_t>(n_tiles), 0);
+  for (int i = 0; i < n_tiles; ++i) {
+    if (seen[list[i]]) {
+      *why = "a tile is listed twice";
+      return RT_E_ARG;
+    }
+    seen[list[i]] = 1;
+  }
+  int total = 0;
+  for (int j = 0; j < max_mult; ++j) total += static_cast<int>(nj[j]);
+  BdUnit* tab = reinterpret_cast<BdUnit*>(out);
+  for (int i = 0; i < n_tiles; ++i)
+    bd_units_at(i, list[i], mult[list[i]], nj, max_mult, total, half == 0 ? tab : nullptr, half == 1 ? tab : nullptr);
+  return total;
 }
 
 #if defined(__HIPCC__) && defined(RT_BUDGET_KERNEL)
@@ -184,6 +278,21 @@ __global__ __launch_bounds__(256) void budget_list_kernel(const uint32_t* __rest
       s_base[m] + __hip_atomic_fetch_add(&state[kBdCursor + m], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (at < static_cast<unsigned>(n_tiles)) list[at] = tile;   // (always: the counts add up to n_tiles)
   counts[tile] = 2u * m * static_cast<uint32_t>(half_spp);
+}
+
+// rt_budget_trace_fused: both halves' unit tables (bd_units_at) from the list,
+// the multipliers and the n_j the list kernel left in `back`.  A thread per
+// list position; every slot below sum_j n_j is written by exactly one thread,
+// none at or past `cap`.
+__global__ __launch_bounds__(256) void budget_units_kernel(const int* __restrict__ list,
+                                                           const uint32_t* __restrict__ mult,
+                                                           const unsigned* __restrict__ back, int n_tiles, int max_mult,
+                                                           int cap, BdUnit* __restrict__ tab0, BdUnit* __restrict__ tab1) {
+  const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+  if (i >= n_tiles) return;
+  const int tile = list[i];
+  if (tile < 0 || tile >= n_tiles) return;   // (never: the list holds tiles of the frame, always)
+  bd_units_at(i, tile, mult[tile], back, max_mult, cap, tab0, tab1);
 }
 #endif  // __HIPCC__ && RT_BUDGET_KERNEL
 

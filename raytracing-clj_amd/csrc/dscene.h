@@ -200,12 +200,14 @@ void pack_frame(A& a, const rt_camera& c, const rt_params& p, int rows) {
 
 // The trace unit's (trace.hip): the selector (rt_set_variant) and whether this
 // is the diagnostic build, for the passes that follow the launch's choice; and
-// rt_launch's body, which the accumulating passes share (acc_sums, active)
+// rt_launch's body, which the accumulating passes share (acc_sums, active,
+// units)
 int selected_variant();
 bool diag_build();
+int launch_tile_rows(const rt_dscene& ds, const rt_params& p, int* vsel);
 int launch_impl(const rt_dscene* ds, const rt_camera* c, const rt_params* p, float* d_out, uint64_t* d_counters,
                 void* hip_stream, unsigned long long* acc_sums, const char* who = "rt_launch",
-                const int* active = nullptr, int n_active = 0);
+                const int* active = nullptr, int n_active = 0, const int2* units = nullptr, int n_units = 0);
 
 // ---- frame buffers that outlive the launches (rt.h): what rt_accum, rt_adapt
 // and rt_feat share.  Each is on its scene's device and holds a frame shape

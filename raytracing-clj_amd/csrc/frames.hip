@@ -575,12 +575,17 @@ extern "C" int rt_adapt_read(const rt_adapt* ad, uint64_t* host_sums0, uint64_t*
 // mult per 8 x 8 tile of the output rows; list: every tile, by descending
 // mult; state: the plan kernels' scratch; back: what the list kernel leaves
 // for the host (n_j, px_j), copied to `pinned` behind it -- rt_budget_trace
-// waits for `ev` and takes the grids of its launches from there.
+// waits for `ev` and takes the grids of its launches from there.  units[h]:
+// rt_budget_trace_fused's unit tables, n_tiles x max_mult entries per half,
+// made by the first fused trace; n_units: the entries the current plan's fused
+// trace wrote (-1: none since the plan).
 struct rt_budget : HalfFrames {
   rt_budget_opts opts{};
   DevBuf<uint32_t> mult;
   DevBuf<int> list;
   DevBuf<unsigned> state, back;   // device u32[kBdState], u32[kBdBack]
+  DevBuf<BdUnit> units[2];
+  int n_units = -1;
   bool planned = false;   // a plan no trace has used yet
   bool have = false;      // nj, px hold a plan's numbers
   unsigned nj[kBdMaxMult] = {}, px[kBdMaxMult] = {};
@@ -643,6 +648,7 @@ static int budget_plan(const char* who, rt_budget* bd, const float* d_len, const
   if (const int rc = stream_on_device(who, stream, bd->device, "the scene")) return rc;
   if (bd->pending) HIP_TRY(hipEventSynchronize(bd->ev));   // (`pinned` is about to be written again)
   bd->pending = bd->planned = bd->have = false;
+  bd->n_units = -1;
   for (int k = 0; k < 2; ++k) HIP_TRY(fill_zero(bd->h[k], bd->n, stream));
   HIP_TRY(fill_zero(bd->state, kBdState, stream));
   const rt_budget_opts& o = bd->opts;
@@ -706,6 +712,58 @@ extern "C" int rt_budget_trace(const rt_dscene* ds, const rt_camera* c, const rt
   return launches;
 }
 
+// rt_budget_trace's samples in two launches (rt.h): budget_units_kernel writes
+// both halves' unit tables from the list, then one pass per half over its
+// table, at the whole frame's spp = 2 max_mult half_spp, of which a unit is
+// one block of half_spp.  The grids are the plan's sum of the n_j: the
+// read-back rt_budget_trace waits for.
+extern "C" int rt_budget_trace_fused(const rt_dscene* ds, const rt_camera* c, const rt_params* p, rt_budget* bd,
+                                     uint64_t* d_counters, void* hip_stream) {
+  clear_error();
+  if (!ds || !c || !p || !bd) return set_error(RT_E_ARG, "rt_budget_trace_fused: NULL argument");
+  if (const int rc = check_match("rt_budget_trace_fused", "the budgeted frame", *bd, *ds, *p)) return rc;
+  std::lock_guard<std::mutex> lk(bd->mu);
+  if (!bd->planned) return set_error(RT_E_ARG, "rt_budget_trace_fused: no fresh plan (rt_budget_plan comes first)");
+  const rt_budget_opts& o = bd->opts;
+  if (p->sample_begin < 0 || static_cast<int64_t>(p->sample_begin) + 2ll * o.max_mult * o.half_spp > INT_MAX)
+    return set_error(RT_E_ARG, "rt_budget_trace_fused: sample_begin + 2 * max_mult * half_spp passes 2^31 - 1");
+  HIP_TRY(hipSetDevice(bd->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (const int rc = stream_on_device("rt_budget_trace_fused", stream, bd->device, "the scene")) return rc;
+  rt_params q = *p;
+  q.spp = 2 * o.max_mult * o.half_spp;
+  q.sample_begin = p->sample_begin;
+  // (launch_impl's refusal, asked before the table kernel is enqueued: a refused call enqueues nothing)
+  int vsel = 0;
+  if (launch_tile_rows(*ds, q, &vsel) != kTile)
+    return set_error(RT_E_ARG, "rt_budget_trace_fused: variant " + std::to_string(vsel) + " has no 8 x 8 tiles");
+  if (const int rc = budget_settle(bd)) return rc;
+  int64_t total = 0;
+  for (int j = 0; j < o.max_mult; ++j) total += std::min<unsigned>(bd->nj[j], static_cast<unsigned>(bd->n_tiles));
+  const int64_t cap = static_cast<int64_t>(bd->n_tiles) * o.max_mult;   // (halves_new: within an int)
+  if (total <= 0 || total > cap) return set_error(RT_E_ARG, "rt_budget_trace_fused: the plan's counts do not add up");
+  for (int h = 0; h < 2; ++h)
+    if (!bd->units[h]) {
+      HIP_TRY(bd->units[h].alloc(static_cast<size_t>(cap)));
+      // (x = -1: no unit)
+      HIP_TRY(hipMemsetAsync(bd->units[h].p, 0xff, static_cast<size_t>(cap) * sizeof(BdUnit), stream));
+    }
+  HIP_TRY(enqueue(budget_units_kernel, dim3(static_cast<unsigned>((bd->n_tiles + 255) / 256)), dim3(256), 0, stream,
+                  static_cast<const int*>(bd->list.p), static_cast<const uint32_t*>(bd->mult.p),
+                  static_cast<const unsigned*>(bd->back.p), bd->n_tiles, o.max_mult, static_cast<int>(cap),
+                  bd->units[0].p, bd->units[1].p));
+  bd->n_units = static_cast<int>(total);
+  int launches = 0;
+  for (int h = 0; h < 2; ++h) {
+    if (const int rc = launch_impl(ds, c, &q, nullptr, d_counters, hip_stream, bd->h[h].p, "rt_budget_trace_fused",
+                                   nullptr, 0, reinterpret_cast<const int2*>(bd->units[h].p), bd->n_units))
+      return rc;
+    ++launches;
+  }
+  bd->planned = false;
+  return launches;
+}
+
 extern "C" int rt_budget_resolve(const rt_budget* bd, int flags, float* d_out, void* hip_stream) {
   return halves_resolve("rt_budget_resolve", bd, flags, d_out, nullptr, hip_stream);
 }
@@ -726,6 +784,31 @@ extern "C" int rt_budget_mult_read(const rt_budget* bd, uint32_t* host_mult, voi
   HIP_TRY(hipMemcpyAsync(host_mult, bd->mult.p, bd->n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   return RT_OK;
+}
+
+extern "C" int rt_budget_list_read(const rt_budget* bd, int32_t* host_list, void* hip_stream) {
+  clear_error();
+  if (!bd || !host_list) return set_error(RT_E_ARG, "rt_budget_list_read: NULL argument");
+  HIP_TRY(hipSetDevice(bd->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  HIP_TRY(hipMemcpyAsync(host_list, bd->list.p, bd->n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return RT_OK;
+}
+
+extern "C" int rt_budget_units_read(const rt_budget* bd, int half, int32_t* host_units, void* hip_stream) {
+  clear_error();
+  if (!bd || !host_units) return set_error(RT_E_ARG, "rt_budget_units_read: NULL argument");
+  if (half != 0 && half != 1) return set_error(RT_E_ARG, "rt_budget_units_read: half is neither 0 nor 1");
+  std::lock_guard<std::mutex> lk(bd->mu);
+  if (bd->n_units < 0 || !bd->units[half])
+    return set_error(RT_E_ARG, "rt_budget_units_read: no rt_budget_trace_fused since the plan");
+  HIP_TRY(hipSetDevice(bd->device));
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  HIP_TRY(hipMemcpyAsync(host_units, bd->units[half].p, static_cast<size_t>(bd->n_units) * sizeof(BdUnit),
+                         hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return bd->n_units;
 }
 
 extern "C" int rt_budget_device_mult(const rt_budget* bd, const uint32_t** d_mult) {

@@ -411,6 +411,16 @@ extern "C" int rt_budget_plan_host(const rt_budget_opts* o, const float* len, in
   return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_budget_plan_host: ") + (why ? why : "failed"));
 }
 
+// rt_budget_trace_fused's unit table on the host (budget.h's bd_host_units:
+// bd_units_at, the text budget_units_kernel runs)
+extern "C" int rt_budget_units_host(const int32_t* list, const uint32_t* mult, int n_tiles, int max_mult, int half,
+                                    int32_t* units) {
+  clear_error();
+  const char* why = nullptr;
+  const int rc = bd_host_units(list, mult, n_tiles, max_mult, half, units, &why);
+  return rc >= 0 ? rc : set_error(rc, std::string("rt_budget_units_host: ") + (why ? why : "failed"));
+}
+
 // rt_launch_ids on the host (body_ids.h's ids_host_pass: the pinhole ray, then
 // first_hit.h's scan over the table rt_scene_upload builds)
 extern "C" int rt_ids_host(const rt_scene* s, const rt_camera* c, int width, int rows, int row0, int32_t* out) {

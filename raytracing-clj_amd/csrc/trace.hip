@@ -592,11 +592,25 @@ struct Kernel {
   const void* fn;
   const void* sweep;
 };
-// ... chosen for (ds, p), and its tree and stack bound to the arguments
-static int bind_variant(const char* who, const rt_dscene& ds, const rt_params& p, KArgs& a, Kernel* out) {
-  int vsel = launch_variant(ds, p);
+// ... chosen for a launch of p on ds
+static int bound_variant(const rt_dscene& ds, const rt_params& p) {
+  const int vsel = launch_variant(ds, p);
   if (variant_traits(vsel).walk == policy::WALK_SORTED && p.max_depth > 1023)
-    vsel = policy::kFull4;   // (a path's depth left: 10 bits in the exchange)
+    return policy::kFull4;   // (a path's depth left: 10 bits in the exchange)
+  return vsel;
+}
+
+// ... and its tile rows: what a caller that enqueues work of its own ahead of a
+// list or unit-table pass asks first, so that the pass's refusal finds nothing
+// enqueued
+int rtclj::launch_tile_rows(const rt_dscene& ds, const rt_params& p, int* vsel) {
+  *vsel = bound_variant(ds, p);
+  return policy::variant_rows(variant_traits(*vsel));
+}
+
+// ... and its tree and stack bound to the arguments
+static int bind_variant(const char* who, const rt_dscene& ds, const rt_params& p, KArgs& a, Kernel* out) {
+  const int vsel = bound_variant(ds, p);
   const Kernel v{vsel, variant_traits(vsel), variant_fn(vsel), variant_sweep(vsel)};
   if (!v.fn) return set_error(RT_E_ARG, std::string(who) + ": no kernel for variant " + std::to_string(vsel));
   const DTree& tr = ds.tree[v.t.tree];
@@ -899,9 +913,13 @@ int Schedule::record(int n_tiles, int spp, int plan_units_next) {
 // launch's tile order, whose length stands for the tile count in the split and
 // the unit count -- the same launch with a shorter order.  It needs 8 x 8
 // tiles, and neither reads nor writes the stream's record (no cost, no order).
+// rt_budget_trace_fused's pass gives `units` instead, a device table of n_tab
+// explicit units (KArgs::unit_tab: a tile and one of s sample ranges of p->spp
+// each; budget.h makes it): one workgroup per entry and no split of its own,
+// under the same conditions as `active` (which it excludes); it needs acc_sums.
 int rtclj::launch_impl(const rt_dscene* ds, const rt_camera* c, const rt_params* p, float* d_out, uint64_t* d_counters,
                        void* hip_stream, unsigned long long* acc_sums, const char* who, const int* active,
-                       int n_active) {
+                       int n_active, const int2* units, int n_tab) {
   if (!ds || !c || !p || (!d_out && !acc_sums)) return set_error(RT_E_ARG, std::string(who) + ": NULL argument");
   if (const int rc = check_frame_args(who, *p)) return rc;
   const int rows = rows_out(*p);
@@ -928,6 +946,10 @@ int rtclj::launch_impl(const rt_dscene* ds, const rt_camera* c, const rt_params*
   const int gx = (p->width + kTile - 1) / kTile, gy = (rows + th - 1) / th;
   if (active && (th != kTile || n_active <= 0 || n_active > gx * gy))
     return set_error(RT_E_ARG, std::string(who) + ": variant " + std::to_string(v.vsel) + " has no 8 x 8 tiles");
+  if (units && th != kTile)
+    return set_error(RT_E_ARG, std::string(who) + ": variant " + std::to_string(v.vsel) + " has no 8 x 8 tiles");
+  if (units && (active || !acc_sums || n_tab <= 0))
+    return set_error(RT_E_ARG, std::string(who) + ": a unit table needs an accumulator, no tile list and n_units > 0");
   const int n_tiles = active ? n_active : gx * gy;
   a.tiles_x = gx;
   if (const int rc = bind_debug(ds->device, v, a)) return rc;
@@ -936,18 +958,19 @@ int rtclj::launch_impl(const rt_dscene* ds, const rt_camera* c, const rt_params*
   // the stream's entry: adaptive schedule and split partial sums
   Schedule* sch = nullptr;
   std::unique_lock<std::mutex> sched_lock;
-  if (!active) {
+  if (!active && !units) {
     sched_lock = std::unique_lock<std::mutex>(ds->sched.mu);
     sch = ds->sched.entry(stream);
   }
   const bool steal = sch && env_int("RTCLJ_STEAL", 1, 0) != 0 && !v.t.stats && v.t.walk != policy::WALK_SORTED;
-  const int split = ((sch || acc_sums) && p->spp > 1) ? launch_split(*ds, v, lds, n_tiles, *p) : 1;
+  // (a unit table is the split already)
+  const int split = ((sch || acc_sums) && p->spp > 1 && !units) ? launch_split(*ds, v, lds, n_tiles, *p) : 1;
   // (an accumulating pass: every unit's sums go to part[])
   const int n_whole = (split > 1 || acc_sums) ? 0 : n_tiles;
   a.split = split;
   a.n_whole = n_whole;
   a.rt_magic = magic64(a.row_tile);
-  const int64_t n_units64 = n_whole + static_cast<int64_t>(n_tiles - n_whole) * split;
+  const int64_t n_units64 = units ? n_tab : n_whole + static_cast<int64_t>(n_tiles - n_whole) * split;
   if (n_units64 > INT_MAX) return set_error(RT_E_ARG, std::string(who) + ": frame too large");
   const int n_units = static_cast<int>(n_units64);
   const bool finalize = split > 1 && !acc_sums;   // the split tiles' sums go through the stream's part buffer
@@ -962,6 +985,10 @@ int rtclj::launch_impl(const rt_dscene* ds, const rt_camera* c, const rt_params*
     if (const int rc = sch->bind_order(a, fills, n_tiles, p->spp, split > 1 ? n_units - n_whole : -1, &first_order))
       return rc;
   if (active) a.tile_order = active;
+  if (units) {
+    a.unit_tab = units;
+    a.tile_order = nullptr;
+  }
   int64_t grid = n_units;
   // Sharing balances a launch whose tiles have no cost record (plain order:
   // a process's or a shape's first frame).  In the recorded longest-first

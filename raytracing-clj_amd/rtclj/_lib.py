@@ -267,6 +267,12 @@ SIGNATURES = {
     "rt_budget_plan_mult": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_budget_trace": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
+    "rt_budget_trace_fused": (C.c_int, [C.c_void_p, C.POINTER(rt_camera), C.POINTER(rt_params), C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "rt_budget_units_host": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(C.c_int32)]),
+    "rt_budget_units_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p]),
+    "rt_budget_list_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "rt_budget_resolve": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "rt_budget_resolve_half": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rt_budget_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
@@ -332,7 +338,8 @@ ADDITIVE = {"rt_prepare", "rt_render_u8", "rt_quantize_device", "rt_render_submi
             "rt_temporal_host_budget", "rt_launch_ids", "rt_ids_host", "rt_ids_occupancy", "rt_body_motion",
             "rt_scene_update", "rt_tree_build_host", "rt_tree_refit_host", "rt_tree_cost_host", "rt_scene_tree_info",
             "rt_scene_tree_read", "rt_schedule_read", "rt_schedule_sort", "rt_camera_coarsen", "rt_upsample",
-            "rt_upsample_host", "rt_launch_feat_chain", "rt_feat_chain_host", "rt_feat_chain_occupancy"}
+            "rt_upsample_host", "rt_launch_feat_chain", "rt_feat_chain_host", "rt_feat_chain_occupancy",
+            "rt_budget_trace_fused", "rt_budget_units_host", "rt_budget_units_read", "rt_budget_list_read"}
 
 RT_FEAT_CHANNELS = 8   # rt_feat_resolve's floats per pixel: albedo rgb, normal xyz, depth, coverage
 

@@ -992,6 +992,24 @@ def budget_plan_host(length, library=None, **opts) -> np.ndarray:
     return mult
 
 
+def budget_units_host(tile_list, mult, half: int, max_mult: int, library=None) -> np.ndarray:
+    """rt_budget_units_host (include/rt.h): the fused trace's unit table of one
+    half, int32 (U, 2) with U = mult.sum(), from the tiles by descending
+    multiplier (int32, every tile once: Budget.tile_list's) and the tiles'
+    multipliers (uint32, 1 .. max_mult: Budget.mult's).  Row u is (tile, k |
+    2 * max_mult << 8): block k = 2 * pass + half of the tile's sample blocks."""
+    dll = library if library is not None else lib
+    tile_list = np.ascontiguousarray(tile_list, np.int32).reshape(-1)
+    mult = np.ascontiguousarray(mult, np.uint32).reshape(-1)
+    if tile_list.size != mult.size:
+        raise ValueError("budget_units_host: list and mult must have one entry per tile")
+    out = np.empty((max(mult.size, 1) * max(min(int(max_mult), 16), 1), 2), np.int32)
+    n = dll.rt_budget_units_host(i32ptr(tile_list), u32ptr(mult), int(mult.size), int(max_mult), int(half), i32ptr(out))
+    if n < 0:
+        raise RTError(n, dll.rt_last_error().decode(errors="replace"))
+    return out[:n].copy()
+
+
 class Budget:
     """A budgeted frame on an uploaded scene's device (rt_budget, include/rt.h):
     two half accumulators traced at a per-tile multiple of half_spp samples.
@@ -1034,13 +1052,29 @@ class Budget:
         one per tile (rt_budget_plan_mult); clamped to 1 .. max_mult."""
         self._check(self._dll.rt_budget_plan_mult(self._bd, C.c_void_p(d_mult), C.c_void_p(stream) if stream else None))
 
-    def trace(self, ds, cam: rt_camera, sample_begin: int = 0, stream=None, d_counters=None) -> int:
-        """Trace the plan (rt_budget_trace); returns the number of launches."""
+    def trace(self, ds, cam: rt_camera, sample_begin: int = 0, stream=None, d_counters=None, fused: bool = False) -> int:
+        """Trace the plan (rt_budget_trace; with `fused` rt_budget_trace_fused:
+        the same sums from two launches over device-built unit tables); returns
+        the number of launches."""
         p = rt_params.from_buffer_copy(self._p)
         p.spp, p.sample_begin = self.opts.half_spp, int(sample_begin)
-        return self._check(self._dll.rt_budget_trace(ds, C.byref(cam), C.byref(p), self._bd,
-                                                     C.c_void_p(d_counters) if d_counters else None,
-                                                     C.c_void_p(stream) if stream else None))
+        fn = self._dll.rt_budget_trace_fused if fused else self._dll.rt_budget_trace
+        return self._check(fn(ds, C.byref(cam), C.byref(p), self._bd, C.c_void_p(d_counters) if d_counters else None,
+                              C.c_void_p(stream) if stream else None))
+
+    def units(self, half: int, stream=None) -> np.ndarray:
+        """The unit table of one half that the plan's fused trace built on the
+        device, int32 (U, 2) (rt_budget_units_read)."""
+        out = np.empty((self.tiles[0] * self.tiles[1] * self.opts.max_mult, 2), np.int32)
+        n = self._check(self._dll.rt_budget_units_read(self._bd, int(half), i32ptr(out),
+                                                       C.c_void_p(stream) if stream else None))
+        return out[:n].copy()
+
+    def tile_list(self, stream=None) -> np.ndarray:
+        """The plan's tiles by descending multiplier, int32 (rt_budget_list_read)."""
+        out = np.empty(self.tiles[0] * self.tiles[1], np.int32)
+        self._check(self._dll.rt_budget_list_read(self._bd, i32ptr(out), C.c_void_p(stream) if stream else None))
+        return out
 
     @property
     def samples(self) -> int:
@@ -1539,8 +1573,10 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
     the ids) and further keywords as render_sequence.  With `stages` it
     yields (denoised, half0, half1, feat, acc0, acc1, ids).  With identical
     scenes it gives render_sequence's bits.
-    With `budget` (a dict of half_spp, target, max_mult, quantile_64: rt_budget_opts)
-    the samples go where the history is short, and `spp` is not read: per frame
+    With `budget` (a dict of half_spp, target, max_mult, quantile_64: rt_budget_opts;
+    and `fused`, default False: trace with rt_budget_trace_fused, the same bits
+    from two launches) the samples go where the history is short, and `spp` is
+    not read: per frame
     the features (a uniform 2 * half_spp, from sample index f * 2 * max_mult *
     half_spp) and the ids come first, then Temporal.probe, Budget.plan,
     Budget.trace from the same index, the two halves' resolves, the weighted
@@ -1570,8 +1606,11 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
     if scale is not None:
         uopts = dict(upsample or {}, scale=scale)
         _upsample_opts(uopts)
+    fused = False
     if budget is not None:
-        bopt = _budget_opts(dict(budget))
+        budget = dict(budget)
+        fused = bool(budget.pop("fused", False))   # (Budget.trace's, no rt_budget_opts field)
+        bopt = _budget_opts(budget)
         spp = 2 * bopt.half_spp
     if spp <= 0 or spp % 2:
         raise ValueError("render_animation: spp must be even and positive")
@@ -1695,7 +1734,7 @@ def render_animation(scenes, cameras, width: int, height: int, spp: int = 4, max
                     tp.probe(cam, d_feat.data_ptr(), d_len.data_ptr(), **moved,
                              **{k: v for k, v in topts.items() if k != "clamp"})
                     bd.plan(d_len.data_ptr())
-                    bd.trace(ds, cam, sample_begin=f * stride)
+                    bd.trace(ds, cam, sample_begin=f * stride, fused=fused)
                     bd.resolve_half_into(d_h[0].data_ptr(), 0)
                     bd.resolve_half_into(d_h[1].data_ptr(), 1)
                     moved["d_mult"] = bd.d_mult
@@ -1909,4 +1948,4 @@ if __name__ == "__main__":  # python -m rtclj.raytracing [spp] [depth]
 
 
 __all__ = ["hittables", "REFERENCE_CAMERA", "image_height", "flatten", "flatten64", "Scene", "camera", "render", "Progressive", "Adaptive", "pass_sizes",
-           "Features", "feat_chain_host", "denoise_host", "Denoiser", "render_denoised", "camera_coarsen", "coarse_size", "upsample_host", "upsample_into", "render_upscaled", "temporal_host", "Temporal", "temporal_probe_host", "budget_plan_host", "Budget", "render_sequence", "ids_host", "body_ids_into", "body_motion", "tree_build_host", "tree_refit_host", "tree_cost", "DeviceScene", "render_animation", "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]
+           "Features", "feat_chain_host", "denoise_host", "Denoiser", "render_denoised", "camera_coarsen", "coarse_size", "upsample_host", "upsample_into", "render_upscaled", "temporal_host", "Temporal", "temporal_probe_host", "budget_plan_host", "budget_units_host", "Budget", "render_sequence", "ids_host", "body_ids_into", "body_motion", "tree_build_host", "tree_refit_host", "tree_cost", "DeviceScene", "render_animation", "write_color", "write_ppm", "write_png", "ppm_to_png", "read_ppm", "main", "dptr"]

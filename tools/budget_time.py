@@ -21,10 +21,18 @@ the tiles -- a rectangle in the middle of the frame -- planned at max_mult = 8
 and the rest at 1 (rt_budget_plan_mult), half_spp = 4:
 
   budget[d]   rt_budget_plan_mult + rt_budget_trace (up to 16 launches)
+  fused[d]    rt_budget_plan_mult + rt_budget_trace_fused (the table kernel and 2
+              launches), on the same rt_budget in the same rounds
   uniform[d]  two rt_launch_accum passes of the same total samples, spread evenly
               (the smallest even spp at or above the budgeted frame's mean)
   full        two rt_launch_accum passes at 8 x the base rate: what bringing the
               short pixels to the same count costs without a plan
+
+budget_units_kernel alone is a kernel inside rt_budget_trace_fused; its time
+comes from a kernel trace of a short run, in a run of its own:
+
+  rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o prof -- \
+      python tools/budget_time.py --rounds 1 --batch 2 --frames 3
 
   python tools/budget_time.py [--rounds 9] [--batch 100] [--frames 20] [--json out.json]
 """
@@ -193,13 +201,17 @@ def main():
         spp_u = 2 * int(np.ceil(mean_spp / 2))
         launches = [0]
 
-        def budgeted(f, dm=dm, launches=launches):
+        def budgeted(f, dm=dm, launches=launches, trace=lib.rt_budget_trace):
             check(lib.rt_budget_plan_mult(bd, ptr(dm), sp))
             p = rt_params(width=w, height=h, row_begin=0, row_end=h, spp=HALF_SPP, max_depth=50, seed=1,
                           sample_begin=f * 2 * MAX_MULT * HALF_SPP)
-            launches[0] = check(lib.rt_budget_trace(ds, C.byref(cam), C.byref(p), bd, None, sp))
+            launches[0] = check(trace(ds, C.byref(cam), C.byref(p), bd, None, sp))
+
+        def fused(f, dm=dm, run=budgeted):
+            run(f, dm, [0], lib.rt_budget_trace_fused)
 
         frame_legs[f"budget[{share}]"] = budgeted
+        frame_legs[f"fused[{share}]"] = fused
         frame_legs[f"uniform[{share}]"] = uniform(spp_u)
         meta[share] = dict(tiles_at_max=int((m == MAX_MULT).sum()), mean_spp=round(mean_spp, 3), uniform_spp=spp_u,
                            launches=launches, keep=dm)
@@ -215,22 +227,27 @@ def main():
     res["shares"] = []
     crossover = None
     for share in SHARES:
-        b, u = stat(fgot[f"budget[{share}]"]), stat(fgot[f"uniform[{share}]"])
+        b, u, fu = stat(fgot[f"budget[{share}]"]), stat(fgot[f"uniform[{share}]"]), stat(fgot[f"fused[{share}]"])
         row = dict(share=share, tiles_at_max=meta[share]["tiles_at_max"], mean_spp=meta[share]["mean_spp"],
                    uniform_spp=meta[share]["uniform_spp"], launches=meta[share]["launches"][0], budget=b, uniform=u,
-                   budget_over_uniform=round(b["ms"] / u["ms"], 3), budget_over_full=round(b["ms"] / res["full"]["ms"], 3))
+                   fused=fu, budget_over_uniform=round(b["ms"] / u["ms"], 3),
+                   budget_over_full=round(b["ms"] / res["full"]["ms"], 3), fused_over_budget=round(fu["ms"] / b["ms"], 3),
+                   fused_over_uniform=round(fu["ms"] / u["ms"], 3))
         res["shares"].append(row)
         if crossover is None and share > 0 and b["ms"] >= u["ms"]:
             crossover = share
     res["first_share_not_cheaper_than_uniform"] = crossover
+    res["first_share_fused_not_cheaper_than_uniform"] = next(
+        (r["share"] for r in res["shares"] if r["share"] > 0 and r["fused"]["ms"] >= r["uniform"]["ms"]), None)
     us = lambda k: res[k]["ms"] * 1e3   # noqa: E731
     print(f"on {w} x {h}: rt_temporal_step_motion {us('motion'):.1f} us, rt_temporal_probe {us('probe'):.1f} us, "
           f"rt_budget_plan {us('plan'):.1f} us; rt_temporal_step_clamp {us('clamp2'):.1f} us, rt_temporal_step_budget "
           f"{us('budget'):.1f} us")
     for row in res["shares"]:
         print(f"  share {row['share']:.2f}: budgeted {row['budget']['ms']:.3f} ms in {row['launches']} launches "
-              f"(mean {row['mean_spp']} spp), uniform at {row['uniform_spp']} spp {row['uniform']['ms']:.3f} ms, "
-              f"ratio {row['budget_over_uniform']}")
+              f"(mean {row['mean_spp']} spp), fused {row['fused']['ms']:.3f} ms in 2 ({row['fused_over_budget']} of the "
+              f"passes), uniform at {row['uniform_spp']} spp {row['uniform']['ms']:.3f} ms, ratios "
+              f"{row['budget_over_uniform']} / {row['fused_over_uniform']}")
     print(f"  full rate ({2 * MAX_MULT * HALF_SPP} spp everywhere) {res['full']['ms']:.3f} ms; first share at which the "
           f"budgeted frame is not cheaper than its uniform equivalent: {crossover}")
     print(json.dumps(res))
