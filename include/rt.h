@@ -1543,10 +1543,30 @@ int rt_set_schedule(int mode);
  * lambertian-or-metal shading blocks / lanes in them, [23..26] wave-level
  * colour-sum blocks, refills, batch claims, drain checks, [27..31] variant
  * 31 (the tile list's prelude): wave-level prelude trips,
- * lanes in them, the trips' leaf passes, their exact-test passes (both also
+ * lanes in them, the trips' list passes (up to four listed bodies each),
+ * their exact steps (one per body some lane holds a candidate of; both also
  * in [12] / [13]), walk segments entered in an iteration that ran a trip.
  * Synchronises the devices. */
 int rt_debug_stats(uint64_t* out32);
+/* The same read-out (and the same clearing) with the counters added since the
+ * array was 32 long: the first n of 40 values, n in 0 .. 40.  [32] variant
+ * 31: the bodies its list passes tested (four or two a pass, a pass's repeats
+ * of a body included); [33..39] unused, 0. */
+int rt_debug_stats_ext(uint64_t* out, int n);
+
+/* The camera prelude's list of one tile on the host, in plain C++ (no device;
+ * raytracing.clj:33-43 for a tile's camera rays): the bodies of s that
+ * variant 22's workgroup prologue lists for 8 x 8 tile `tile` (row-major over
+ * the launch's compacted rows, ceil(width / 8) tiles a row) of the launch (c,
+ * p) -- csrc/tile_list.h's cull, the text the kernel runs, over the leaf
+ * records of the 4-body tree.  bodies receives the first cap kept bodies'
+ * indices, in record order (the kernel's order is not defined); slots
+ * (nullable) their places, 4 x record + slot.  Returns how many bodies are
+ * kept (more than 14: the kernel makes no list for the tile, its camera rays
+ * take the walk), 0 for a tile without pixels.  RT_E_ARG on a NULL s, c, p or
+ * bodies, a negative cap or tile, or a row selection rt_rows_out refuses. */
+int rt_tile_bodies_host(const rt_scene* s, const rt_camera* c, const rt_params* p, int tile, int32_t* bodies,
+                        int32_t* slots, int cap);
 
 /* Diagnostic wave timeline of the stats variants' last launches on `device`
  * (of every variant's when the diagnostic build is loaded with

@@ -37,6 +37,7 @@
 #include "rt_internal.h"
 #include "spec_chain.h"
 #include "temporal.h"
+#include "tile_list.h"
 #include "budget.h"
 #include "upsample.h"
 
@@ -419,6 +420,27 @@ extern "C" int rt_budget_units_host(const int32_t* list, const uint32_t* mult, i
   const char* why = nullptr;
   const int rc = bd_host_units(list, mult, n_tiles, max_mult, half, units, &why);
   return rc >= 0 ? rc : set_error(rc, std::string("rt_budget_units_host: ") + (why ? why : "failed"));
+}
+
+// the camera prelude's list of one tile on the host (tile_list.h's
+// tl_host_tile: the cull and the rectangle the kernel's prologue takes)
+extern "C" int rt_tile_bodies_host(const rt_scene* s, const rt_camera* c, const rt_params* p, int tile, int32_t* bodies,
+                                   int32_t* slots, int cap) {
+  clear_error();
+  if (!s || !c || !p || !bodies || cap < 0 || tile < 0 || s->n < 0 || (s->n > 0 && !s->sphere))
+    return set_error(RT_E_ARG, "rt_tile_bodies_host: NULL argument, or a negative cap, tile or body count");
+  if (s->n > RT_MAX_SPHERES) return set_error(RT_E_ARG, "rt_tile_bodies_host: too many bodies");
+  const int rows = rows_out(*p);
+  if (rows < 0 || p->width <= 0) return set_error(RT_E_ARG, "rt_tile_bodies_host: bad width or row selection");
+  float cam[18];
+  std::memcpy(cam + 0, c->center, 12);
+  std::memcpy(cam + 3, c->p00, 12);
+  std::memcpy(cam + 6, c->du, 12);
+  std::memcpy(cam + 9, c->dv, 12);
+  std::memcpy(cam + 12, c->disk_u, 12);
+  std::memcpy(cam + 15, c->disk_v, 12);
+  const TlFrame f{p->width, rows, p->row_begin, p->row_tile > 0 ? p->row_tile : 8, p->tile_first, p->tile_step};
+  return tl_host_tile(s->sphere, s->n, bvh_sah_default(), cam, c->defocus ? 1 : 0, f, tile, bodies, slots, cap);
 }
 
 // rt_launch_ids on the host (body_ids.h's ids_host_pass: the pinhole ray, then

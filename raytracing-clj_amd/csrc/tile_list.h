@@ -48,6 +48,8 @@
 #pragma once
 #include <cmath>
 
+#include "bvh.h"
+
 #if defined(__HIPCC__)
 #define RT_TL_FN __host__ __device__ __forceinline__
 #else
@@ -121,6 +123,82 @@ RT_TL_FN bool tile_keeps(const TileRays& t, float cx, float cy, float cz, float 
   };
   // [0, 1]: E(s) = (K + R_l) + s (R_f - R_l); [1, inf): E(s) = (K - R_l) + s (R_f + R_l)
   return !(excluded(K + t.rl, t.rf - t.rl, true) && excluded(K - t.rl, t.rf + t.rl, false));
+}
+
+// The list as the kernel holds it (trace_kernel.h: the prologue writes it, the
+// prelude's trip reads it): a count word and up to kTlMax u16 entries, one per
+// kept body.  A body is slot j of a leaf record of the 4-body tree: kTlRecBytes
+// bytes, the four bodies as float4s (cx, cy, cz, -r^2) at + 16 j, their
+// indices at + 64 + 4 j.  The records start 16-aligned and are a multiple of
+// 16 long, so an address's two low bits are free: the entry is the record's
+// address with j there.  More than kTlMax kept bodies, or a record above 64 KB:
+// no list.
+constexpr int kTlMax = 14;
+constexpr unsigned kTlRecBytes = 80;
+static_assert(kTlRecBytes % 16 == 0, "a record's address leaves its low bits to the slot");
+RT_TL_FN unsigned tl_entry(unsigned rec_addr, unsigned j) { return rec_addr | j; }
+RT_TL_FN unsigned tl_body_addr(unsigned e) { return (e & ~3u) + ((e & 3u) << 4); }
+RT_TL_FN unsigned tl_index_addr(unsigned e) { return (e & ~3u) + 64u + ((e & 3u) << 2); }
+
+// The pixel rectangle of 8 x th tile `tile` of a launch's compacted rows, as
+// the kernel's prologue takes it: the first and last pixel centres (columns;
+// image rows -- with interleaved row tiles, tile_step > 0, compacted row r is
+// image row row_begin + (tile_first + (r / row_tile) tile_step) row_tile + r %
+// row_tile).  false: the tile holds no pixel.
+struct TlFrame {
+  int width, rows_out, row_begin, row_tile, tile_first, tile_step;
+};
+inline bool tl_rect(const TlFrame& f, int th, int tile, float* x0, float* x1, float* y0, float* y1) {
+  const int tiles_x = (f.width + 7) / 8;
+  const int tby = tile / tiles_x, tbx = tile - tby * tiles_x;
+  const int qx0 = tbx * 8, qy0 = tby * th;
+  const int vw = f.width - qx0 < 8 ? f.width - qx0 : 8, vh = f.rows_out - qy0 < th ? f.rows_out - qy0 : th;
+  if (vw <= 0 || vh <= 0) return false;
+  auto image_row = [&](int r) {
+    if (f.tile_step > 0) {
+      const int t = r / f.row_tile;
+      return f.row_begin + (f.tile_first + t * f.tile_step) * f.row_tile + (r - t * f.row_tile);
+    }
+    return f.row_begin + r;
+  };
+  *x0 = static_cast<float>(qx0), *x1 = static_cast<float>(qx0 + vw - 1);
+  *y0 = static_cast<float>(image_row(qy0)), *y1 = static_cast<float>(image_row(qy0 + vh - 1));
+  return true;
+}
+
+// The prologue's pass on the host (rt_tile_bodies_host): tile_keeps over every
+// body of every leaf record -- pairs as bvh_build leaves them, 8 floats per
+// pair (x0 x1 y0 y1 z0 z1 w0 w1), two pairs a record; pidx their body indices.
+// bodies / slots (nullable) receive the first `cap` kept bodies' indices and
+// places 4 record + j, in record order; returns how many are kept.
+inline int tl_host_bodies(const TileRays& t, const float* pairs, const int* pidx, int n_rec, int* bodies, int* slots,
+                          int cap) {
+  int kept = 0;
+  for (int k = 0; k < n_rec; ++k)
+    for (int j = 0; j < 4; ++j) {
+      const int pr = 2 * k + (j >> 1), e = j & 1;
+      const float* p = pairs + 8 * static_cast<long>(pr);
+      if (!tile_keeps(t, p[e], p[2 + e], p[4 + e], p[6 + e])) continue;
+      if (kept < cap) {
+        if (bodies) bodies[kept] = pidx[2 * pr + e];
+        if (slots) slots[kept] = 4 * k + j;
+      }
+      ++kept;
+    }
+  return kept;
+}
+
+// rt_tile_bodies_host's body (and tools/tile_bodies_check.cpp's subject): the
+// 4-body tree of the scene as rt_scene_upload builds it, the tile's rectangle,
+// the pass above.  sphere: n x (cx, cy, cz, r); cam: KArgs::cam's 18 floats.
+inline int tl_host_tile(const float* sphere, int n, bool sah, const float* cam, int defocus, const TlFrame& f, int tile,
+                        int* bodies, int* slots, int cap) {
+  float x0, x1, y0, y1;
+  if (!tl_rect(f, 8, tile, &x0, &x1, &y0, &y1)) return 0;
+  BvhHost tree;
+  bvh_build(sphere, n, &tree, 4, sah);
+  const TileRays t = tile_rays(cam, defocus, x0, x1, y0, y1);
+  return tl_host_bodies(t, tree.pairs.data(), tree.pidx.data(), static_cast<int>(tree.pairs.size() / 16), bodies, slots, cap);
 }
 
 }  // namespace rtclj

@@ -275,7 +275,7 @@ static const bool g_timeline = [] {
 #endif
 // stats builds: per device, u64[kDbg] event counters and the u64[4 * kDbgWaves]
 // wave timeline, allocated on that device at its first stats launch
-constexpr int kDbg = 32;
+constexpr int kDbg = 40;   // (rt_debug_stats reads the first 32, rt_debug_stats_ext all)
 constexpr int kDbgDevices = 64;
 static std::mutex g_dbg_mu;
 static unsigned long long* g_dbg[kDbgDevices] = {};
@@ -1085,11 +1085,11 @@ extern "C" int rt_prepare(int device, double* out_ms4) {
 }
 
 // Stats builds read-back: sums and clears the kDbg debug counters of every
-// device that ran a stats launch.
-extern "C" int rt_debug_stats(uint64_t* out32) {
+// device that ran a stats launch; the first n of them go to out.
+static int debug_stats(uint64_t* out, int n, const char* who) {
   clear_error();
-  if (!out32) return set_error(RT_E_ARG, "rt_debug_stats: NULL");
-  for (int i = 0; i < kDbg; ++i) out32[i] = 0;
+  if (!out || n < 0 || n > kDbg) return set_error(RT_E_ARG, std::string(who) + ": NULL, or a count outside 0 .. 40");
+  for (int i = 0; i < n; ++i) out[i] = 0;
   std::lock_guard<std::mutex> lk(g_dbg_mu);
   for (int d = 0; d < kDbgDevices; ++d) {
     if (!g_dbg[d]) continue;
@@ -1098,10 +1098,12 @@ extern "C" int rt_debug_stats(uint64_t* out32) {
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(v, g_dbg[d], sizeof v, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemset(g_dbg[d], 0, sizeof v));
-    for (int i = 0; i < kDbg; ++i) out32[i] += v[i];
+    for (int i = 0; i < n; ++i) out[i] += v[i];
   }
   return RT_OK;
 }
+extern "C" int rt_debug_stats(uint64_t* out32) { return debug_stats(out32, 32, "rt_debug_stats"); }
+extern "C" int rt_debug_stats_ext(uint64_t* out, int n) { return debug_stats(out, n, "rt_debug_stats_ext"); }
 
 // Steals of the launches on (ds, stream) since the last call: out2 =
 // {steals, samples stolen}; waits for the stream, then clears them.

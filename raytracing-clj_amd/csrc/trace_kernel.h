@@ -562,9 +562,12 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
   // wave-level events of the loop's bookkeeping: colour sums
   // added, refills, batch claims, drain-phase checks (batches spent)
   uint64_t st_sums = 0, st_refill = 0, st_claim = 0, st_drain = 0;
-  // PRE, wave-level: prelude trips and the lanes in them, the trips' leaf
-  // passes and exact passes (counted in st_leafw / st_consw too), and the walk
-  // segments entered in an iteration that ran a trip
+  // PRE, wave-level: prelude trips and the lanes in them, the trips' list
+  // passes and per-body exact steps (counted in st_leafw / st_consw too), the
+  // walk segments entered in an iteration that ran a trip.  (st_pre_leaf's
+  // high half: the bodies those passes tested, four or two a pass, a pass's
+  // repeats included -- a lane's counts stay far below 2^32; one variable
+  // more would reorder the other statistics kernels' set-up)
   uint64_t st_pre = 0, st_pre_lanes = 0, st_pre_leaf = 0, st_pre_exact = 0, st_pre_walk = 0;
   uint64_t st_c_cam = 0, st_c_scan = 0, st_c_shade = 0, st_c_acc = 0, st_ts = 0;  // clock split
   uint64_t st_t0 = 0;
@@ -826,20 +829,22 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
   if constexpr (kCompactPx) {
     if (threadIdx.x < NPX * 3 / 4) s_carry[threadIdx.x] = 0u;
   }
-  // The tile's list (PRE): the leaf records, big bodies' included, that hold a
-  // body some camera ray of the unit's pixel rectangle can reach
-  // (tile_list.h) -- as their LDS addresses, u16, behind a count word: 32
-  // bytes, all that variant 22's image leaves of a seventh of a CU's LDS (a
-  // copy of the surviving bodies would be 80 bytes per four).  A record is
-  // listed whole: its other bodies are bodies of the scene, and a test more
-  // never changes the closest hit.  More than kTlMax records, or a record
-  // above 64 KB: the count says so, and the tile's camera segments take the walk.
-  constexpr int kTlMax = 14;
+  // The tile's list (PRE): the bodies, big ones included, that some camera ray
+  // of the unit's pixel rectangle can reach (tile_list.h) -- each as its leaf
+  // record's LDS address, u16, with its slot in the record in the two low bits
+  // (tl_entry), behind a count word: 32 bytes, all that variant 22's image
+  // leaves of a seventh of a CU's LDS (a copy of the surviving bodies would be
+  // 80 bytes per four).  In any order: the acceptance is order-independent.
+  // More than kTlMax bodies, or a record above 64 KB: the count says so, and
+  // the tile's camera segments take the walk.
+  static_assert(kTlRecBytes == kLeafRecBytes, "tile_list.h's record is the leaf record");
   unsigned* s_tl = nullptr;
   if constexpr (PRE) {
     __shared__ unsigned tl_words[8];
     s_tl = tl_words;
-    if (threadIdx.x == 0) tl_words[0] = 0u;
+    // (the records lie whole float4s behind s_geo, declared 16-aligned: were
+    // the base ever not 4-aligned, the slot bits would not be free -- no list)
+    if (threadIdx.x == 0) tl_words[0] = (lds_addr(s_geo) & 3u) ? static_cast<unsigned>(kTlMax + 1) : 0u;
   }
   __syncthreads();
   if constexpr (PRE) {
@@ -853,16 +858,13 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
       const unsigned rec0 = lds_addr(s_geo) + static_cast<unsigned>(a.bvh_off_pairs >> 4) * 16u;
       for (int i = static_cast<int>(threadIdx.x); i < n_rec; i += NT) {
         const unsigned ra = rec0 + static_cast<unsigned>(i) * kLeafRecBytes;
-        bool any = false;
 #pragma unroll 1
         for (unsigned b = 0; b < 4; ++b) {
           const f4v g = *(LdsF4)(uintptr_t)(ra + 16u * b);
-          any = any || tile_keeps(tr, g.x, g.y, g.z, g.w);
-        }
-        if (any) {
+          if (!tile_keeps(tr, g.x, g.y, g.z, g.w)) continue;
           const unsigned slot = atomicAdd(&s_tl[0], ra > 0xffffu ? static_cast<unsigned>(kTlMax + 1) : 1u);
           if (slot < static_cast<unsigned>(kTlMax))
-            reinterpret_cast<unsigned short*>(s_tl + 1)[slot] = static_cast<unsigned short>(ra);
+            reinterpret_cast<unsigned short*>(s_tl + 1)[slot] = static_cast<unsigned short>(tl_entry(ra, b));
         }
       }
     }
@@ -1055,6 +1057,13 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
   constexpr int kPreMin = RTCLJ_PRE_MIN;
 #else
   constexpr int kPreMin = 16;
+#endif
+  // The list's 2-body pass for a remainder of one or two bodies (off under
+  // -DRTCLJ_TL_PASS4_ONLY, the A/B build of DESIGN.md §8.1's measurement)
+#ifdef RTCLJ_TL_PASS4_ONLY
+  constexpr bool kTlPass2 = false;
+#else
+  constexpr bool kTlPass2 = true;
 #endif
   bool pre_listed = false;   // PRE: the tile has a list (wave-uniform; set per iteration)
   auto segment = [&](auto seg_tag, SegHit& hit) __attribute__((always_inline)) {
@@ -1269,7 +1278,9 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
       auto consider_tie = [&](float h, float disc, int s) {
         if constexpr (STATS) st_fl += 3;   // sqrt, h -/+ sq
         if constexpr (STATS) ++st_blk_lanes;
-        const float sq = (s == last) ? fabsf(h) : sqrt_rn(disc);
+        // (LIST: a trip's rays are camera rays, last == -1 and no body's
+        // index: the self-hit guard's compare and select drop out)
+        const float sq = (!LIST && s == last) ? fabsf(h) : sqrt_rn(disc);
         const float tn = h - sq;
         const float t = tn > tmin ? tn : h + sq;
         // (t, index) < (best_t, best) lexicographically as one 64-bit compare:
@@ -1517,10 +1528,74 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
         hit1 = pad_meets(tn1, tf1, tmin, best_t);
       };
       if constexpr (LIST) {
-        // the tile's list: a wave-uniform loop of leaf passes, no walk
+        // The tile's list: a wave-uniform loop of list passes over the entries,
+        // held in scalar registers, no walk.  A pass tests up to four listed
+        // bodies (two when one or two are left: most of C1's tiles list no
+        // more) -- each body's address decoded on the scalar side, its
+        // (h, c, disc) and candidate bit by the leaf pass's operations, the
+        // same bits.  Then per body, if any lane holds its bit, those lanes
+        // run the exact step from the pass's own registers: the body is the
+        // same in every lane, so nothing is re-read or recomputed and no lane
+        // picks a candidate.  A pass's unused slots repeat its first body,
+        // which the strict (t, index) compare rejects: no pad body, no LDS.
         RT_MARKL("tile_list");
         const int n_list = min(sgpr(static_cast<int>(s_tl[0])), kTlMax);   // (<= kTlMax here: the prelude's condition)
-        for (int b = 0; b < n_list; ++b) leaf(static_cast<int>(reinterpret_cast<const unsigned short*>(s_tl + 1)[b]));
+        auto list_pass = [&](auto nb_tag, const unsigned (&e)[4]) {
+          constexpr int NB = decltype(nb_tag)::value;
+          if constexpr (NB == 4) RT_MARKL("list_pass4");
+          else RT_MARKL("list_pass2");
+          if constexpr (STATS) {
+            ++st_blk;
+            const uint64_t ex = __builtin_amdgcn_read_exec();
+            if (lane == __ffsll(static_cast<long long>(ex)) - 1) {
+              ++st_leafw;
+              st_pre_leaf += 1ull + (static_cast<uint64_t>(NB) << 32);
+            }
+          }
+          float h[NB], disc[NB];
+          unsigned nc[NB];
+          int sidx[NB];
+#pragma unroll
+          for (int s = 0; s < NB; ++s) {
+            if constexpr (STATS) st_fl += 16;
+            const f4v g = *(LdsF4)(uintptr_t)tl_body_addr(e[s]);
+            sidx[s] = *(const int __attribute__((address_space(3)))*)(uintptr_t)tl_index_addr(e[s]);
+            const float ocx = g.x - o_xy.x, ocy = g.y - o_xy.y, ocz = g.z - o_zux.x;
+            h[s] = fmaf(u_yz.y, ocz, fmaf(u_yz.x, ocy, o_zux.y * ocx));
+            const float c = fmaf(ocx, ocx, fmaf(ocz, ocz, fmaf(ocy, ocy, g.w)));
+            disc[s] = fmaf(h[s], h[s], -c);
+            // (bit 31: a candidate, as the leaf pass's nc)
+            nc[s] = __builtin_amdgcn_bitop3_b32(__float_as_uint(disc[s]), __float_as_uint(h[s]), __float_as_uint(c), 0x0b);
+          }
+#pragma unroll
+          for (int s = 0; s < NB; ++s) {
+            if (static_cast<int>(nc[s]) < 0) {
+              RT_MARKL("list_exact");
+              if constexpr (STATS) {
+                const uint64_t ex = __builtin_amdgcn_read_exec();
+                if (lane == __ffsll(static_cast<long long>(ex)) - 1) {
+                  ++st_consw;
+                  ++st_pre_exact;
+                }
+              }
+              consider_tie(h[s], disc[s], sidx[s]);
+            }
+          }
+          RT_MARKL("tile_list");
+        };
+        for (int b = 0; b < n_list; b += 4) {
+          const int listed = n_list - b;
+          // entries b .. b + 3: two words of the list (the last pass's second
+          // word may lie past the entries: read inside the list, unused)
+          const unsigned w0 = static_cast<unsigned>(sgpr(static_cast<int>(s_tl[1 + (b >> 1)])));
+          const unsigned w1 = static_cast<unsigned>(sgpr(static_cast<int>(s_tl[min(2 + (b >> 1), 7)])));
+          const unsigned e0 = w0 & 0xffffu;
+          const unsigned e[4] = {e0, listed > 1 ? w0 >> 16 : e0, listed > 2 ? w1 & 0xffffu : e0, listed > 3 ? w1 >> 16 : e0};
+          if (kTlPass2 && listed <= 2)
+            list_pass(std::integral_constant<int, 2>{}, e);
+          else
+            list_pass(std::integral_constant<int, 4>{}, e);
+        }
       } else {
       // the big bodies' leaves first: every lane, so a wave-uniform loop (their
       // hits, e.g. the ground, then cull the tree)
@@ -2081,9 +2156,10 @@ __global__ __launch_bounds__(64 * NW, min_waves(SCAN, STATS, NW)) void trace_ker
     if (a.dbg && st_pre) {
       atomicAdd(&a.dbg[27], static_cast<unsigned long long>(st_pre));
       atomicAdd(&a.dbg[28], static_cast<unsigned long long>(st_pre_lanes));
-      atomicAdd(&a.dbg[29], static_cast<unsigned long long>(st_pre_leaf));
+      atomicAdd(&a.dbg[29], static_cast<unsigned long long>(st_pre_leaf & 0xffffffffull));
       atomicAdd(&a.dbg[30], static_cast<unsigned long long>(st_pre_exact));
       atomicAdd(&a.dbg[31], static_cast<unsigned long long>(st_pre_walk));
+      atomicAdd(&a.dbg[32], static_cast<unsigned long long>(st_pre_leaf >> 32));
     }
     if (a.dbg && st_blk) {
       atomicAdd(&a.dbg[3], static_cast<unsigned long long>(st_blk));

@@ -128,7 +128,7 @@ constexpr Traits kTraits[kVariants] = {
     kNone,
     // (22 without the tile list: camera segments through the walk)
     {8, 256, 0, true, false, BUILD_PRODUCT, WALK_BVH, 1, true, 1, 0},     // 30
-    // (22's statistics build, the prelude's counters included: rt_debug_stats 27-31)
+    // (22's statistics build, the prelude's counters included: rt_debug_stats 27-31, rt_debug_stats_ext 32)
     {8, 256, 0, true, true, BUILD_DIAG, WALK_BVH, 1, true, 1, 0},         // 31 = 22 + stats
 };
 // does a build (diag: the diagnostic library) carry variant v?

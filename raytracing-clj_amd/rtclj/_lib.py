@@ -305,6 +305,9 @@ SIGNATURES = {
     "rt_launch_occupancy": (C.c_int, [C.c_void_p, C.POINTER(rt_params), C.POINTER(C.c_int)]),
     "rt_set_schedule": (C.c_int, [C.c_int]),
     "rt_debug_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
+    "rt_debug_stats_ext": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
+    "rt_tile_bodies_host": (C.c_int, [C.POINTER(rt_scene), C.POINTER(rt_camera), C.POINTER(rt_params), C.c_int,
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]),
     "rt_debug_waves": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.c_size_t]),
     "rt_steal_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "rt_export_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -339,7 +342,8 @@ ADDITIVE = {"rt_prepare", "rt_render_u8", "rt_quantize_device", "rt_render_submi
             "rt_scene_update", "rt_tree_build_host", "rt_tree_refit_host", "rt_tree_cost_host", "rt_scene_tree_info",
             "rt_scene_tree_read", "rt_schedule_read", "rt_schedule_sort", "rt_camera_coarsen", "rt_upsample",
             "rt_upsample_host", "rt_launch_feat_chain", "rt_feat_chain_host", "rt_feat_chain_occupancy",
-            "rt_budget_trace_fused", "rt_budget_units_host", "rt_budget_units_read", "rt_budget_list_read"}
+            "rt_budget_trace_fused", "rt_budget_units_host", "rt_budget_units_read", "rt_budget_list_read",
+            "rt_debug_stats_ext", "rt_tile_bodies_host"}
 
 RT_FEAT_CHANNELS = 8   # rt_feat_resolve's floats per pixel: albedo rgb, normal xyz, depth, coverage
 

@@ -1010,6 +1010,20 @@ def budget_units_host(tile_list, mult, half: int, max_mult: int, library=None) -
     return out[:n].copy()
 
 
+def tile_bodies_host(scene, cam, params, tile: int, library=None):
+    """rt_tile_bodies_host (include/rt.h): the bodies variant 22's prologue lists
+    for 8 x 8 tile `tile` of the launch (cam, params: an rt_params), as (body
+    indices, places 4 * record + slot), int32 each, in record order.  More than
+    14 bodies: the kernel makes no list for the tile."""
+    dll = library if library is not None else lib
+    cap = max(int(scene.c.n), 1)
+    bodies, slots = np.empty(cap, np.int32), np.empty(cap, np.int32)
+    n = dll.rt_tile_bodies_host(C.byref(scene.c), C.byref(cam), C.byref(params), int(tile), i32ptr(bodies), i32ptr(slots), cap)
+    if n < 0:
+        raise RTError(n, dll.rt_last_error().decode(errors="replace"))
+    return bodies[:n].copy(), slots[:n].copy()
+
+
 class Budget:
     """A budgeted frame on an uploaded scene's device (rt_budget, include/rt.h):
     two half accumulators traced at a per-tile multiple of half_spp samples.

@@ -43,6 +43,10 @@ EXCESS_TO = "tree_setup"
 # at the address list's): what a larger copy holds goes to the list loop's block
 PRE = "pre_"
 PER_COPY += tuple(PRE + b for b in PER_COPY)
+# the body list's trip (the list passes of four and of two bodies,
+# "pre_list_pass4" / "pre_list_pass2", and after each the exact step per body,
+# "pre_list_exact": six copies, one step runs one)
+PER_COPY += (PRE + "list_exact",)
 PRE_EXCESS_TO = PRE + "tile_list"
 TAIL_SPLIT = re.compile(r"v_bitop3_b32.*bitop3:0xa8")
 
@@ -145,6 +149,12 @@ def main():
             ev.update({PRE + b: tr for b in ("iteration", "camera", "setup", "tile_list", "hit", "compaction")})
             ev.update({PRE + "leaf": pw["prelude_leaf_passes"], PRE + "node": pw["prelude_leaf_passes"]})
             ev.update({PRE + b: pw["prelude_exact_passes"] for b in ("exact", "exact_accept", "exact_tail")})
+            # the body list: passes of four bodies and of two, from the passes and
+            # the bodies they tested (4 p4 + 2 p2); an exact step per body and pass
+            if "prelude_bodies_tested" in pw:
+                p4 = max((pw["prelude_bodies_tested"] - 2.0 * pw["prelude_leaf_passes"]) / 2.0, 0.0)
+                ev.update({PRE + "list_pass4": p4, PRE + "list_pass2": pw["prelude_leaf_passes"] - p4,
+                           PRE + "list_exact": pw["prelude_exact_passes"]})
             # (the walk's once-per-iteration blocks: the iterations that reach the walk)
             walk = pw.get("walk_segments", 1.0)
             for b in ("iteration", "setup", "bigleaf", "tree_setup", "hit", "compaction"):

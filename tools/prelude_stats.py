@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """The statistics build of variant 22 (variant 31, the diagnostic library) on
 the C1 frame: one warm-up launch, one counted launch, and the wave-level events
-per segment call -- the walk's and the prelude's (rt_debug_stats 27-31:
-prelude trips, lanes in them, their leaf and exact passes, walk segments
-entered in an iteration that ran a trip).  Under the tile list a wave
+per segment call -- the walk's and the prelude's (rt_debug_stats_ext 27-32:
+prelude trips, lanes in them, their list passes and per-body exact steps, walk
+segments entered in an iteration that ran a trip, the bodies the list passes
+tested: four or two a pass).  Under the tile list a wave
 iteration is a walk segment, a prelude trip or both, shaded in one tail; a walk
 and a trip are each one search of the segment's text and one count of
 rt_debug_stats[0]; the rates below are per such call.
@@ -54,13 +55,15 @@ def main():
         out = torch.empty(h * w * 3, dtype=torch.float32, device="cuda")
         cnt = torch.zeros(2, dtype=torch.int64, device="cuda")
         s = torch.cuda.current_stream()
-        d = (C.c_uint64 * 32)()
+        d = (C.c_uint64 * 40)()
         for timed in (False, True):
             cnt.zero_()
             check(lib.rt_launch(ds, C.byref(cam), C.byref(p), C.c_void_p(out.data_ptr()), C.c_void_p(cnt.data_ptr()),
                                 C.c_void_p(s.cuda_stream)))
             torch.cuda.synchronize()
-            check(lib.rt_debug_stats(d))   # (the warm-up's counts read and cleared)
+            # (the warm-up's counts read and cleared; a build from before the list
+            # passes has 32 counters)
+            check(lib.rt_debug_stats_ext(d, 40) if hasattr(lib, "rt_debug_stats_ext") else lib.rt_debug_stats(d))
         segs, smp = (float(x) for x in cnt.cpu().tolist())
     finally:
         lib.rt_set_variant(old)
@@ -78,12 +81,14 @@ def main():
           "leaf_passes": d[12] / wi, "exact_passes": d[13] / wi,
           "prelude_trips": trips / wi, "prelude_lanes": d[28] / max(trips, 1),
           "prelude_leaf_passes": d[29] / wi, "prelude_exact_passes": d[30] / wi,
+          "prelude_bodies_tested": d[32] / wi,
           "walk_segments": (wi - trips) / wi, "walk_segments_after_a_trip": d[31] / wi,
           "wave_iterations": (wi - d[31]) / wi}
     line = {"workload": f"cover({a.grid}) {w}x{h} spp {a.spp} depth {a.depth}", "segments": segs, "samples": smp,
             "occupancy": list(occ), "raw": d,
             "prelude": {"trips_per_sample": trips / smp, "lanes_per_trip": d[28] / max(trips, 1),
                         "leaf_passes_per_trip": d[29] / max(trips, 1), "exact_passes_per_trip": d[30] / max(trips, 1),
+                        "bodies_tested_per_trip": d[32] / max(trips, 1),
                         "walk_segments_per_sample": (wi - trips) / smp,
                         "share_of_walk_segments_after_a_trip": d[31] / max(wi - trips, 1)},
             "stats_build": {"stats_variant": STATS, "flops_per_segment": d[18] / segs, "segments_per_sample": segs / smp,

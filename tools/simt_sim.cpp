@@ -32,6 +32,13 @@
 //          trip costs CPRE (default 330, close to the whole outer block) plus
 //          the list's leaf passes and the exact passes of the trip's busiest
 //          lane (its camera segment's candidates as the walk met them).
+//   BLIST=1 (with PRE; round 24): the list names bodies, not
+//          leaf records (INFL is not applied): a trip runs ceil(n / 4) list
+//          passes over the tile's n kept bodies -- passes of four (CLP4,
+//          default 72) and, for a remainder of one or two, one of two (CLP2,
+//          default 38) -- and an exact step per body some lane holds a
+//          candidate of (CLX, default 24), priced for the trip's busiest
+//          lane's candidates: a lower bound of the bodies with one.
 //   PREK=K (with PRE; round 21): the gate on the trips -- a
 //          trip runs only when at least K lanes hold an unstarted sample, or
 //          no lane holds a live path, or the pool is spent; otherwise those
@@ -94,6 +101,8 @@ static int g_charge_rej = 0;   // policies 0/1: add the rejection trips to the c
 static int g_pre = 0;          // PRE=T: prelude trips per wave iteration (0: none)
 static double g_infl = 1.0, C_PRE = 330;   // INFL, CPRE
 static int g_prek = 0;         // PREK=K: the gate on the prelude's trips (0: none)
+static int g_blist = 0;        // BLIST=1: the list names bodies; its passes' and exact steps' costs
+static double C_LP4 = 72, C_LP2 = 38, C_LX = 24;
 static int g_tail = 0;         // TAIL=1: the rotated iteration -- walk, miss exit, trip, one tail
 static double C_TAIL = 140, C_MISS = 40;   // CTAIL, CMISS
 static double g_pre_trips = 0, g_pre_lanes = 0, g_list_len = 0, g_list_tiles = 0, g_list_max = 0;
@@ -616,6 +625,7 @@ static void run_tile(const Ctx& C, int tx, int ty, int policy, int key_mode, Res
   if (policy == 0) {
     // the tile's list (PRE): tile_list.h's cull of every body
     int list_passes = 0;
+    double list_cost = 0, c_pre_exact = C_EXACT;
     if (g_pre) {
       const float* cam = C.cam.center;   // center, p00, du, dv, disk_u, disk_v: contiguous
       const TileRays tr = tile_rays(cam, C.cam.defocus, float(tx * 8), float(tx * 8 + 7), float(ty * g_tile_h),
@@ -626,6 +636,13 @@ static void run_tile(const Ctx& C, int tx, int ty, int policy, int key_mode, Res
         nb += tile_keeps(tr, sp[0], sp[1], sp[2], -(sp[3] * sp[3]));
       }
       list_passes = int(std::ceil(nb * g_infl / 4.0));
+      list_cost = C_LEAF * list_passes;
+      if (g_blist) {
+        const int p2 = nb % 4 == 1 || nb % 4 == 2, p4 = nb / 4 + (nb % 4 == 3);
+        list_passes = p4 + p2;
+        list_cost = C_LP4 * p4 + C_LP2 * p2;
+        c_pre_exact = C_LX;
+      }
       g_list_len += nb;
       g_list_tiles += 1;
       g_list_max = std::max(g_list_max, double(nb));
@@ -685,7 +702,7 @@ static void run_tile(const Ctx& C, int tx, int ty, int policy, int key_mode, Res
             max_c = std::max(max_c, nc);
             ++n_hold;
           }
-          c += C_PRE - C_TAIL + C_LEAF * list_passes + C_EXACT * max_c;
+          c += C_PRE - C_TAIL + list_cost + c_pre_exact * max_c;
           g_pre_trips += 1;
           g_pre_lanes += n_fresh;
         }
@@ -729,7 +746,7 @@ static void run_tile(const Ctx& C, int tx, int ty, int policy, int key_mode, Res
             }
           }
           if (!n_in) break;
-          const double c = C_PRE + C_LEAF * list_passes + C_EXACT * max_c;
+          const double c = C_PRE + list_cost + c_pre_exact * max_c;
           wc[w] += c;
           R.cost += c;
           g_pre_trips += 1;
@@ -944,6 +961,10 @@ int main(int argc, char** argv) {
   if (std::getenv("INFL")) g_infl = std::atof(std::getenv("INFL"));
   if (std::getenv("CPRE")) C_PRE = std::atof(std::getenv("CPRE"));
   if (std::getenv("PREK")) g_prek = std::atoi(std::getenv("PREK"));
+  if (std::getenv("BLIST")) g_blist = std::atoi(std::getenv("BLIST"));
+  if (std::getenv("CLP4")) C_LP4 = std::atof(std::getenv("CLP4"));
+  if (std::getenv("CLP2")) C_LP2 = std::atof(std::getenv("CLP2"));
+  if (std::getenv("CLX")) C_LX = std::atof(std::getenv("CLX"));
   if (std::getenv("TAIL")) g_tail = std::atoi(std::getenv("TAIL"));
   if (std::getenv("CTAIL")) C_TAIL = std::atof(std::getenv("CTAIL"));
   if (std::getenv("CMISS")) C_MISS = std::atof(std::getenv("CMISS"));

@@ -30,6 +30,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <random>
 #include <string>
 #include <vector>
@@ -261,6 +262,7 @@ void c1_lists(std::FILE* out) {
   const int n_rec = static_cast<int>(tree.pairs.size() / 16);
   long tiles = 0, sum_b = 0, sum_r = 0, over_b = 0, over_r = 0, empty = 0;
   int max_b = 0, max_r = 0;
+  std::vector<long> hist(16, 0);   // tiles by kept bodies, 15: 15 or more (no list)
   for (int ty = 0; ty * 8 < h; ++ty)
     for (int tx = 0; tx * 8 < w; ++tx) {
       const int x0 = tx * 8, x1 = std::min(w, x0 + 8) - 1, y0 = ty * 8, y1 = std::min(h, y0 + 8) - 1;
@@ -281,13 +283,96 @@ void c1_lists(std::FILE* out) {
       max_b = std::max(max_b, nb), max_r = std::max(max_r, nr);
       over_b += nb > 16, over_r += nr > 15;
       empty += nb == 0;
+      ++hist[std::min(nb, 15)];
     }
   std::fprintf(out,
                "\"c1\": {\"tiles\": %ld, \"bodies\": %d, \"records\": %d, \"mean_bodies\": %.3f, \"max_bodies\": %d, "
                "\"share_over_16_bodies\": %.5f, \"mean_records\": %.3f, \"max_records\": %d, \"share_over_15_records\": %.5f, "
-               "\"share_empty\": %.4f}",
+               "\"share_empty\": %.4f, \"tiles_by_bodies\": [",
                tiles, n, n_rec, static_cast<double>(sum_b) / tiles, max_b, static_cast<double>(over_b) / tiles,
                static_cast<double>(sum_r) / tiles, max_r, static_cast<double>(over_r) / tiles, static_cast<double>(empty) / tiles);
+  for (size_t i = 0; i < hist.size(); ++i) std::fprintf(out, "%s%ld", i ? ", " : "", hist[i]);
+  std::fprintf(out, "]}");
+}
+
+// `tile_list_check bodies`: tl_host_tile, the body of rt_tile_bodies_host (the
+// sanitizer build lib/tile_bodies_check runs this mode).  Over random finite
+// scenes, cameras and launches (partial border tiles, interleaved row tiles),
+// every tile: the kept bodies are exactly those tile_keeps keeps of the
+// scene's (centre, -r * r in fp32), body by body, each once; every output
+// array is a heap block of exactly its size, `cap` at, below and above the
+// count; a slot's entry (tl_entry over a 16-aligned record base) decodes back
+// to the body's and the index's address and fits 16 bits.  One JSON line.
+int bodies_mode() {
+  std::mt19937 g(20241021u);
+  std::uniform_real_distribution<double> U(0.0, 1.0);
+  auto sym = [&](double a) { return a * (2.0 * U(g) - 1.0); };
+  long bad = 0, tiles = 0, kept_sum = 0, entries = 0, over14 = 0, empty = 0, stepped = 0;
+  auto expect = [&](bool ok, const char* what) {
+    if (!ok && bad++ < 5) std::fprintf(stderr, "tile_list_check bodies: %s\n", what);
+  };
+  for (int cs = 0; cs < 60; ++cs) {
+    const int w = 9 + static_cast<int>(U(g) * 40), h = 5 + static_cast<int>(U(g) * 30);
+    const int n = static_cast<int>(U(g) * U(g) * 90);   // 0 included
+    const double lf[3] = {sym(8), sym(3) + 1.0, 6.0 + sym(2)}, la[3] = {sym(1), sym(1), sym(1)};
+    float cam[18];
+    int defocus;
+    make_cam(w, h, 15.0 + 50.0 * U(g), lf, la, cs % 3 ? 0.5 + 3.0 * U(g) : 0.0, 6.0, cam, &defocus);
+    std::vector<float> sph(4 * static_cast<size_t>(std::max(n, 1)));
+    for (int i = 0; i < n; ++i) {
+      const bool twin = i > 0 && U(g) < 0.1;   // coincident bodies: each is listed
+      for (int k = 0; k < 3; ++k) sph[4 * i + k] = twin ? sph[4 * (i - 1) + k] : static_cast<float>(sym(k == 1 ? 1.5 : 4.0));
+      sph[4 * i + 3] = twin ? sph[4 * (i - 1) + 3] : static_cast<float>(U(g) < 0.05 ? 50.0 + 500.0 * U(g) : 0.02 + 0.7 * U(g));
+    }
+    TlFrame f{w, h, 0, 8, 0, 0};
+    if (cs % 4 == 3) {   // the odd row tiles of height T from row_begin
+      const int T = cs % 8 == 3 ? 1 : 8, rb = static_cast<int>(U(g) * 3), span = h - rb, nt = (span + T - 1) / T;
+      int rows = 0;
+      for (int t = 1; t < nt; t += 2) rows += std::min(T, span - t * T);
+      f = TlFrame{w, rows, rb, T, 1, 2};
+      ++stepped;
+    }
+    const int n_tiles = ((w + 7) / 8) * ((f.rows_out + 7) / 8);
+    for (int tile = 0; tile <= n_tiles; ++tile) {   // (one past the frame: no pixels, 0)
+      float x0, x1, y0, y1;
+      const bool has = tl_rect(f, 8, tile, &x0, &x1, &y0, &y1);
+      std::vector<int> want;
+      if (has) {
+        const TileRays t = tile_rays(cam, defocus, x0, x1, y0, y1);
+        for (int i = 0; i < n; ++i) {
+          const float r = sph[4 * i + 3];
+          if (tile_keeps(t, sph[4 * i], sph[4 * i + 1], sph[4 * i + 2], -(r * r))) want.push_back(i);
+        }
+      }
+      const int cnt = static_cast<int>(want.size());
+      for (int cap : {cnt, cnt > 0 ? cnt - 1 : 0, cnt + 3}) {
+        std::unique_ptr<int[]> bodies(new int[cap]), slots(new int[cap]);
+        for (int i = 0; i < cap; ++i) bodies[i] = slots[i] = -7;
+        const int got = tl_host_tile(sph.data(), n, true, cam, defocus, f, tile, bodies.get(), slots.get(), cap);
+        expect(got == cnt, "the count differs from tile_keeps body by body");
+        std::vector<int> have(bodies.get(), bodies.get() + std::min(cap, cnt));
+        for (int i = std::min(cap, cnt); i < cap; ++i) expect(bodies[i] == -7 && slots[i] == -7, "written past the count");
+        if (cap >= cnt) {
+          std::sort(have.begin(), have.end());
+          expect(have == want, "the kept bodies differ from tile_keeps body by body");
+          for (int i = 0; i < cnt; ++i) {
+            const unsigned base = 16u * static_cast<unsigned>(U(g) * 200), rec = base + kTlRecBytes * static_cast<unsigned>(slots[i] >> 2);
+            const unsigned j = static_cast<unsigned>(slots[i] & 3), e = tl_entry(rec, j);
+            expect(slots[i] >= 0 && e <= 0xffffu, "a slot outside the records, or an entry above 16 bits");
+            expect(tl_body_addr(e) == rec + 16u * j && tl_index_addr(e) == rec + 64u + 4u * j, "an entry decodes to another address");
+            ++entries;
+          }
+        }
+      }
+      ++tiles;
+      kept_sum += cnt;
+      over14 += cnt > kTlMax;
+      empty += cnt == 0;
+    }
+  }
+  std::printf("{\"tiles\": %ld, \"kept\": %ld, \"entries\": %ld, \"tiles_over_14\": %ld, \"tiles_empty\": %ld, "
+              "\"interleaved_cases\": %ld, \"bad\": %ld}\n", tiles, kept_sum, entries, over14, empty, stepped, bad);
+  return bad == 0 && over14 > 0 && empty > 0 && stepped > 0 ? 0 : 1;
 }
 
 // `tile_list_check count FILE`: the list length of one pixel rectangle of a
@@ -325,6 +410,7 @@ int count_file(const char* path) {
 
 int main(int argc, char** argv) {
   if (argc > 2 && std::string(argv[1]) == "count") return count_file(argv[2]);
+  if (argc > 1 && std::string(argv[1]) == "bodies") return bodies_mode();
   const long want = argc > 1 ? std::atol(argv[1]) : 5000000;   // candidate pairs at least
   std::mt19937 g(20240611u);
   Counts n;
