@@ -1,6 +1,7 @@
 """Scenes for the camera prelude's body list (tests/test_gpu_body_list.py,
-tests/test_tile_bodies_host.py): frames of a few 8 x 8 tiles in which tile t's
-list holds t bodies, as rt_tile_bodies_host (include/rt.h) counts them.
+tests/test_tile_bodies_host.py, tests/test_gpu_list_modes.py): frames of a few
+8 x 8 tiles in which tile t's list holds t bodies, as rt_tile_bodies_host
+(include/rt.h) counts them.
 
 A ground and a mirror ball (the big bodies: the walk's first leaves) under a
 pinhole camera pitched up, so that the top row of tiles sees the sky alone;
@@ -51,8 +52,8 @@ def _scene(sph, kind, mat):
     return R.Scene(np.array(sph, np.float32), np.array(kind, np.int32), np.array(mat, np.float32))
 
 
-def staircase(w, h, scattered=False, first=0):
-    """-> (scene, camera): tile t aims at first + t listed bodies."""
+def staircase(w, h, scattered=False, first=0, aims=None):
+    """-> (scene, camera): tile t aims at first + t listed bodies, or at aims[t]."""
     from rtclj import raytracing as R
     cam = camera(w, h)
     sph, kind, mat = _big()
@@ -60,10 +61,11 @@ def staircase(w, h, scattered=False, first=0):
     c, p00, du, dv = (np.array(v[:], np.float64) for v in (cam.center, cam.p00, cam.du, cam.dv))
     px = float(np.linalg.norm(du))   # a pixel's width on the focus plane (s = 1)
     tiles_x = (w + 7) // 8
+    stair = [(-1, 0.0, 0.0, 0.0)] * len(sph)   # per body: its tile (-1: a big body), fx, fy, s
     for t, b in enumerate(have):
         x0, y0 = 8 * (t % tiles_x), 8 * (t // tiles_x)
         vw, vh = min(8, w - x0), min(8, h - y0)
-        for k in range(max(0, first + t - b)):
+        for k in range(max(0, (first + t if aims is None else aims[t]) - b)):
             kk = 0 if k == 1 else k   # (the second coincides with the first)
             fx = x0 + (vw - 1) / 2 + ((kk % 4) - 1.5) * min(1.0, (vw - 1) / 6)
             fy = y0 + (vh - 1) / 2 + (((kk // 4) % 4) - 1.5) * min(1.0, (vh - 1) / 6)
@@ -72,7 +74,10 @@ def staircase(w, h, scattered=False, first=0):
             sph.append((pt[0], pt[1], pt[2], 0.45 * px * s))
             kind.append((R.RT_LAMBERTIAN, R.RT_METAL, R.RT_DIELECTRIC)[k % 3])
             mat.append(((0.8, 0.3, 0.3, 0.0), (0.7, 0.7, 0.9, 0.1), (0.0, 0.0, 0.0, 1.5))[k % 3])
-    return _scene(sph, kind, mat), cam
+            stair.append((t, fx, fy, s))
+    sc = _scene(sph, kind, mat)
+    sc.stair = dict(w=w, h=h, body=np.array(stair, np.float64))   # (what moved() needs)
+    return sc, cam
 
 
 # the frames of the GPU cases: 40 x 24 (15 whole tiles), 44 x 27 (24 tiles, the
@@ -80,10 +85,59 @@ def staircase(w, h, scattered=False, first=0):
 FRAMES = {"40x24": (40, 24, False, 0), "44x27": (44, 27, True, 0)}
 
 
+# The launch-mode cases (tests/test_gpu_list_modes.py) want nearly every tile of
+# a frame with partial tiles listed.  In "44x27" the spheres of a partial tile
+# stand within three pixels of the neighbouring whole tile and enter its list
+# too, so only ten of its tiles list 1 .. 14 bodies.  "44x27m" is the same frame
+# with an aim per tile: small lists in the partial tiles (last column, last
+# row), the exact lengths 0, 1, 2, 5, 9, 11, 13, 14 in the whole tiles that touch
+# no partial one, and the overflow in the third row and the last row's end.
+MODE_AIMS = {"44x27m": (44, 27, True, (0, 1, 2, 5, 3, 1,
+                                      9, 11, 13, 14, 6, 2,
+                                      20, 20, 20, 20, 20, 8,
+                                      3, 4, 7, 16, 16, 16))}
+MODE_FRAMES = ("40x24", "44x27m")
+
+
 def frame(name):
+    if name in MODE_AIMS:
+        w, h, scattered, aims = MODE_AIMS[name]
+        sc, cam = staircase(w, h, scattered, aims=aims)
+        return sc, cam, w, h
     w, h, scattered, first = FRAMES[name]
     sc, cam = staircase(w, h, scattered, first)
     return sc, cam, w, h
+
+
+def listed_tiles(sc, cam, p):
+    """The tiles of the launch whose camera segments take the list: at most 14 bodies."""
+    return [t for t, (b, _) in enumerate(tile_lists(sc, cam, p)) if len(b) <= 14]
+
+
+def moved_tiles(sc, k):
+    """The tiles whose small spheres moved(sc, k) displaces: every third, from k % 3."""
+    tiles = sorted({int(t) for t in sc.stair["body"][:, 0] if t >= 0})
+    return [t for t in tiles if t % 3 == k % 3]
+
+
+def moved(sc, k):
+    """A copy of a staircase scene in which the small spheres of every third
+    tile (t % 3 == k % 3) stand 8 pixels' width farther along their tile's row,
+    at their own depth: staircase's point with fx + 8 for fx.  They leave their
+    tile's list and enter the next one's (from a row's last tile they leave the
+    frame).  The big bodies stay, and so do radii, kinds and materials:
+    rt_scene_update's condition."""
+    w, h = sc.stair["w"], sc.stair["h"]
+    cam = camera(w, h)
+    c, p00, du, dv = (np.array(v[:], np.float64) for v in (cam.center, cam.p00, cam.du, cam.dv))
+    sph = sc.sphere.copy()
+    for i, (t, fx, fy, s) in enumerate(sc.stair["body"]):
+        if t >= 0 and int(t) % 3 == k % 3:
+            pt = c + s * (p00 + (fx + 8.0) * du + fy * dv - c)
+            sph[i, :3] = pt
+    out = _scene(sph, sc.kind, sc.mat)
+    out.stair = sc.stair
+    return out
 
 
 def describe(lists):
