@@ -769,6 +769,104 @@ int rt_ids_occupancy(const rt_dscene* ds, int* out4);
  * described; a sphere's rotation is invisible with one albedo per body. */
 int rt_body_motion(const rt_scene* cur, const rt_scene* prev, float* out);
 
+/* ---- ray queries: closest hit and occlusion for the caller's rays ---------------
+ * hit-anything (raytracing.clj:33-43) over the sphere ::hit-fn
+ * (hittable.clj:7-31) for rays the caller brings: a pick through the real lens,
+ * line of sight between two bodies, a collision probe, a shadow or occlusion
+ * test -- answered by the search the renderer itself runs, on the tree
+ * rt_scene_upload built and rt_scene_update refits.  The device kernels and
+ * the host entries give the same bits.
+ *
+ * Per ray i (o, t_min, d, t_max), in fp32 with every fma written out:
+ *   1. Set-up, as rt_launch_ids' step 2: |d| = sqrt(fma(d_z, d_z, fma(d_y, d_y,
+ *      d_x * d_x))) and 1 / |d| correctly rounded, u = d * (1 / |d|).  The lower
+ *      bound is tmin = t_min * |d|, one multiplication (t_min = 1e-3f gives
+ *      raytracing.clj:48's t-min as rt_launch_ids computes it, bit for bit); the
+ *      search starts from the best (t_max * |d|, no body), and a root is accepted
+ *      only if it is below the best: t_max is a strict upper bound, +inf is none.
+ *   2. The ray is inactive if a component of o is not finite; if |d| as
+ *      computed is 0 (d is zero, or its square underflows), infinite (also where
+ *      the square overflows) or NaN; if t_min is NaN or negative; if t_max is
+ *      NaN or t_max <= t_min; or if the two products leave no interval
+ *      (t_min * |d| < t_max * |d| fails).  An inactive ray is not searched: its
+ *      record is the "none" record {-1, 0, +inf, +inf, 0, 0, 0, 0}, its
+ *      occlusion byte 0.
+ *   3. The closest hit is rt_launch_ids' step 2 with these bounds: the same body
+ *      test, ties to the lower index.  With last[i] >= 0 the body last[i] takes
+ *      the trace kernel's self-hit guard (|h| in place of sqrt(disc), as in
+ *      rt_launch_feat_chain's step 2): for a ray that leaves that body's
+ *      surface.  last == NULL or last[i] < 0: no guard; last[i] >= the body
+ *      count names no body and is no error; nor does a body that can never be
+ *      hit (a centre or radius that is NaN or infinite, an r * r that overflows):
+ *      the guard needs no disc, so on such a body it would invent a root.
+ *   4. The record of a hit on body b at the accepted root `dist`:
+ *      t = dist * (1 / |d|), one multiplication.  The normal is hittable.clj:
+ *      24-31's (P - C) * (1 / r), with P - C rebuilt around the ray's closest
+ *      point to the centre rather than from P = o + dist * u: with oc = C - o
+ *      and h as in step 3, w_c = fma(-h, u_c, oc_c), b2 = fma(w_z, w_z,
+ *      fma(w_y, w_y, w_x * w_x)), s = sqrt(max(r * r - b2, 0)) correctly
+ *      rounded (r * r the product step 3 uses), taken with + if dist > h (the
+ *      farther root, the guard's too) and with - otherwise, and
+ *      n_c = fma(+-s, u_c, -w_c) * (1 / r).  Then hit.clj:14-15 as
+ *      rt_launch_feat reads it: front_face = dot(d, n) < 0 on the un-normalised
+ *      d, n turned against d and scaled by one correctly rounded 1 / |n|.  A
+ *      component that comes out NaN (a body of radius 0 hit in its centre) is
+ *      stored as 0, as rt_feat's sums take it.  A ray that meets nothing has
+ *      the "none" record.
+ *   5. occluded[i] = 1 iff step 3 finds a body, else 0.  The occlusion kernel
+ *      stops at the first body the test accepts against (tmin, t_max * |d|).
+ * The device follows rt_set_variant as rt_launch_ids does (5: the scan, 12: the
+ * tree in global memory, else the tree in LDS where it fits); the walk gives
+ * the scan's answer bit for bit (tests/test_rays_host.py holds that on query
+ * rays: origins far outside and deep inside bodies, t_min = 0, finite t_max,
+ * |d| from 2^-6 to 2^6).
+ *
+ * To know: dist lies within about 6e-4 * (|C - o| + r) of the exact root (the
+ * fp32 test's position error: it is the depth rt_launch_feat records, bit for
+ * bit, for the same ray).  The normal does not inherit that error: the
+ * discriminant's cancellation at the size of |C - o|^2 would put it off by
+ * 8e-3 a component on a body of r = 0.2 met 27 units away, while s comes from
+ * numbers of the size of r -- within 1e-4 of the exact normal there
+ * (tests/test_rays_host.py).  On such a hit it is more exact than the normal
+ * rt_launch_feat accumulates, and differs from it. */
+typedef struct rt_ray {      /* 32 bytes, 16-byte aligned on the device */
+  float o[3];  float t_min;  /* origin; lower bound of the ray parameter, in units of |d| */
+  float d[3];  float t_max;  /* direction, any length; upper bound, +inf = unbounded      */
+} rt_ray;
+typedef struct rt_ray_hit {  /* 32 bytes, 16-byte aligned on the device */
+  int32_t body;              /* index in the scene's array order, -1: none                */
+  int32_t front_face;        /* hit.clj:14-15: dot(d, outward normal) < 0; 0 when none    */
+  float t;                   /* ray parameter in units of |d|: dist * RN(1/|d|)           */
+  float dist;                /* the distance the search found (rt_feat's depth unit)      */
+  float normal[3];           /* (P - C) * (1/r), turned against d (hittable.clj:24-31)    */
+  float reserved;            /* 0 */
+} rt_ray_hit;
+/* raytracing.clj:33-43 and hittable.clj:7-31 for n caller-supplied rays, on the
+ * device.  Asynchronous, on hip_stream (NULL: the default stream) of ds's
+ * device: d_hits[0 .. n) is written, every word.  d_rays, d_hits: device
+ * memory, 16-byte aligned; d_last: NULL or n int32 on the device.  RT_E_ARG on
+ * a NULL argument other than d_last (the arrays may be NULL when n == 0), a
+ * misaligned d_rays or d_hits, n > 2^31 - 1, or a stream of another device --
+ * before anything is enqueued.  n == 0 is RT_OK and enqueues nothing. */
+int rt_launch_rays(const rt_dscene* ds, const rt_ray* d_rays, const int32_t* d_last, size_t n, rt_ray_hit* d_hits,
+                   void* hip_stream);
+/* raytracing.clj:33-43's "some body" for the same rays: d_occluded[0 .. n) is
+ * written, one byte a ray (step 5).  Arguments and errors as rt_launch_rays'
+ * (d_occluded needs no alignment). */
+int rt_launch_occluded(const rt_dscene* ds, const rt_ray* d_rays, const int32_t* d_last, size_t n, uint8_t* d_occluded,
+                       void* hip_stream);
+/* The same on the host, in plain C++ (no device; raytracing.clj:33-43's scan in
+ * array order with hittable.clj:7-31's test, the text the kernels run): the
+ * yardstick of the kernels, and queries against scenes that are on the host.
+ * last: NULL or n int32.  RT_E_ARG on a NULL argument other than last (with
+ * n > 0) or n > 2^31 - 1. */
+int rt_rays_host(const rt_scene* s, const rt_ray* rays, const int32_t* last, size_t n, rt_ray_hit* out);
+int rt_occluded_host(const rt_scene* s, const rt_ray* rays, const int32_t* last, size_t n, uint8_t* out);
+/* The closest-hit kernel a launch on ds would run under the current selector
+ * (diagnostic; raytracing.clj:33-43's scan as it is run): out4 as
+ * rt_ids_occupancy's. */
+int rt_rays_occupancy(const rt_dscene* ds, int* out4);
+
 /* ---- feature-guided denoiser: an a-trous filter over rt_feat's guides --------
  * What a low-sample frame of compute-pixel's loop (raytracing.clj:141-155)
  * looks like after an edge-avoiding a-trous wavelet filter (Dammertz et al.

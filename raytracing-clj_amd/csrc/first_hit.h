@@ -20,7 +20,8 @@
 //     scan, `consider_tie`), without the self-hit guard -- a camera ray
 //     leaves no body.  sqrt and 1/x are correctly rounded on either side
 //     (fp_rn.h on the device, std::sqrt and IEEE division on the host), so
-//     host and device give the same bits.
+//     host and device give the same bits.  Beside the walk, its twin for
+//     occlusion queries (fh_walk_any: out at the first body, ray_query.h).
 //  2. The device kernel (under __HIPCC__): one 256-thread workgroup per 8 x 8
 //     tile.  Lane q of each of the four waves owns pixel q of the tile; wave w
 //     traces the samples k = w, w + 4, ... of its pixels and keeps their
@@ -193,6 +194,53 @@ RT_FH_FN void fh_walk(const FhRay& r, const FhTree& t, Stack& st, FhBest& b, int
       node = i0 ? n0 : n1;
     } else if (!st.pop(node)) {
       break;
+    }
+  }
+}
+
+// The walk of an occlusion query (ray_query.h): is any body met in
+// (t-min, tmax)?  fh_walk's big-body leaves first and its padded-box cull,
+// against the fixed interval (t-min, tmax] -- nothing is "closest" here, so the
+// children are taken in tree order, no near/far compare, and the walk returns
+// at the first leaf that accepted a body.  Until then the best stays
+// {tmax, -1}, so every body meets fh_test's acceptance against that pair: the
+// predicate is "fh_scan from {tmax, -1} ends on a body", body for body.
+template <bool GUARD = false, class Stack>
+RT_FH_FN bool fh_walk_any(const FhRay& r, const FhTree& t, Stack& st, float tmax, int last = -1) {
+  FhBest b{tmax, -1};
+  for (int k = 0; k < t.n_big_leaves; ++k) {
+    fh_leaf<GUARD>(r, t, t.big_pair0 + k * t.leaf_pairs, b, last);
+    if (b.body >= 0) return true;
+  }
+  const float ex = r.ox - t.c[0], ey = r.oy - t.c[1], ez = r.oz - t.c[2];
+  const PadRay pr = pad_ray(ex, ey, ez, r.ux, r.uy, r.uz, t.r, t.c0);
+  const PadAxis ax = pad_axis(r.ux, ex, r.tmin, pr), ay = pad_axis(r.uy, ey, r.tmin, pr),
+                az = pad_axis(r.uz, ez, r.tmin, pr);
+  const unsigned offx = ax.sign >> 28, offy = 24u + (ay.sign >> 28), offz = 48u + (az.sign >> 28);
+  unsigned node = 0;
+  for (;;) {
+    const char* nb = t.base + node;
+    const float* px = reinterpret_cast<const float*>(nb + offx);
+    const float* py = reinterpret_cast<const float*>(nb + offy);
+    const float* pz = reinterpret_cast<const float*>(nb + offz);
+    const int c0 = reinterpret_cast<const int*>(nb + 72)[0], c1 = reinterpret_cast<const int*>(nb + 72)[1];
+    float tn0, tf0, tn1, tf1;
+    pad_interval(ax, ay, az, px[0], px[2], py[0], py[2], pz[0], pz[2], tn0, tf0);
+    pad_interval(ax, ay, az, px[1], px[3], py[1], py[3], pz[1], pz[3], tn1, tf1);
+    const bool hit0 = pad_meets(tn0, tf0, r.tmin, tmax), hit1 = pad_meets(tn1, tf1, r.tmin, tmax);
+    if (hit0 && c0 < 0) fh_leaf<GUARD>(r, t, ~c0, b, last);
+    if (hit1 && c1 < 0) fh_leaf<GUARD>(r, t, ~c1, b, last);
+    if (b.body >= 0) return true;
+    const bool i0 = hit0 && c0 >= 0, i1 = hit1 && c1 >= 0;
+    const unsigned n0 = static_cast<unsigned>(c0) * static_cast<unsigned>(t.ref_mul),
+                   n1 = static_cast<unsigned>(c1) * static_cast<unsigned>(t.ref_mul);
+    if (i0 && i1) {
+      st.push(n1);
+      node = n0;
+    } else if (i0 || i1) {
+      node = i0 ? n0 : n1;
+    } else if (!st.pop(node)) {
+      return false;
     }
   }
 }

@@ -1,6 +1,7 @@
 // first_hit.hip — the passes that stop at a camera ray's first hit: the feature
 // buffers (rt_feat, rt_launch_feat; first_hit.h's feat_kernel) and the body-id
 // pass (rt_launch_ids; body_ids.h's ids_kernel), with their occupancy entries;
+// the ray queries (rt_launch_rays, rt_launch_occluded; ray_query.h's kernels);
 // and the pass into the same buffers that goes on through mirrors and glass
 // (rt_launch_feat_chain; spec_chain.h's chain_kernel).  All follow the trace
 // unit's selector (dscene.h).  DESIGN.md §3.7, §3.10, §3.15.
@@ -9,6 +10,8 @@
 #include "first_hit.h"
 #define RT_BODY_IDS_KERNEL
 #include "body_ids.h"
+#define RT_RAY_QUERY_KERNEL
+#include "ray_query.h"
 #define RT_SPEC_CHAIN_KERNEL
 #include "spec_chain.h"
 #include "dscene.h"
@@ -316,6 +319,89 @@ extern "C" int rt_ids_occupancy(const rt_dscene* ds, int* out4) {
   const policy::Scene si = scene_info(*ds);
   const int src = policy::ids_source(si, selected_variant(), diag_build());
   if (const int rc = occupancy_report(ids_fn(src), kFeatThreads, policy::feat_lds(si, src), out4)) return rc;
+  out4[3] = src;
+  return RT_OK;
+}
+
+// ---- ray queries (rt.h, ray_query.h) -------------------------------------------
+static const void* rays_fn(int src, bool any) {
+  if (any)
+    return src == FEAT_LDS      ? reinterpret_cast<const void*>(&occluded_kernel<FEAT_LDS>)
+           : src == FEAT_GLOBAL ? reinterpret_cast<const void*>(&occluded_kernel<FEAT_GLOBAL>)
+                                : reinterpret_cast<const void*>(&occluded_kernel<FEAT_SCAN>);
+  return src == FEAT_LDS      ? reinterpret_cast<const void*>(&rays_kernel<FEAT_LDS>)
+         : src == FEAT_GLOBAL ? reinterpret_cast<const void*>(&rays_kernel<FEAT_GLOBAL>)
+                              : reinterpret_cast<const void*>(&rays_kernel<FEAT_SCAN>);
+}
+
+// Both launches: the checks, then one kernel whose grid is the ray blocks, at
+// most the workgroups the device holds at once (each stages the tree once and
+// takes its blocks grid-stride).
+static int launch_query(const char* who, bool any, const rt_dscene* ds, const rt_ray* d_rays, const int32_t* d_last,
+                        size_t n, rt_ray_hit* d_hits, uint8_t* d_occ, void* hip_stream) {
+  clear_error();
+  const std::string me(who);
+  if (!ds || (n > 0 && (!d_rays || (!d_hits && !d_occ)))) return set_error(RT_E_ARG, me + ": NULL argument");
+  if ((reinterpret_cast<uintptr_t>(d_rays) | reinterpret_cast<uintptr_t>(d_hits)) & 15u)
+    return set_error(RT_E_ARG, me + ": the rays and the hits must be 16-byte aligned");
+  if (n > 0x7fffffffu) return set_error(RT_E_ARG, me + ": more than 2^31 - 1 rays");
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (const int rc = stream_on_device(me, stream, ds->device, "the scene")) return rc;
+  if (n == 0) return RT_OK;
+  HIP_TRY(hipSetDevice(ds->device));
+  const policy::Scene si = scene_info(*ds);
+  const int src = policy::ids_source(si, selected_variant(), diag_build());
+  const size_t lds = policy::feat_lds(si, src);
+  const void* fn = rays_fn(src, any);
+  int per_cu = 0, cus = 0;
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kFeatThreads, lds));
+  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ds->device));
+  const size_t resident = static_cast<size_t>(std::max(per_cu, 1)) * static_cast<size_t>(std::max(cus, 1));
+  const size_t blocks = (n + kFeatThreads - 1) / kFeatThreads;
+  const DTree& tr = ds->tree[1];
+  RqArgs a{};
+  a.geo = ds->geo;
+  a.sph = ds->sph;
+  a.blob = tr.blob;
+  a.blob_f4 = tr.blob_f4;
+  a.off_pairs = tr.off_pairs;
+  a.off_pidx = tr.off_pidx;
+  a.leaf_pairs = 2;
+  a.big_pair0 = tr.big_pair0;
+  a.n_big_leaves = tr.n_big_leaves;
+  a.ref_mul = 1;   // (rt_scene_upload made the 4-body tree's inner refs byte offsets)
+  for (int k = 0; k < 3; ++k) a.bvh_c[k] = tr.c[k];
+  a.bvh_r = tr.r;
+  a.bvh_c0 = tr.c0;
+  a.n = ds->n;
+  a.n_rays = static_cast<unsigned>(n);
+  a.rays = reinterpret_cast<const float4*>(d_rays);
+  a.last = d_last;
+  a.hits = reinterpret_cast<float4*>(d_hits);
+  a.occ = d_occ;
+  HIP_TRY(enqueue(fn, dim3(static_cast<unsigned>(std::min(blocks, resident))), dim3(kFeatThreads), lds, stream, a));
+  return RT_OK;
+}
+
+extern "C" int rt_launch_rays(const rt_dscene* ds, const rt_ray* d_rays, const int32_t* d_last, size_t n,
+                              rt_ray_hit* d_hits, void* hip_stream) {
+  return launch_query("rt_launch_rays", false, ds, d_rays, d_last, n, d_hits, nullptr, hip_stream);
+}
+
+extern "C" int rt_launch_occluded(const rt_dscene* ds, const rt_ray* d_rays, const int32_t* d_last, size_t n,
+                                  uint8_t* d_occluded, void* hip_stream) {
+  return launch_query("rt_launch_occluded", true, ds, d_rays, d_last, n, nullptr, d_occluded, hip_stream);
+}
+
+// The closest-hit kernel a launch on ds would run under the current selector
+// (diagnostic, tools/rays_time.py): out4 as rt_feat_occupancy's.
+extern "C" int rt_rays_occupancy(const rt_dscene* ds, int* out4) {
+  clear_error();
+  if (!ds || !out4) return set_error(RT_E_ARG, "rt_rays_occupancy: NULL argument");
+  HIP_TRY(hipSetDevice(ds->device));
+  const policy::Scene si = scene_info(*ds);
+  const int src = policy::ids_source(si, selected_variant(), diag_build());
+  if (const int rc = occupancy_report(rays_fn(src, false), kFeatThreads, policy::feat_lds(si, src), out4)) return rc;
   out4[3] = src;
   return RT_OK;
 }

@@ -34,6 +34,7 @@
 #include "bvh_refit.h"
 #include "denoise.h"
 #include "first_hit.h"
+#include "ray_query.h"
 #include "rt_internal.h"
 #include "spec_chain.h"
 #include "temporal.h"
@@ -460,6 +461,21 @@ extern "C" int rt_feat_chain_host(const rt_scene* s, const rt_feat_chain_opts* o
   const char* why = nullptr;
   const int rc = chain_host_pass(s, opts, rays, n, out, &why);
   return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_feat_chain_host: ") + (why ? why : "failed"));
+}
+
+// rt_launch_rays and rt_launch_occluded on the host (ray_query.h's host passes:
+// the text the kernels run, over first_hit.h's guarded scan)
+extern "C" int rt_rays_host(const rt_scene* s, const rt_ray* rays, const int32_t* last, size_t n, rt_ray_hit* out) {
+  clear_error();
+  const char* why = nullptr;
+  const int rc = rays_host_pass(s, rays, last, n, out, &why);
+  return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_rays_host: ") + (why ? why : "failed"));
+}
+extern "C" int rt_occluded_host(const rt_scene* s, const rt_ray* rays, const int32_t* last, size_t n, uint8_t* out) {
+  clear_error();
+  const char* why = nullptr;
+  const int rc = occluded_host_pass(s, rays, last, n, out, &why);
+  return rc == RT_OK ? RT_OK : set_error(rc, std::string("rt_occluded_host: ") + (why ? why : "failed"));
 }
 
 // the bodies' displacement between two scenes (body_ids.h's body_motion)

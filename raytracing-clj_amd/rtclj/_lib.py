@@ -102,6 +102,21 @@ CHAIN_SAMPLE_DTYPE = [("body", "<i4"), ("bounces", "<i4"), ("length", "<f4"), ("
                       ("normal", "<f4", (3,))]
 
 
+class rt_ray(C.Structure):
+    _fields_ = [("o", C.c_float * 3), ("t_min", C.c_float), ("d", C.c_float * 3), ("t_max", C.c_float)]
+
+
+class rt_ray_hit(C.Structure):
+    _fields_ = [("body", C.c_int32), ("front_face", C.c_int32), ("t", C.c_float), ("dist", C.c_float),
+                ("normal", C.c_float * 3), ("reserved", C.c_float)]
+
+
+# rt_ray and rt_ray_hit as NumPy records (32 bytes each, no padding)
+RAY_DTYPE = [("o", "<f4", (3,)), ("t_min", "<f4"), ("d", "<f4", (3,)), ("t_max", "<f4")]
+RAY_HIT_DTYPE = [("body", "<i4"), ("front_face", "<i4"), ("t", "<f4"), ("dist", "<f4"), ("normal", "<f4", (3,)),
+                 ("reserved", "<f4")]
+
+
 # rt_upsample's defaults (include/rt.h)
 UPSAMPLE_DEFAULTS = dict(scale=2, normal_pow2=0, sigma_z=0.05)
 
@@ -291,6 +306,13 @@ SIGNATURES = {
                               C.POINTER(C.c_int32)]),
     "rt_ids_occupancy": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rt_body_motion": (C.c_int, [C.POINTER(rt_scene), C.POINTER(rt_scene), C.POINTER(C.c_float)]),
+    "rt_launch_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rt_launch_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rt_rays_host": (C.c_int, [C.POINTER(rt_scene), C.POINTER(rt_ray), C.POINTER(C.c_int32), C.c_size_t,
+                               C.POINTER(rt_ray_hit)]),
+    "rt_occluded_host": (C.c_int, [C.POINTER(rt_scene), C.POINTER(rt_ray), C.POINTER(C.c_int32), C.c_size_t,
+                                   C.POINTER(C.c_uint8)]),
+    "rt_rays_occupancy": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rt_scene_update": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_void_p]),
     "rt_tree_build_host": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                      C.POINTER(rt_tree_info)]),
@@ -343,7 +365,8 @@ ADDITIVE = {"rt_prepare", "rt_render_u8", "rt_quantize_device", "rt_render_submi
             "rt_scene_tree_read", "rt_schedule_read", "rt_schedule_sort", "rt_camera_coarsen", "rt_upsample",
             "rt_upsample_host", "rt_launch_feat_chain", "rt_feat_chain_host", "rt_feat_chain_occupancy",
             "rt_budget_trace_fused", "rt_budget_units_host", "rt_budget_units_read", "rt_budget_list_read",
-            "rt_debug_stats_ext", "rt_tile_bodies_host"}
+            "rt_debug_stats_ext", "rt_tile_bodies_host", "rt_launch_rays", "rt_launch_occluded", "rt_rays_host",
+            "rt_occluded_host", "rt_rays_occupancy"}
 
 RT_FEAT_CHANNELS = 8   # rt_feat_resolve's floats per pixel: albedo rgb, normal xyz, depth, coverage
 

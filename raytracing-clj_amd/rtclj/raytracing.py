@@ -29,7 +29,7 @@ from ._lib import (BUDGET_DEFAULTS, DENOISE_DEFAULTS, RT_DIELECTRIC, RT_FEAT_CHA
                    rt_adapt_opts, rt_budget_opts, rt_camera, i32ptr, rt_denoise_opts, rt_params, rt_scene, rt_schedule_info, rt_stats,
                    rt_temporal_clamp_opts, rt_temporal_opts, rt_tree_info, u8ptr, u32ptr, u64ptr,
                    UPSAMPLE_DEFAULTS, rt_upsample_opts, CHAIN_DEFAULTS, CHAIN_SAMPLE_DTYPE, rt_chain_sample,
-                   rt_feat_chain_opts)
+                   rt_feat_chain_opts, RAY_DTYPE, RAY_HIT_DTYPE, rt_ray, rt_ray_hit)
 
 # ---- scene (raytracing.clj:63-78) --------------------------------------------
 hittables = [
@@ -1336,6 +1336,65 @@ def ids_host(scene, cam: rt_camera, width: int, rows: int, row0: int = 0, librar
     return out
 
 
+def pinhole_rays(cam: rt_camera, width: int, rows: int, row0: int = 0) -> np.ndarray:
+    """rt_launch_ids' rays as rt_ray records, (rows, width): origin = center,
+    d = ((p00 + x * du) + j * dv) - center with j = row0 + y, each operation
+    one float32 operation rounded once, t_min = 1e-3, t_max = inf."""
+    f = np.float32
+    center, p00, du, dv = (np.array(list(v), f) for v in (cam.center, cam.p00, cam.du, cam.dv))
+    x = np.arange(int(width), dtype=f)[None, :, None]
+    j = (np.arange(int(rows), dtype=np.int64) + int(row0)).astype(f)[:, None, None]
+    rays = np.zeros((int(rows), int(width)), np.dtype(RAY_DTYPE))
+    rays["o"] = center
+    rays["d"] = ((p00 + x * du) + j * dv) - center
+    rays["t_min"] = f(1e-3)
+    rays["t_max"] = f(np.inf)
+    return rays
+
+
+def _query_args(scene, rays, last):
+    sc = scene if isinstance(scene, Scene) else Scene.from_bodies(scene)
+    rays = np.ascontiguousarray(rays, np.dtype(RAY_DTYPE))
+    if last is not None:
+        last = np.ascontiguousarray(last, np.int32)
+        if last.shape != rays.shape:
+            raise ValueError("ray query: last must have the rays' shape")
+    return sc, rays, last
+
+
+def rays_host(scene, rays, last=None, library=None) -> np.ndarray:
+    """rt_rays_host (include/rt.h): the closest hit of each caller-supplied ray
+    on the host, in plain C++ -- the records DeviceScene.intersect_into writes
+    on the device, bit for bit.  rays: a record array of RAY_DTYPE (o, t_min,
+    d, t_max), any shape; last: None, or int32 of the same shape, the body each
+    ray leaves (-1: none).  Returns RAY_HIT_DTYPE records of rays' shape: body
+    (-1: none), front_face, t, dist, normal, reserved."""
+    dll = library if library is not None else lib
+    sc, rays, last = _query_args(scene, rays, last)
+    out = np.zeros(rays.shape, np.dtype(RAY_HIT_DTYPE))
+    assert out.dtype.itemsize == C.sizeof(rt_ray_hit) and rays.dtype.itemsize == C.sizeof(rt_ray)
+    code = dll.rt_rays_host(C.byref(sc.c), rays.ctypes.data_as(C.POINTER(rt_ray)),
+                            None if last is None else i32ptr(last), rays.size,
+                            out.ctypes.data_as(C.POINTER(rt_ray_hit)))
+    if code < 0:
+        raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+    return out
+
+
+def occluded_host(scene, rays, last=None, library=None) -> np.ndarray:
+    """rt_occluded_host (include/rt.h): per ray whether any body is met in
+    (t_min, t_max) -- rays_host(...)["body"] >= 0, found with the first body
+    the test accepts.  Returns bool of rays' shape."""
+    dll = library if library is not None else lib
+    sc, rays, last = _query_args(scene, rays, last)
+    out = np.zeros(rays.shape, np.uint8)
+    code = dll.rt_occluded_host(C.byref(sc.c), rays.ctypes.data_as(C.POINTER(rt_ray)),
+                                None if last is None else i32ptr(last), rays.size, u8ptr(out))
+    if code < 0:
+        raise RTError(code, dll.rt_last_error().decode(errors="replace"))
+    return out.astype(bool)
+
+
 def body_ids_into(scene, cam: rt_camera, width: int, height: int, d_ids: int, rows=None, stream=None, device: int = 0,
                   library=None) -> None:
     """rt_launch_ids (include/rt.h) for a scene on the host: upload it, enqueue
@@ -1525,6 +1584,25 @@ class DeviceScene:
             raise ValueError("DeviceScene.update: the body count differs from the upload's")
         self._ok(self._dll.rt_scene_update(self.handle, fptr(sph) if self.n else None,
                                            C.c_void_p(stream) if stream else None))
+        return self
+
+    def intersect_into(self, d_rays: int, n: int, d_hits: int, d_last=None, stream=None):
+        """rt_launch_rays: the closest hits of n rays (device address d_rays,
+        rt_ray records) into d_hits (device address, rt_ray_hit records),
+        enqueued on `stream` (a HIP stream address; None: the default stream).
+        d_last: None or the device address of n int32, the body each ray
+        leaves.  Asynchronous."""
+        self._ok(self._dll.rt_launch_rays(self.handle, C.c_void_p(d_rays), C.c_void_p(d_last) if d_last else None,
+                                          int(n), C.c_void_p(d_hits), C.c_void_p(stream) if stream else None))
+        return self
+
+    def occluded_into(self, d_rays: int, n: int, d_occluded: int, d_last=None, stream=None):
+        """rt_launch_occluded: per ray one byte, 1 iff a body lies in
+        (t_min, t_max), into d_occluded (device address, n bytes); the other
+        arguments as intersect_into's.  Asynchronous."""
+        self._ok(self._dll.rt_launch_occluded(self.handle, C.c_void_p(d_rays), C.c_void_p(d_last) if d_last else None,
+                                              int(n), C.c_void_p(d_occluded),
+                                              C.c_void_p(stream) if stream else None))
         return self
 
     def tree_info(self, k: int) -> rt_tree_info:
